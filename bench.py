@@ -10,7 +10,10 @@ Multi-GPU: one process per GPU (torch.distributed.run); --scaling weak (default:
 own 2^18-sample batch per step) or strong (one global 2^18 batch sharded over the ranks); gradients
 summed with one RCCL all-reduce per step, inside the step's HIP graph.
 
-At N=1 the JSON line also carries (rank 0, after the timed region):
+A plain run sets up, warms up, times the K steps (--steps; ms_per_step = their wall time / K), writes
+--dump-outputs and prints the result line. Everything below runs only with --full.
+
+At N=1 the JSON line of a --full run also carries (rank 0, after the timed region):
   roofline      the dominant region's algorithmic bytes (or FLOPs) per launch / its HIP-event time;
                 regions: grid forward, grid backward (bucket scan + plan + scatter + accumulate + split
                 reduce), fused MLP training kernel, optimizer (46 B per updated parameter, 16 B per
@@ -231,16 +234,25 @@ def read_profiler(lib):
     return json.loads(cbuf.value.decode())
 
 
-def timed_steps(lib, step, steps, warmup, world, capture=None, comm=None):
+GRAPH_MAX_STEPS = 500   # steps per captured HIP graph: a longer timed region is several launches queued back to back
+GRAPH_WARM_STEPS = 200  # untimed graph replays before the timed launch cover at least this many steps
+
+
+def timed_steps(lib, step, steps, warmup, world, capture=None, comm=None, replay=True, after_timed=None):
     """W untimed warmup steps, then K steps between barrier + synchronize on both sides (one captured
-    HIP graph of K steps when `capture` gives one), then the same K steps replayed eagerly with the
-    engine's per-kernel HIP events (queued behind graph launches so the events bracket kernels only).
+    HIP graph of K steps when `capture` gives one; K > GRAPH_MAX_STEPS: graphs of GRAPH_MAX_STEPS steps
+    and one of the remainder, all queued before the closing synchronize), then, with `replay`, the same K
+    steps again, eagerly, with the engine's per-kernel HIP events (queued behind graph launches so the
+    events bracket kernels only).
     `step` must run what the graph runs (Trainer.train_step is the eager form of a captured step).
     comm: a host-side exchange (dp.HostComm) whose own round-trip timer stands in for the engine
-    profiler's "allreduce" region. Returns (seconds for the K timed steps, launch mode, per-phase
-    profiler dict)."""
+    profiler's "allreduce" region. after_timed: called right after the timed region, before any replay
+    (the state it sees is what the last timed step left). The number of steps run before the timed region
+    depends on K and W alone, so the timed steps see the same inputs in every run. Returns (seconds for
+    the K timed steps, launch mode, per-phase profiler dict: empty for a graph launch without replay)."""
     stream = torch.cuda.Stream()
     graph_note = None
+    graphs = []
     with torch.cuda.stream(stream):
         for _ in range(warmup):
             step()
@@ -248,19 +260,23 @@ def timed_steps(lib, step, steps, warmup, world, capture=None, comm=None):
         graph = None
         if capture is not None:
             try:
-                graph = capture(steps)
-                # untimed replays: graph upload / first-launch costs, then at least ~25 ms of GPU work before the
-                # timed launch. A short warmup leaves the clocks ramping into the timed region: at K = 20 after 5
-                # warmup steps the first timed launch ran 146 us/step and every later one 135-138
+                chunk = min(steps, GRAPH_MAX_STEPS)
+                graph = capture(chunk)
+                graphs = [(graph, steps // chunk)]
+                if steps % chunk:
+                    graphs.append((capture(steps % chunk), 1))
+                # untimed replays: graph upload / first-launch costs, then ~25 ms of GPU work (GRAPH_WARM_STEPS
+                # C2 steps; a fixed count, not a wall-clock test, so that every run trains the same number of steps)
+                # before the timed launch. A short warmup leaves the clocks ramping into the timed region: at K = 20
+                # after 5 warmup steps the first timed launch ran 146 us/step and every later one 135-138
                 # (tools/graph_probe.py, profiles/r05e_graph_probe.jsonl)
-                t_w = time.perf_counter()
-                for i in range(16):
+                for g, _ in graphs[1:]:
+                    g.launch()
+                for _ in range(min(16, max(2, -(-GRAPH_WARM_STEPS // chunk)))):
                     graph.launch()
                     torch.cuda.synchronize()
-                    if i >= 1 and time.perf_counter() - t_w > 0.025:
-                        break
             except Exception as e:  # same HIP kernels, launched one by one
-                graph, graph_note = None, f"graph capture failed ({e}); eager launches"
+                graph, graph_note, graphs = None, f"graph capture failed ({e}); eager launches", []
                 print(f"[bench] {graph_note}", file=sys.stderr, flush=True)
         if graph is None:
             lib.ngp_profiler_reset()
@@ -272,7 +288,9 @@ def timed_steps(lib, step, steps, warmup, world, capture=None, comm=None):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         if graph is not None:
-            graph.launch()
+            for g, launches in graphs:
+                for _ in range(launches):
+                    g.launch()
         else:
             for _ in range(steps):
                 step()
@@ -280,19 +298,57 @@ def timed_steps(lib, step, steps, warmup, world, capture=None, comm=None):
         if world > 1:
             dist.barrier()
         t1 = time.perf_counter()
-        if graph is not None:
+        if after_timed is not None:
+            after_timed()
+        if graph is not None and replay:
             lib.ngp_profiler_reset()
-            for _ in range(3):  # ~3x the host's enqueue time of K eager steps
+            for _ in range(3 * graphs[0][1]):  # ~3x the host's enqueue time of K eager steps
                 graph.launch()
             lib.ngp_profiler_enable(1)
             for _ in range(steps):
                 step()
             torch.cuda.synchronize()
         lib.ngp_profiler_enable(0)
-    prof = read_profiler(lib)
+    prof = read_profiler(lib) if graph is None or replay else {}
     if hasattr(comm, "reset_timer") and comm.calls and "allreduce" not in prof:
         prof["allreduce"] = {"ms": comm.ms, "calls": comm.calls, "timer": "host round trip (gloo)"}
     return t1 - t0, ("hip_graph" if graph is not None else (graph_note or "eager")), prof
+
+
+# The synthetic dL/doutput is the same array every step and no loss gradient: nothing pulls the weights back, and
+# Adam moves each one by about its learning rate per step whatever the gradient's size. At the config's 1e-2 the
+# weights left fp16's range within a few hundred steps (after 260, 4439 of C2's 9216 MLP weights were NaN), so
+# the default run's steps were timed, and would be dumped, on NaN. The same kernels move the same bytes at any rate; at 1e-7
+# the drift over 10^5 steps is 1e-2, the grid entries (U(+-1e-4) at start) still change visibly from the first
+# step, and the weights stay where a trained model's are.
+SYNTHETIC_LR = 1e-7
+
+DUMP_MAX_ELEMS = 7 << 20  # per dumped array (float32: 28 MiB; two arrays stay under 64 MB)
+
+
+def snapshot_outputs(net, trainer, world):
+    """What a caller of the timed step holds after it, as host float32 arrays: `params`, the trainer's fp16
+    parameters the step updated (grid and MLPs), and at N = 1 `mlp_gradients`, the fp16 gradients of the MLP
+    matrices that its backward stored (the grid's part of the gradient buffer is not written when the update is
+    fused into the backward). An array of more than DUMP_MAX_ELEMS elements is sampled at fixed positions
+    (sorted draws of default_rng(0))."""
+    torch.cuda.synchronize()
+    arrays = {"params": trainer.params}
+    if world == 1:
+        arrays["mlp_gradients"] = trainer.gradients[:int(net.n_matrix_params)]
+    out = {}
+    for name, t in arrays.items():
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), DUMP_MAX_ELEMS))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        out[name] = t.float().cpu().numpy()
+    return out
+
+
+def write_outputs(directory, arrays):
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def nerf_pass(pkg, variant, n, rank, world, opts=(), overlap=None, wire="f32", shard=True, exchange_at_world_1=False,
@@ -309,6 +365,7 @@ def nerf_pass(pkg, variant, n, rank, world, opts=(), overlap=None, wire="f32", s
         k, v = kv.split("=")
         net.set_option(k, float(v))
     trainer = pkg.Trainer(net, cfg["optimizer"], seed=1337)
+    trainer.learning_rate = SYNTHETIC_LR
     net.reserve(n)
     x, dL = synthetic_batch(n, 1337 + rank, "cuda")
     comm = None
@@ -538,6 +595,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything else the docstring lists: the per-kernel replay and "
+                         "roofline, the CPU baseline, the other configurations (c2p, c5, c5_online, c3), dp1_overhead, e2e, "
+                         "and at N > 1 the in-job 1-GPU reference, the other scaling mode and the data-parallel e2e")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left (snapshot_outputs) as DIR/<name>.npy, float32 (rank 0)")
     ap.add_argument("--variant", default="C2", choices=["C2", "C2p", "C5", "IMG"])
     ap.add_argument("--batch", type=int, default=B)
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
@@ -598,7 +661,7 @@ def main():
     lib = pkg.lib()
 
     vs1 = None
-    if world > 1 and args.variant in ("C2", "C2p") and not args.no_vs1:
+    if args.full and world > 1 and args.variant in ("C2", "C2p") and not args.no_vs1:
         # the 1-GPU reference for the N-vs-1 ratios, measured in this job: rank 0 alone trains the same
         # --batch per step with no exchange, launched like the N-rank passes; the other ranks wait
         if rank == 0:
@@ -619,7 +682,7 @@ def main():
         step, capture, net, trainer, comm = nerf_pass(pkg, args.variant, n, rank, world, args.opt, args.overlap,
                                                       args.wire, shard=bool(args.dp_shard), dp_parts=args.dp_parts,
                                                       dp_wire16=bool(args.dp_wire16))
-        if not args.no_opt_count:
+        if args.full and not args.no_opt_count:
             *n_opt, c5_fused = optimizer_counts(net, trainer, step, fused=trainer.fused_update_active(n))
         if not args.graph:
             capture = None
@@ -627,7 +690,7 @@ def main():
         if world > 1:
             raise SystemExit("C5 bench is single-GPU")
         step, net, trainer = c5_pass(pkg, n, rank)
-        if not args.no_opt_count:
+        if args.full and not args.no_opt_count:
             *n_opt, c5_fused = optimizer_counts(net, trainer, step, fused=True)
         capture = None
     else:  # IMG
@@ -645,11 +708,17 @@ def main():
         capture = None
 
     n_params_total = net.n_params
-    dt, launch, kernels = timed_steps(lib, step, args.steps, args.warmup, world, capture, comm)
+    dumped = {}
+    snap = (lambda: dumped.update(snapshot_outputs(net, trainer, world))) if args.dump_outputs and rank == 0 else None
+    dt, launch, kernels = timed_steps(lib, step, args.steps, args.warmup, world, capture, comm, replay=args.full,
+                                      after_timed=snap)
+    if snap is not None:
+        write_outputs(args.dump_outputs, dumped)
     slab_b = slab_reduction_bytes(lib, net)
     param_hashes = None
     if world > 1:
         dt = pkg.dp.reduce_scalar(dt, "max")
+    if world > 1 and args.full:
         # data parallelism keeps every rank's parameters identical (same all-reduced gradient, same update)
         import hashlib
         torch.cuda.synchronize()
@@ -657,7 +726,7 @@ def main():
         dist.all_gather_object(param_hashes, hashlib.sha1(trainer.params.cpu().numpy().tobytes()).hexdigest())
 
     strong = None
-    if world > 1 and args.variant in ("C2", "C2p") and not args.no_strong:
+    if args.full and world > 1 and args.variant in ("C2", "C2p") and not args.no_strong:
         # the other scaling mode in the same line: weak = fixed batch per GPU (headline), strong = one
         # global --batch sharded over the N ranks
         n_s = args.batch // world if args.scaling == "weak" else args.batch
@@ -672,7 +741,7 @@ def main():
                   "exchange_ms_per_step": exchange_ms(k_s)}
         del s_s, c_s, comm_s
     e2e_dp = e2e_dp_weak = None
-    if world > 1 and args.variant == "C2" and args.e2e_seconds > 0:
+    if args.full and world > 1 and args.variant == "C2" and args.e2e_seconds > 0:
         # the metric's full form on N GPUs: the Testbed NeRF step data-parallel (rays sharded with their
         # global ids, RCCL all-reduce of gradients, density-grid maxima and counters), then PSNR on rank 0.
         # strong: the 1-GPU batch over N ranks (the 1-GPU ray set); weak: 2^18 samples per rank
@@ -685,7 +754,6 @@ def main():
                                      rank=rank, world=world, scaling="weak", dp_wire16=bool(args.dp_wire16))
 
     if rank == 0:
-        kern_summary, rl = roofline(args.variant, n, kernels, *n_opt, slab_bytes=slab_b, fused_grid_updated=c5_fused)
         res = {
             "metric": "training samples/sec + PSNR@30s, NeRF Lego at 1/2/4/8 MI355X",
             "value": n * world * args.steps / dt,
@@ -708,16 +776,22 @@ def main():
                                     + (" (engine RCCL communicator, inside the step's graph)" if args.comm == "rccl" else
                                        " (gloo host round trips)")
                                     if world > 1 else None)},
-            "kernel_timing": ("HIP events per kernel on the launch stream, eager replay of the same K steps queued "
-                              "behind a graph launch" if launch == "hip_graph" else "HIP events per kernel over the timed region"),
-            "roofline": rl,
-            "optimizer_params": ({"updated": n_opt[0], "skipped": n_opt[1]} if c5_fused is None else
-                                 {"mlp_updated": n_opt[0], "grid_updated_in_backward": c5_fused}),
-            "kernels_sum_ms": kernels_sum_ms(kernels),
-            "kernels": kern_summary,
+            "full": args.full,
         }
+        if args.full:
+            kern_summary, rl = roofline(args.variant, n, kernels, *n_opt, slab_bytes=slab_b, fused_grid_updated=c5_fused)
+            res.update({
+                "kernel_timing": ("HIP events per kernel on the launch stream, eager replay of the same K steps queued "
+                                  "behind a graph launch" if launch == "hip_graph" else "HIP events per kernel over the timed region"),
+                "roofline": rl,
+                "optimizer_params": ({"updated": n_opt[0], "skipped": n_opt[1]} if c5_fused is None else
+                                     {"mlp_updated": n_opt[0], "grid_updated_in_backward": c5_fused}),
+                "kernels_sum_ms": kernels_sum_ms(kernels),
+                "kernels": kern_summary,
+            })
         if world > 1:
-            res["exchange_ms_per_step"] = exchange_ms(kernels)
+            if args.full:
+                res["exchange_ms_per_step"] = exchange_ms(kernels)
             q = 8 * world
             n_pad = (int(n_params_total) + q - 1) // q * q
             res["exchange_bytes"] = ({"reduce_scatter_f16" if args.dp_wire16 else "reduce_scatter_f32":
@@ -725,7 +799,8 @@ def main():
                                      {"all_reduce": (4 if args.wire == "f32" else 2) * int(n_params_total)})
             if strong is not None:
                 res["strong"] = strong
-            res["param_sha1_per_rank"] = param_hashes
+            if param_hashes is not None:
+                res["param_sha1_per_rank"] = param_hashes
             if vs1 is not None:
                 # N-vs-1 from this job's own 1-GPU pass: weak = N x batch per step over N GPUs, strong = one
                 # batch per step over N GPUs, both against one GPU training one batch per step
@@ -740,7 +815,8 @@ def main():
             if e2e_dp is not None:
                 res["e2e"] = {k: e2e_dp[k] for k in ("value", "unit", "psnr", "psnr_views", "train_seconds", "steps",
                                                      "ms_per_step", "n_gpus", "data", "config")}
-        if world == 1 and args.variant in ("C2", "C2p") and not args.no_dp1 and not args.pmc_collect and args.comm == "rccl":
+        if (args.full and world == 1 and args.variant in ("C2", "C2p") and not args.no_dp1 and not args.pmc_collect
+                and args.comm == "rccl"):
             # (not in counter-collection runs: their summaries describe the headline step's kernels alone)
             # the data-parallel step's own cost, measured where it can be (one GPU): the same pass with the
             # engine's RCCL communicator attached at world 1, timed like the headline (one graph of K steps),
@@ -764,7 +840,7 @@ def main():
                     "phases_us": {k: round(v["ms"] / max(v["calls"], 1) * 1e3, 2) for k, v in kd.items()}}
                 del sd, cd, commd
             torch.cuda.synchronize()
-        if world == 1 and args.variant == "C2":
+        if args.full and world == 1 and args.variant == "C2":
             if not args.no_c2p:
                 # BASELINE's literal "L=16": the same training pass at C2' (L=16 F=2 T=2^19)
                 s2, c2, net2, tr2, _ = nerf_pass(pkg, "C2p", n, 0, 1)
@@ -822,7 +898,7 @@ def main():
                                                    "train_seconds", "steps", "ms_per_step", "data", "config")}
                 else:
                     res["c3"] = {"skipped": "data/fox not staged (tools/stage_fox.sh copies it from the reference tree)"}
-        if world == 1 and not args.no_cpu_baseline and args.variant in ("C2", "C2p"):
+        if args.full and world == 1 and not args.no_cpu_baseline and args.variant in ("C2", "C2p"):
             res["cpu_baseline"] = cpu_baseline(args.variant)
         print(json.dumps(res), flush=True)
     if world > 1:

@@ -57,7 +57,8 @@ def test_launched_ranks_see_world(tmp_path):
         "import bench\n"
         "need, world = bench.check_world(int(sys.argv[2]))\n"
         "assert not need and world == dist.get_world_size()\n"
-        "print('rank', dist.get_rank(), 'world', world, flush=True)\n"
+        # one write per rank: the ranks share the pipe, and an unbuffered print() writes its pieces one by one
+        "os.write(1, f'rank {dist.get_rank()} world {world}\\n'.encode())\n"
         "dist.destroy_process_group()\n")
     b = _bench()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",

@@ -1,6 +1,6 @@
 """bench.py's N > 1 flow executed end to end on the box's one GPU (BASELINE C4).
 
-`bench.py --gpus 2 --comm gloo --device 0` starts two rank processes itself (torch.distributed.run on
+`bench.py --full --gpus 2 --comm gloo --device 0` starts two rank processes itself (torch.distributed.run on
 127.0.0.1) that share device 0 and exchange gradients through gloo (a host round trip per step), so every
 line of the multi-rank code path runs: the in-job 1-GPU reference pass, the weak-scaling headline, the
 strong-scaling sub-record, the all-reduce timing, the parameter hashes gathered from both ranks and the
@@ -21,7 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_two_ranks_gloo_line():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--comm", "gloo", "--device", "0", "--graph", "0",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--comm", "gloo", "--device", "0", "--graph", "0",
            "--steps", "3", "--warmup", "1", "--e2e-seconds", "2", "--e2e-weak-seconds", "2", "--e2e-images", "8", "--e2e-res", "128",
            "--c3-seconds", "0", "--no-cpu-baseline"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")

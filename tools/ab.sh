@@ -1,7 +1,7 @@
 # A/B runs on one GPU box: optional parity tests, then bench.py (and optionally the NeRF step profile) for each
 # variant, interleaved twice so that clock drift hits every variant alike. One summary line per run.
 #
-#   bash tools/ab.sh TAG [-t "test files"] [-b "bench.py args"] [-n] VARIANT...
+#   bash tools/ab.sh TAG [-t "test files"] [-b "bench.py args" (--full for the c2p, c5 and per-kernel columns)] [-n] VARIANT...
 #
 # VARIANT = name[:KEY=VAL,KEY=VAL...]. KEY is an environment variable for that run (NGP_MODEL_OPTS="k=v;k=v"
 # sets engine options on every model, NGP_SC_* the grid-backward plan knobs, ...), or lib=DIR to load
@@ -10,7 +10,7 @@
 # gpurun_out/TAG/.  Example: bash tools/ab.sh r04x -t tests/test_gpu_network_full.py new old:NGP_MODEL_OPTS="fuse_slabs=0"
 set -e -o pipefail
 T=$1; shift
-TESTS=""; BENCH="--no-cpu-baseline --e2e-seconds 0 --c3-seconds 0"; NERF=""
+TESTS=""; BENCH="--full --no-cpu-baseline --e2e-seconds 0 --c3-seconds 0"; NERF=""
 while getopts "t:b:n" o; do
   case $o in t) TESTS=$OPTARG ;; b) BENCH=$OPTARG ;; n) NERF=1 ;; *) exit 2 ;; esac
 done

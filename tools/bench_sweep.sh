@@ -12,7 +12,7 @@ for c in "${CASES[@]}"; do
   for tok in $c; do
     if [[ "$tok" != --* && "$tok" == *=* ]]; then envs+=("$tok"); else args+=("$tok"); fi
   done
-  timeout -k 10 300 env "${envs[@]}" python bench.py --no-cpu-baseline "${args[@]}" > "$OUT/case$i.json" 2> "$OUT/case$i.err"
+  timeout -k 10 300 env "${envs[@]}" python bench.py --full --no-cpu-baseline "${args[@]}" > "$OUT/case$i.json" 2> "$OUT/case$i.err"
   python3 -c "
 import json,sys
 d=json.load(open('$OUT/case$i.json'))

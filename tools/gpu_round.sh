@@ -20,12 +20,12 @@ if has smoke; then
   tail -2 "$OUT/smoke.log"
 fi
 if has bench; then
-  timeout -k 10 400 python bench.py ${BENCH_ARGS} > "$OUT/bench.json" 2> "$OUT/bench.err"
+  timeout -k 10 400 python bench.py --full ${BENCH_ARGS} > "$OUT/bench.json" 2> "$OUT/bench.err"
   cat "$OUT/bench.json"
 fi
 if has prof; then
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/prof" -o run -- \
-      python3 bench.py --no-cpu-baseline --e2e-seconds 0 --c3-seconds 0 --no-c5 --pmc-collect ${PMC_ARGS} > "$OUT/prof_bench.json" 2> "$OUT/prof.err"
+      python3 bench.py --full --no-cpu-baseline --e2e-seconds 0 --c3-seconds 0 --no-c5 --pmc-collect ${PMC_ARGS} > "$OUT/prof_bench.json" 2> "$OUT/prof.err"
   find "$OUT/prof" -name '*kernel_stats.csv' -exec cp {} "$OUT/kernel_stats.csv" \;
   rm -rf "$OUT/prof"
   head -12 "$OUT/kernel_stats.csv"
