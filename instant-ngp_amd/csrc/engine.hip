@@ -178,6 +178,8 @@ struct ngp_model {
 	bool fuse_opt = true;                   // option "fuse_opt": lazy-layout optimizer update inside the grid backward (training_step)
 	bool fuse_mlp_opt = true;               // option "fuse_mlp_opt": ... and the MLP section's update in its dW slab blocks (no optimizer launch)
 	bool grid_bricks = false;               // option "grid_bricks": dense levels of the bucketed backward summed per brick (off: measured slower)
+	bool grid_direct = true;                // option "grid_direct": levels of at most two buckets summed without items (ScatterPlan::direct_mask)
+	bool grid_plan_inline = false;          // option "grid_plan_inline": no k_sc_plan launch where the bucket list is small (ScatterPlan::plan_inline; off: measured slower)
 	hipStream_t side = nullptr;             // overlaps fragments + bucket histogram with forward + MLP,
 	                                        // and the dW slab reduction with the grid backward
 	hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_frags = nullptr, ev_mlp = nullptr, ev_red = nullptr;
@@ -241,7 +243,7 @@ struct ngp_model {
 	bool side_prepare(uint32_t n) const { return use_sorted(n) && (overlap & 1); }
 	const ScatterPlan& sc_plan_for(uint32_t n) {
 		if (sc_plan_n != n) {
-			sc_plan = make_scatter_plan(grid, n, grid_bricks);
+			sc_plan = make_scatter_plan(grid, n, grid_bricks, grid_direct, grid_plan_inline);
 			sc_plan_n = n;
 			fb_dirty = true;  // the brick fallback table may now lie over bytes the previous plan used (items)
 		}
@@ -990,6 +992,12 @@ int ngp_model_set_option(ngp_model* m, const char* key, double value) {
 		} else if (k == "grid_bricks") {
 			m->grid_bricks = value != 0;
 			m->sc_plan_n = 0;  // re-plan at the next batch
+		} else if (k == "grid_direct") {
+			m->grid_direct = value != 0;
+			m->sc_plan_n = 0;
+		} else if (k == "grid_plan_inline") {
+			m->grid_plan_inline = value != 0;
+			m->sc_plan_n = 0;
 		} else if (k == "win_debug") {
 			m->win_debug = (uint32_t)value;
 		} else {
@@ -1006,6 +1014,9 @@ int ngp_model_query(const ngp_model* m, const char* key, double* value) {
 	NGP_TRY({
 		const std::string k = key;
 		if (k == "grid_brick_levels") *value = m->sc_plan_n ? (double)(m->sc_plan.bk.LD - m->sc_plan.bk.LB) : 0.0;
+		else if (k == "grid_direct_levels") *value = m->sc_plan_n ? (double)m->sc_plan.direct_levels : 0.0;
+		else if (k == "grid_direct_part") *value = (double)make_scatter_plan(m->grid, 4096, false).direct_part;
+		else if (k == "grid_plan_inline") *value = m->sc_plan_n && m->sc_plan.plan_inline ? 1.0 : 0.0;
 		else throw Error("unknown model query: " + k);
 	});
 }

@@ -61,6 +61,7 @@ struct GridHist {
 	uint32_t B, n_chunks, chunk;
 	uint32_t vb_base[33];
 	uint32_t brick_first = 0, brick_levels = 0, n_bricks = 0, brick_cells = 8, bricks_per_dim = 0, brick_vb0 = 0;  // levels [first, levels)
+	uint32_t direct_levels = 0;  // levels [0, direct_levels) have no items (ScatterPlan::direct_mask): not counted
 };
 
 // mode: 0/1 per-sample kernels, 2 XCD-partitioned (level, chunk) kernel (L2-local tables; measured

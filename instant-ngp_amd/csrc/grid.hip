@@ -152,7 +152,8 @@ __global__ void __launch_bounds__(HIST ? 512 : 256) k_grid_forward_rows(const Gr
 #pragma unroll
 		for (uint32_t f = 0; f < F; ++f) acc[f] = 0.f;
 		const bool active = l < c.n_levels && !((float)l >= ml + 1e-3f);
-		const bool count = HIST && !(l >= h.brick_first && l < h.brick_levels);  // brick levels: counted once per sample above
+		// brick levels: counted once per sample above; direct levels: no items
+		const bool count = HIST && !(l >= h.brick_first && l < h.brick_levels) && l >= h.direct_levels;
 		if (count && l < c.n_levels && !active) {
 			// the backward stages items for masked levels too (with zero values): count them
 			float frac[D]; uint32_t base[D];

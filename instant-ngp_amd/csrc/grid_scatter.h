@@ -29,14 +29,25 @@ struct ScatterPlan {
 	uint32_t spb = 0;        // samples per chunk (hist/scatter blocks are (chunk, level))
 	uint32_t n_chunks = 0;
 	uint32_t max_lb = 0;     // most buckets any one level spans
-	uint64_t n_items = 0;    // n * L * 2^D contributions
+	uint64_t n_items = 0;    // n * 2^D contributions per item level
 	uint32_t split_limit = 0;// buckets with more items are summed in parts (k_sc_plan)
 	uint32_t part = 0;
 	uint32_t max_split_blocks = 0;
 	uint32_t max_split_buckets = 0;
 	uint32_t xcd_map = 2;    // scatter block order: 2 = a chunk's level blocks and neighbouring chunks share an XCD
 	uint32_t bt = 1024;      // bucket accumulation block threads (experiment knob NGP_SC_BT)
-	BrickConst bk;           // bk.LD = 0: every level through items
+	BrickConst bk;           // bk.LD = 0: no brick levels
+	// Direct levels: a level of at most two buckets (its whole table fits one or two LDS tiles; always the leading
+	// direct_levels levels) is not sorted into items. Its buckets keep their numbers but get no histogram counts,
+	// no scatter blocks and no items; direct part blocks of k_sc_accumulate, one per (direct bucket, range of
+	// direct_part samples), recompute the contributions from the positions and dL/dy, sum them in LDS and store a
+	// slab each, and k_sc_split_reduce adds a bucket's direct_parts slabs like a split bucket's parts. Not with
+	// bricks or F = 8. With BwdParts they stay on: every direct part runs in the first range's launch.
+	uint32_t direct_mask = 0, direct_levels = 0, direct_buckets = 0;
+	uint32_t direct_part = 0, direct_parts = 0;  // samples per direct part; parts = ceil(n / direct_part)
+	// No k_sc_plan launch (at most 1024 buckets, no bricks): the scatter, accumulate and split-reduce blocks derive the
+	// bucket starts and the split lists they read from the bucket totals (same integers, so the same parts)
+	bool plan_inline = false;
 	uint32_t brick_part = 1024;  // samples per brick part (parts of one brick each store a slab)
 	// workspace layout (bytes)
 	size_t off_hist = 0, off_cur = 0, off_tot = 0, off_split = 0, off_lo = 0, off_splitb = 0, off_scratch = 0, off_idx = 0, off_val = 0,
@@ -46,7 +57,8 @@ struct ScatterPlan {
 };
 
 // bricks: allow the brick-summed dense levels (ScatterPlan::bk; chosen only where they move fewer bytes)
-ScatterPlan make_scatter_plan(const GridDesc& g, uint32_t n, bool bricks = true);
+// direct: allow direct levels (ScatterPlan::direct_mask; off with bricks); plan_inline: allow ScatterPlan::plan_inline
+ScatterPlan make_scatter_plan(const GridDesc& g, uint32_t n, bool bricks = true, bool direct = true, bool plan_inline = false);
 // Phase 1 (positions only, so it can run on a side stream while the forward pass and the MLP run):
 // bucket histogram per block of samples + per-bucket scans.
 // hist_done: the histogram was produced by the training forward (scatter_hist, grid_forward).

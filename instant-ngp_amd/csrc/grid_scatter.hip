@@ -27,6 +27,12 @@
 //                     zero LDS, accumulate, store every entry once (no memset, no atomics)
 //     k_sc_split_reduce  per oversized bucket: sum its parts (exact), write every entry once
 //
+// Direct levels (ScatterPlan::direct_mask): a level of at most two buckets (C2's level 0) has no histogram counts, no
+// scatter blocks and no items. Direct part blocks in front of k_sc_accumulate, one per (direct bucket, range of
+// samples), form the same contributions from the positions and dL/dy, sum them in LDS and store a slab each; the
+// plan lists the level's buckets as split buckets with those static parts, so k_sc_split_reduce sums them.
+// Inline plan (ScatterPlan::plan_inline, off by default): no k_sc_plan launch, the consumers scan the totals themselves.
+//
 // Bricks (ScatterPlan::bk, 3D grids): the leading dense levels (C2: 0-2 of 4) do not go through items. The
 // histogram counts each sample once in its brick (K^3 cells of the finest of those levels), the scatter's
 // brick slot writes the sample's index as its one item, every non-empty brick is a "split" bucket whose
@@ -155,6 +161,10 @@ __device__ __forceinline__ void load_pos(const GridBwdArgs& a, uint32_t i, float
 
 struct Levels {
 	uint32_t vb_base[33];  // first bucket of each level; vb_base[L] = number of buckets (bricks first: vbs [0, NBK))
+	// direct levels [0, nd) (ScatterPlan::direct_mask): their buckets [0, vb_base[nd)) get no items; dP parts of dS
+	// samples each store a slab per bucket, bucket v's in scratch slots [v * dP, (v + 1) * dP)
+	uint32_t nd = 0, dS = 0, dP = 0;
+	uint32_t level_items = 0;  // n * 2^D: item level q starts at item q * level_items (inline plan)
 };
 
 // sample index as a brick item: low 16 bits in the idx slot, high 16 in the first value element
@@ -198,6 +208,10 @@ __global__ void __launch_bounds__(SC_THREADS) k_sc_hist(const GridConst c, const
 		return;
 	}
 	const uint32_t nvb = lv.vb_base[l + 1] - lv.vb_base[l];
+	if (l < lv.nd) {  // direct level: no items, its buckets' counts stay 0
+		for (uint32_t j = threadIdx.x; j < nvb; j += blockDim.x) hist[(size_t)chunk * lv.vb_base[c.n_levels] + lv.vb_base[l] + j] = 0;
+		return;
+	}
 	const uint32_t few_bits = nvb <= 1 ? 0u : nvb <= 2 ? 1u : nvb <= 4 ? 2u : nvb <= 8 ? 3u : nvb <= 16 ? 4u : 32u;
 	for (uint32_t j = threadIdx.x; j < nvb; j += blockDim.x) h[j] = 0;
 	__syncthreads();
@@ -308,7 +322,7 @@ __global__ void __launch_bounds__(SC_PLAN_THREADS) k_sc_plan(const uint32_t* __r
                                                              uint32_t part, uint32_t* __restrict__ lo_out,
                                                              uint32_t* __restrict__ split, uint32_t* __restrict__ splitb,
                                                              uint32_t brick_vb0, uint32_t n_bricks, uint32_t brick_part, uint32_t* __restrict__ bp,
-                                                             uint32_t* __restrict__ fb_flag) {
+                                                             uint32_t* __restrict__ fb_flag, uint32_t nd_b, uint32_t dP) {
 	// bricks (vbs [brick_vb0, + n_bricks)): every non-empty one is summed in parts of brick_part samples, each storing a
 	// slab; bp[2 b] = first part, bp[2 b + 1] = parts. They are not split buckets of k_sc_split_reduce.
 	if (fb_flag && threadIdx.x == 0) *fb_flag = 0u;  // the previous step's finalize has read and cleared the fallback
@@ -319,7 +333,10 @@ __global__ void __launch_bounds__(SC_PLAN_THREADS) k_sc_plan(const uint32_t* __r
 	constexpr bool VEC = SC_PLAN_K % 4 == 0;
 	uint32_t K = min(SC_PLAN_K, (n_vb + SC_PLAN_THREADS - 1) / SC_PLAN_THREADS);
 	if (VEC) K = (K + 3) & ~3u;
-	uint32_t c_lo = 0, c_parts = 0, c_sb = 0;
+	// direct buckets [0, nd_b) (total 0: no items): split buckets 0..nd_b-1 with dP slabs each in the leading
+	// scratch slots, written by the accumulate's direct parts; the lists of the item buckets follow them
+	for (uint32_t v = threadIdx.x; v < nd_b; v += SC_PLAN_THREADS) { splitb[3 * v] = v; splitb[3 * v + 1] = v * dP; splitb[3 * v + 2] = dP; }
+	uint32_t c_lo = 0, c_parts = nd_b * dP, c_sb = nd_b;
 	for (uint32_t b0 = 0; b0 < n_vb; b0 += SC_PLAN_THREADS * K) {
 		const uint32_t v0 = b0 + threadIdx.x * K;
 		uint32_t t[SC_PLAN_K];
@@ -401,6 +418,49 @@ __global__ void __launch_bounds__(SC_PLAN_THREADS) k_sc_plan(const uint32_t* __r
 	if (threadIdx.x == 0) { split[0] = c_parts; split[1] = c_sb; }
 }
 
+// Inline plan (ScatterPlan::plan_inline: at most SC_PLAN_THREADS buckets, no bricks): k_sc_plan is not launched and
+// every consumer derives what it would have read from the bucket totals, which the scan has written when the consumer
+// starts (launch order; nothing waits on another block). plan_scan is k_sc_plan's arithmetic by one block of any size:
+// visit(vb, total, lo, first part, split bucket index, parts) for every bucket — the same integers, so the same parts.
+struct PlanShared {
+	uint32_t wsum[3][SC_PLAN_THREADS / 64];
+	uint32_t res[3];
+};
+template <class Fn>
+__device__ __forceinline__ void plan_scan(const uint32_t* __restrict__ tot, uint32_t n_vb, uint32_t split_limit, uint32_t part,
+                                          uint32_t first0, uint32_t sb0, PlanShared& sh, Fn visit) {
+	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+	uint32_t c0 = 0, c1 = first0, c2 = sb0;
+	for (uint32_t b0 = 0; b0 < n_vb; b0 += blockDim.x) {
+		const uint32_t vb = b0 + threadIdx.x;
+		const uint32_t t = vb < n_vb ? tot[vb] : 0u;
+		const uint32_t sp = t > split_limit ? 1u : 0u, np = sp ? (t + part - 1) / part : 0u;
+		const uint32_t i0 = wave_inclusive_scan(t), i1 = wave_inclusive_scan(np), i2 = wave_inclusive_scan(sp);
+		if (lane == 63) { sh.wsum[0][wave] = i0; sh.wsum[1][wave] = i1; sh.wsum[2][wave] = i2; }
+		__syncthreads();
+		uint32_t p0 = c0, p1 = c1, p2 = c2;
+		for (uint32_t w = 0; w < nw; ++w) {
+			if (w < wave) { p0 += sh.wsum[0][w]; p1 += sh.wsum[1][w]; p2 += sh.wsum[2][w]; }
+			c0 += sh.wsum[0][w]; c1 += sh.wsum[1][w]; c2 += sh.wsum[2][w];
+		}
+		__syncthreads();
+		if (vb < n_vb) visit(vb, t, p0 + i0 - t, p1 + i1 - np, p2 + i2 - sp, np);
+	}
+}
+// the start of bucket vb of level l (its first bucket vb0): the level's static item offset plus the totals of the
+// level's buckets before vb (one load per thread, one barrier)
+__device__ __forceinline__ uint32_t plan_bucket_lo(const uint32_t* __restrict__ tot, uint32_t level_items, uint32_t vb0, uint32_t vb,
+                                                   PlanShared& sh) {
+	uint32_t sum = 0;
+	for (uint32_t j = vb0 + threadIdx.x; j < vb; j += blockDim.x) sum += tot[j];
+	sum = wave_inclusive_scan(sum);
+	if ((threadIdx.x & 63) == 63) sh.wsum[0][threadIdx.x >> 6] = sum;
+	__syncthreads();
+	uint32_t lo = level_items;
+	for (uint32_t w = 0; w < (blockDim.x >> 6); ++w) lo += sh.wsum[0][w];
+	return __builtin_amdgcn_readfirstlane(lo);  // block-uniform: a scalar register, like the plan's load
+}
+
 // The brick slot of a chunk: one item per sample (its index) in its brick's bucket, ranked, staged and
 // written out like the level items.
 template <uint32_t F, uint32_t SC_CHUNK, uint32_t SC_ST>
@@ -451,11 +511,13 @@ __device__ void scatter_bricks(const GridConst& c, const BrickConst& bk, const G
 	}
 }
 
-template <uint32_t D, uint32_t F, uint32_t SC_CHUNK, uint32_t SC_ST>
+// INL (here and in k_sc_accumulate / k_sc_split_reduce): the inline plan's instantiation. A template flag: with the
+// inline plan's code as a runtime branch of the one kernel the k_sc_plan path measured 1 % slower at C2.
+template <uint32_t D, uint32_t F, uint32_t SC_CHUNK, uint32_t SC_ST, bool INL = false>
 __global__ void __launch_bounds__(SC_ST) k_sc_scatter(const GridConst c, const Levels lv, const BrickConst bk, const GridBwdArgs a, uint32_t B,
                                                       uint32_t n_vb, uint32_t n_chunks, uint32_t xcd_map, const uint32_t* __restrict__ cur_t,
                                                       const uint32_t* __restrict__ lo_vb, uint16_t* __restrict__ item_idx,
-                                                      f16* __restrict__ item_val, uint32_t debug) {
+                                                      f16* __restrict__ item_val, uint32_t debug, const uint32_t* __restrict__ tot) {
 	typedef typename ValVec<F>::T V;
 	constexpr uint32_t NC = 1u << D;
 	constexpr uint32_t NIT = SC_CHUNK * NC;  // items per block
@@ -463,7 +525,8 @@ __global__ void __launch_bounds__(SC_ST) k_sc_scatter(const GridConst c, const L
 	extern __shared__ uint32_t lds[];
 	__shared__ uint32_t wsum[SC_ST / 64];
 	// slots per chunk: one per item level, the brick slot in place of the brick levels (slot LB)
-	const uint32_t n_slots = c.n_levels - (bk.LD - bk.LB) + (bk.LD ? 1u : 0u);
+	// (direct levels, without bricks only, have no slot)
+	const uint32_t n_slots = c.n_levels - (bk.LD - bk.LB) + (bk.LD ? 1u : 0u) - lv.nd;
 	// XCD-aware order: blocks b and b + 8 share an XCD (round-robin dispatch), so the L level blocks of a
 	// chunk run back to back on one XCD and its positions and dL/dy rows leave HBM once, not L times
 	uint32_t chunk, l;
@@ -491,6 +554,7 @@ __global__ void __launch_bounds__(SC_ST) k_sc_scatter(const GridConst c, const L
 		}
 		l = l - bk.LB - 1 + bk.LD;
 	}
+	l += lv.nd;
 	const uint32_t nvb = lv.vb_base[l + 1] - lv.vb_base[l];
 	uint32_t* cur = lds;                                   // [nvb] this block's global cursor per bucket
 	uint32_t* lh = cur + nvb;                              // [nvb] counts
@@ -499,10 +563,21 @@ __global__ void __launch_bounds__(SC_ST) k_sc_scatter(const GridConst c, const L
 	uint16_t* st_idx = st_b + NIT;                         // [NIT]
 	V* st_val = (V*)(((uintptr_t)(st_idx + NIT) + 15) & ~(uintptr_t)15);  // [NIT]
 	// global start of (bucket, this chunk): bucket start (k_sc_plan) + the chunk's cursor (k_sc_scan)
-	for (uint32_t j = threadIdx.x; j < nvb; j += blockDim.x) {
-		const uint32_t vb = lv.vb_base[l] + j;
-		cur[j] = lo_vb[vb] + cur_t[(size_t)chunk * n_vb + vb];
-		lh[j] = 0;
+	if constexpr (INL) {
+		// inline plan: the bucket starts from the totals. Item level q (levels after the direct ones) starts at item
+		// n 2^D q; within the level an exclusive scan of its buckets' totals
+		block_exclusive_scan<SC_ST>(tot + lv.vb_base[l], loff, nvb, wsum);
+		const uint32_t level_items = a.n * NC * (l - lv.nd);
+		for (uint32_t j = threadIdx.x; j < nvb; j += blockDim.x) {  // thread j wrote loff[j] itself
+			cur[j] = level_items + loff[j] + cur_t[(size_t)chunk * n_vb + lv.vb_base[l] + j];
+			lh[j] = 0;
+		}
+	} else {
+		for (uint32_t j = threadIdx.x; j < nvb; j += blockDim.x) {
+			const uint32_t vb = lv.vb_base[l] + j;
+			cur[j] = lo_vb[vb] + cur_t[(size_t)chunk * n_vb + vb];
+			lh[j] = 0;
+		}
 	}
 	__syncthreads();
 	const uint32_t off_l = c.offsets[l];
@@ -849,6 +924,112 @@ __device__ __forceinline__ void store_pair(f16* grad, float* g32, size_t k, floa
 	}
 }
 
+// One direct part: the contributions of samples [i0, i1) to features [f0, f0 + FT) of entries [t0, t0 + TE) of
+// direct level l, formed as k_sc_scatter forms its items (to_f16(w * dL/dy), nothing for a masked level) and
+// added as accumulate_items adds them (fixed point, zero skipped, lane-rotated feature order), into
+// acc[(f - f0) * (TE + 1) + entry - t0]. Corners outside the tile belong to the level's other bucket's block.
+template <uint32_t D, uint32_t F, uint32_t FT>
+__device__ __forceinline__ void direct_samples(const GridConst& c, const GridBwdArgs& a, uint32_t l, uint32_t i0, uint32_t i1, uint32_t f0,
+                                               uint32_t t0, uint32_t TE, unsigned long long* acc) {
+	typedef typename ValVec<F>::T V;
+	constexpr uint32_t NC = 1u << D, U = 2;  // samples per thread in flight
+	const uint32_t TEP = TE + 1, off_l = c.offsets[l] + t0, rot = threadIdx.x % FT;
+	for (uint32_t ib = i0 + threadIdx.x; ib < i1; ib += blockDim.x * U) {
+		float x[U][D], g[U][FT];
+		bool active[U];
+#pragma unroll
+		for (uint32_t u = 0; u < U; ++u) {
+			const uint32_t i = min(ib + u * blockDim.x, i1 - 1);  // clamped loads, issued together
+			load_pos<D>(a, i, x[u]);
+			const float ml = (a.max_level_per_sample ? a.max_level_per_sample[i] : a.max_level) * (float)c.n_levels;
+			active[u] = !((float)l > ml + 1e-3f) && ib + u * blockDim.x < i1;
+			if (a.dy_layout == AoS) {
+				const V gv = *(const V*)(a.dL_dy + (size_t)i * a.dy_stride + l * F);
+#pragma unroll
+				for (uint32_t f = 0; f < FT; ++f) {
+					if constexpr (F == 1) g[u][f] = (float)gv;
+					else {
+						float t = (float)gv[f];
+#pragma unroll
+						for (uint32_t q = 1; q < F / FT; ++q) t = f0 == q * FT ? (float)gv[q * FT + f] : t;
+						g[u][f] = t;
+					}
+				}
+			} else {
+#pragma unroll
+				for (uint32_t f = 0; f < FT; ++f) g[u][f] = (float)a.dL_dy[(size_t)(l * F + f0 + f) * a.dy_stride + i];
+			}
+		}
+#pragma unroll
+		for (uint32_t u = 0; u < U; ++u) {
+			if (!active[u]) continue;
+			float frac[D]; uint32_t base[D];
+			level_setup<D>(c, l, x[u], frac, base);
+			uint32_t cidx[NC];
+			corner_indices<D>(c, l, base, cidx);
+#pragma unroll
+			for (uint32_t k = 0; k < NC; ++k) {
+				const uint32_t e = cidx[k] - off_l;
+				if (e >= TE) continue;
+				const float w = corner_weight<D>(frac, k);
+#pragma unroll
+				for (uint32_t q = 0; q < FT; ++q) {
+					const uint32_t f = (q + rot) & (FT - 1);
+					float gf = g[u][0];
+#pragma unroll
+					for (uint32_t r = 1; r < FT; ++r) gf = f == r ? g[u][r] : gf;
+					const float v = (float)to_f16(w * gf);
+#if NGP_ACC_SKIP0
+					if (v != 0.f) atomicAdd(&acc[f * TEP + e], (unsigned long long)(long long)(v * FIX_SCALE));
+#else
+					atomicAdd(&acc[f * TEP + e], (unsigned long long)(long long)(v * FIX_SCALE));
+#endif
+				}
+			}
+		}
+	}
+}
+
+// Direct part block x = (direct bucket v, sample range r): level l = v's level sums samples [r dS, (r + 1) dS)
+// without items. A one-bucket level: the whole level, every feature, stored as slab (v, r). A two-bucket level with
+// F >= 2: block v - vb_base[l] = h takes feature half h over the whole level (the same 64-KB tile; every corner of every
+// sample lands in it, so both blocks do equal work whatever the cloud) and stores its planes of both buckets' slabs.
+// F = 1: the block takes its own bucket's entries and drops the other corners. Slabs have the split parts' layout
+// [f * NE + entry], so k_sc_split_reduce sums them like a split bucket's.
+template <uint32_t D, uint32_t F>
+__device__ __forceinline__ void accumulate_direct(const GridConst& c, const Levels& lv, const GridBwdArgs& a, uint32_t B, uint32_t x,
+                                                  unsigned long long* acc, unsigned long long* __restrict__ scratch) {
+	const uint32_t nd_b = lv.vb_base[lv.nd], v = x % nd_b, r = x / nd_b, NE = 1u << B;
+	uint32_t l = 0;
+	while (lv.vb_base[l + 1] <= v) ++l;
+	const uint32_t nb = lv.vb_base[l + 1] - lv.vb_base[l], sub = v - lv.vb_base[l], n_l = c.offsets[l + 1] - c.offsets[l];
+	const uint32_t i0 = min(r * lv.dS, a.n), i1 = min(i0 + lv.dS, a.n);
+	if (i0 >= i1) return;
+	const size_t pstride = (size_t)NE * F;
+	if constexpr (F >= 2) {
+		if (nb == 2) {
+			constexpr uint32_t FH = F / 2;
+			const uint32_t TEP = n_l + 1, f0 = sub * FH;
+			for (uint32_t k = threadIdx.x; k < TEP * FH; k += blockDim.x) acc[k] = 0ull;
+			__syncthreads();
+			direct_samples<D, F, FH>(c, a, l, i0, i1, f0, 0u, n_l, acc);
+			__syncthreads();
+			for (uint32_t k = threadIdx.x; k < n_l * FH; k += blockDim.x) {
+				const uint32_t f = k / n_l, e = k % n_l, b = e >> B;
+				scratch[((size_t)(lv.vb_base[l] + b) * lv.dP + r) * pstride + (size_t)(f0 + f) * NE + (e & (NE - 1))] = acc[f * TEP + e];
+			}
+			return;
+		}
+	}
+	const uint32_t t0 = sub << B, TE = min(NE, n_l - t0), TEP = TE + 1;
+	for (uint32_t k = threadIdx.x; k < TEP * F; k += blockDim.x) acc[k] = 0ull;
+	__syncthreads();
+	direct_samples<D, F, F>(c, a, l, i0, i1, 0u, t0, TE, acc);
+	__syncthreads();
+	unsigned long long* dst = scratch + ((size_t)v * lv.dP + r) * pstride;
+	for (uint32_t k = threadIdx.x; k < TE * F; k += blockDim.x) dst[(size_t)(k / TE) * NE + k % TE] = acc[(k / TE) * TEP + k % TE];
+}
+
 // One workgroup per work unit, heaviest first: blocks [0, max_parts) are the parts of oversized
 // buckets (coarse levels, where thousands of samples share a handful of entries; exact int64 partial
 // sums to their scratch slot, added by k_sc_split_reduce), blocks max_parts + vb the other buckets:
@@ -858,7 +1039,10 @@ __device__ __forceinline__ void store_pair(f16* grad, float* g32, size_t k, floa
 // branch for the fused update cost C2' 25 %): SC_STORE_F16 the fp16 gradient store; SC_FUSED_ADAM the grid's
 // optimizer update (FusedAdam) instead of the store; SC_STORE_F32 the fp16-rounded gradient widened to fp32
 // into fa.g32 (the sharded optimizer's reduce-scatter input: no separate widening pass).
-template <uint32_t F, uint32_t MODE>
+// DD (0, or the grid's dimensions 2 / 3): the instantiation that also holds the direct parts, blocks [0, n_direct) in
+// front of the split parts (accumulate_direct; launched only for plans with direct levels, so that plans without
+// them keep the item-only kernel and its register allocation).
+template <uint32_t F, uint32_t MODE, uint32_t DD = 0, bool INL = false>
 __global__ void __launch_bounds__(SC_BT) k_sc_accumulate(const GridConst c, const Levels lv, const BrickConst bk, const GridBwdArgs a,
                                                          const uint32_t* __restrict__ tot,
                                                          const uint32_t* __restrict__ lo_arr, uint32_t B, uint32_t split_limit,
@@ -866,17 +1050,47 @@ __global__ void __launch_bounds__(SC_BT) k_sc_accumulate(const GridConst c, cons
                                                          const f16* __restrict__ item_val, f16* __restrict__ grad, bool overwrite,
                                                          const uint32_t* __restrict__ split, unsigned long long* __restrict__ scratch,
                                                          uint32_t debug, const FusedAdam fa, const BrickFallback fb, uint32_t vb_off,
-                                                         uint32_t part_lo, uint32_t part_hi) {
+                                                         uint32_t part_lo, uint32_t part_hi, uint32_t n_direct, uint32_t inline_part) {
+	// inline_part != 0: the inline plan with parts of that many items; lo_arr and split are not read
+	if constexpr (!INL) inline_part = 0u;
 	constexpr bool FUSED = MODE == SC_FUSED_ADAM, G32 = MODE == SC_STORE_F32;
 	extern __shared__ unsigned long long acc[];
+	__shared__ PlanShared psh;
 	const uint32_t NE = 1u << B, NEP = NE + 1;  // feature planes padded by one entry (accumulate_items)
-	if (blockIdx.x < max_parts) {
-		if (blockIdx.x >= split[0]) return;
-		const uint32_t* d = split + 2 + 3 * (size_t)blockIdx.x;
-		if (d[0] < part_lo || d[0] >= part_hi) return;  // BwdParts: a split part of a bucket of another range
-		const uint32_t lo = d[1], hi = d[2];
-		if (d[0] - bk.vb0 < bk.NBK) {
-			accumulate_brick<F>(c, bk, a, d[0] - bk.vb0, lo, hi, item_idx, item_val, acc, scratch + (size_t)blockIdx.x * NE * F, NE, fb);
+	uint32_t bx = blockIdx.x;
+	if constexpr (DD != 0) {
+		if (bx < n_direct) {
+			accumulate_direct<DD, F>(c, lv, a, B, bx, acc, scratch);
+			return;
+		}
+		bx -= n_direct;
+	}
+	if (bx < max_parts) {
+		// the split list and the scratch slots start with the direct buckets' static parts (k_sc_plan)
+		const uint32_t slot = bx + lv.vb_base[lv.nd] * lv.dP;
+		uint32_t pvb, lo, hi;
+		if (inline_part) {
+			if (threadIdx.x == 0) psh.res[0] = ~0u;  // ordered before the visits by plan_scan's barriers
+			plan_scan(tot, lv.vb_base[c.n_levels], split_limit, inline_part, lv.vb_base[lv.nd] * lv.dP, 0u, psh,
+			          [&](uint32_t vb, uint32_t t, uint32_t lo_b, uint32_t first, uint32_t, uint32_t np) {
+				          if (slot - first < np) {  // this block's part (first <= slot < first + np: one bucket at most)
+					          const uint32_t q = slot - first;
+					          psh.res[0] = vb; psh.res[1] = lo_b + q * inline_part; psh.res[2] = min(lo_b + (q + 1) * inline_part, lo_b + t);
+				          }
+			          });
+			__syncthreads();
+			// block-uniform: kept in scalar registers like the list's loads
+			pvb = __builtin_amdgcn_readfirstlane(psh.res[0]); lo = __builtin_amdgcn_readfirstlane(psh.res[1]);
+			hi = __builtin_amdgcn_readfirstlane(psh.res[2]);
+			if (pvb == ~0u) return;  // past the last part
+		} else {
+			if (slot >= split[0]) return;
+			const uint32_t* d = split + 2 + 3 * (size_t)slot;
+			pvb = d[0]; lo = d[1]; hi = d[2];
+		}
+		if (pvb < part_lo || pvb >= part_hi) return;  // BwdParts: a split part of a bucket of another range
+		if (pvb - bk.vb0 < bk.NBK) {
+			accumulate_brick<F>(c, bk, a, pvb - bk.vb0, lo, hi, item_idx, item_val, acc, scratch + (size_t)slot * NE * F, NE, fb);
 			return;
 		}
 		for (uint32_t k = threadIdx.x; k < NEP * F; k += blockDim.x) acc[k] = 0ull;
@@ -884,11 +1098,12 @@ __global__ void __launch_bounds__(SC_BT) k_sc_accumulate(const GridConst c, cons
 		if (!(debug & 1)) accumulate_items<F>(acc, NE, lo, hi, item_idx, item_val, debug);
 		__syncthreads();
 		// scratch keeps the unpadded layout [f * NE + entry] (k_sc_split_reduce)
-		unsigned long long* dst = scratch + (size_t)blockIdx.x * NE * F;
+		unsigned long long* dst = scratch + (size_t)slot * NE * F;
 		for (uint32_t k = threadIdx.x; k < NE * F; k += blockDim.x) dst[k] = acc[(k / NE) * NEP + k % NE];
 		return;
 	}
-	const uint32_t vb = blockIdx.x - max_parts + vb_off;  // vb_off: a launch over buckets [vb_off, ..) (BwdParts)
+	const uint32_t vb = bx - max_parts + vb_off;  // vb_off: a launch over buckets [vb_off, ..) (BwdParts)
+	if (vb < lv.vb_base[lv.nd]) return;  // direct buckets: summed by k_sc_split_reduce from the direct parts' slabs
 	if (vb - bk.vb0 < bk.NBK) return;  // bricks: parts only
 	const uint32_t t = tot[vb];
 	if (t > split_limit) return;
@@ -900,7 +1115,12 @@ __global__ void __launch_bounds__(SC_BT) k_sc_accumulate(const GridConst c, cons
 			for (uint32_t k = threadIdx.x; k < n_e * F / 2; k += blockDim.x) store_pair<G32>(grad, fa.g32, (size_t)e0 * F / 2 + k, 0.f, 0.f);
 		return;
 	}
-	const uint32_t lo = lo_arr[vb];
+	uint32_t lo;
+	if (inline_part) {
+		uint32_t l = 0;
+		while (lv.vb_base[l + 1] <= vb) ++l;
+		lo = plan_bucket_lo(tot, lv.level_items * (l - lv.nd), lv.vb_base[l], vb, psh);
+	} else lo = lo_arr[vb];
 	for (uint32_t k = threadIdx.x; k < NEP * F; k += blockDim.x) acc[k] = 0ull;
 	__syncthreads();
 	if (!(debug & 1)) accumulate_items<F>(acc, NE, lo, lo + t, item_idx, item_val, debug);
@@ -970,14 +1190,16 @@ __global__ void __launch_bounds__(SC_BT) k_sc_accumulate(const GridConst c, cons
 // Columns [fin_x0, gridDim.x) finalize the brick levels: one entry per thread (two for F = 1), every feature
 // summed over the bricks' slabs in one pass over the geometry (brick_entry_sums), written as parameter pairs
 // (pair k = features 2k, 2k + 1 of the grid's leading entries).
-template <uint32_t F, uint32_t MODE>
+template <uint32_t F, uint32_t MODE, bool INL = false>
 __global__ void __launch_bounds__(SC_THREADS) k_sc_split_reduce(const GridConst c, const Levels lv, uint32_t B,
                                                                 const uint32_t* __restrict__ split, const uint32_t* __restrict__ splitb,
                                                                 const unsigned long long* __restrict__ scratch, f16* __restrict__ grad,
                                                                 bool overwrite, const SlabJob sj, uint32_t slab_x0, const FusedAdam fa,
                                                                 const BrickConst bk, const uint32_t* __restrict__ bp, const BrickFallback fb,
-                                                                uint32_t fin_x0, uint32_t part_lo, uint32_t part_hi) {
+                                                                uint32_t fin_x0, uint32_t part_lo, uint32_t part_hi,
+                                                                const uint32_t* __restrict__ tot, uint32_t split_limit, uint32_t inline_part) {
 	static_assert(SC_THREADS == SLAB_THREADS, "slab blocks share the split-reduce block shape");
+	if constexpr (!INL) inline_part = 0u;
 	constexpr bool FUSED = MODE == SC_FUSED_ADAM, G32 = MODE == SC_STORE_F32;
 	if (blockIdx.x >= fin_x0) {
 		constexpr uint32_t EPT = F == 1 ? 2 : 1;  // entries per thread: whole parameter pairs
@@ -1047,8 +1269,28 @@ __global__ void __launch_bounds__(SC_THREADS) k_sc_split_reduce(const GridConst 
 		return;
 	}
 	// grid (split bucket, 256-pair chunk): one pair per thread, the parts' loads 8 at a time
-	if (blockIdx.x >= split[1]) return;
-	const uint32_t vb = splitb[3 * blockIdx.x], first = splitb[3 * blockIdx.x + 1], parts = splitb[3 * blockIdx.x + 2];
+	uint32_t vb, first, parts;
+	if (inline_part) {
+		// inline plan: the direct buckets are split buckets 0..nd_b-1 with static slabs; the others from the totals
+		const uint32_t nd_b = lv.vb_base[lv.nd];
+		if (blockIdx.x < nd_b) { vb = blockIdx.x; first = vb * lv.dP; parts = lv.dP; }
+		else {
+			__shared__ PlanShared psh;
+			if (threadIdx.x == 0) psh.res[0] = ~0u;  // ordered before the visits by plan_scan's barriers
+			const uint32_t want = blockIdx.x;
+			plan_scan(tot, lv.vb_base[c.n_levels], split_limit, inline_part, nd_b * lv.dP, nd_b, psh,
+			          [&](uint32_t b, uint32_t, uint32_t, uint32_t first_b, uint32_t sb, uint32_t np) {
+				          if (np && sb == want) { psh.res[0] = b; psh.res[1] = first_b; psh.res[2] = np; }
+			          });
+			__syncthreads();
+			vb = __builtin_amdgcn_readfirstlane(psh.res[0]); first = __builtin_amdgcn_readfirstlane(psh.res[1]);
+			parts = __builtin_amdgcn_readfirstlane(psh.res[2]);
+			if (vb == ~0u) return;  // past the last split bucket
+		}
+	} else {
+		if (blockIdx.x >= split[1]) return;
+		vb = splitb[3 * blockIdx.x]; first = splitb[3 * blockIdx.x + 1]; parts = splitb[3 * blockIdx.x + 2];
+	}
 	if (vb < part_lo || vb >= part_hi) return;  // BwdParts: a split bucket of another range
 	const uint32_t NE = 1u << B;
 	uint32_t e0, n_e;
@@ -1091,8 +1333,9 @@ size_t scatter_lds_bytes(uint32_t max_lb, uint32_t chunk, uint32_t D, uint32_t F
 	return (size_t)(3 * max_lb + 1) * 4 + nit * 4 + 16 + nit * F * 2;
 }
 
-Levels make_levels(const GridDesc& g, uint32_t B, const BrickConst& bk) {
+Levels make_levels(const GridDesc& g, uint32_t B, const BrickConst& bk, uint32_t nd = 0, uint32_t dS = 0, uint32_t dP = 0) {
 	Levels lv{};
+	lv.nd = nd; lv.dS = dS; lv.dP = dP;
 	uint32_t vb = 0;  // level LB's range holds the bricks [bk.vb0, + NBK); levels LB+1..LD-1 own no buckets
 	for (uint32_t l = 0; l < g.n_levels; ++l) {
 		lv.vb_base[l] = vb;
@@ -1100,6 +1343,11 @@ Levels make_levels(const GridDesc& g, uint32_t B, const BrickConst& bk) {
 		else if (!(l >= bk.LB && l < bk.LD)) vb += (g.offsets[l + 1] - g.offsets[l] + (1u << B) - 1) >> B;
 	}
 	for (uint32_t l = g.n_levels; l <= 32; ++l) lv.vb_base[l] = vb;
+	return lv;
+}
+Levels make_levels(const GridDesc& g, const ScatterPlan& p) {
+	Levels lv = make_levels(g, p.B, p.bk, p.direct_levels, p.direct_part, p.direct_parts);
+	lv.level_items = g.n_levels > p.direct_levels ? (uint32_t)(p.n_items / (g.n_levels - p.direct_levels)) : 0u;
 	return lv;
 }
 
@@ -1118,13 +1366,15 @@ void launch_backward(uint32_t F, const GridConst& c, const Levels& lv, const Gri
 	const BrickFallback fb{(unsigned long long*)(ws + p.off_fb), (uint32_t*)(ws + p.off_fb + (size_t)c.offsets[p.bk.LD] * c.n_features * 8)};
 	const size_t lds_s = scatter_lds_bytes(p.max_lb, p.spb, D, F);
 	const uint32_t xcd_map = p.xcd_map;
-	const uint32_t n_slots = c.n_levels - (p.bk.LD - p.bk.LB) + (p.bk.LD ? 1u : 0u);
+	const uint32_t n_slots = c.n_levels - (p.bk.LD - p.bk.LB) + (p.bk.LD ? 1u : 0u) - p.direct_levels;
+	const uint32_t n_direct = p.direct_buckets * p.direct_parts;  // direct part blocks, in front of the accumulate's
+	const uint32_t inline_part = p.plan_inline ? p.part : 0u;
 	const dim3 grid_s(xcd_map ? (uint32_t)div_round_up(p.n_chunks, 8) * 8 * n_slots : p.n_chunks * n_slots);
 	auto go = [&](auto scatter, auto accum, auto splitr) {
 		ensure_dynamic_lds((const void*)scatter, lds_s);
-		if (!(debug & 4))
+		if (!(debug & 4) && n_slots)  // every level direct: no items
 			scatter<<<grid_s, p.spb == 512 ? 512 : 1024, lds_s, s>>>(c, lv, p.bk, a, p.B, p.n_buckets, p.n_chunks, xcd_map, cur_t, lo, idx, val,
-			                                                          debug);
+			                                                          debug, p.plan_inline ? tot : nullptr);
 		NGP_HIP(hipGetLastError());
 		const size_t lds_a = ((size_t)8 << p.B) * c.n_features + SC_LDS_PAD_BYTES + (fa.rec ? SC_LIST_BYTES : 0);
 		ensure_dynamic_lds((const void*)accum, lds_a);
@@ -1136,19 +1386,20 @@ void launch_backward(uint32_t F, const GridConst& c, const Levels& lv, const Gri
 		const size_t fin_threads = c.n_features == 1 ? div_round_up(fin_entries, 2) : fin_entries;
 		const uint32_t fin_x = (uint32_t)div_round_up(div_round_up(fin_threads, SC_THREADS), gy);
 		if (!parted) {
-			accum<<<p.max_split_blocks + p.n_buckets, p.bt, lds_a, s>>>(c, lv, p.bk, a, tot, lo, p.B, p.split_limit, p.max_split_blocks,
-			                                                             idx, val, a.grad, overwrite, split, scratch, debug, fa, fb, 0u,
-			                                                             0u, ~0u);
+			accum<<<n_direct + p.max_split_blocks + p.n_buckets, p.bt, lds_a, s>>>(c, lv, p.bk, a, tot, lo, p.B, p.split_limit,
+			                                                                        p.max_split_blocks, idx, val, a.grad, overwrite, split, scratch,
+			                                                                        debug, fa, fb, 0u, 0u, ~0u, n_direct, inline_part);
 			NGP_HIP(hipGetLastError());
 			const dim3 grid_r(p.max_split_buckets + slab_x + fin_x, gy);
 			splitr<<<grid_r, SC_THREADS, 0, s>>>(c, lv, p.B, split, splitb, scratch, a.grad, overwrite, sj, p.max_split_buckets, fa, p.bk, bp,
-			                                     fb, p.max_split_buckets + slab_x, 0u, ~0u);
+			                                     fb, p.max_split_buckets + slab_x, 0u, ~0u, tot, p.split_limit, inline_part);
 			NGP_HIP(hipGetLastError());
 			return;
 		}
 		// parted (no bricks): the bucket ranges from the last to the first, each with its own split parts and split
 		// buckets, so a range's gradient is final when its two launches are; the MLP's slabs with range 0, which
-		// holds the MLP's parameters. The highest ranges (the hashed levels) rarely hold a split bucket: their
+		// holds the MLP's parameters. The direct parts all run in the first launch: their slabs stay in their own
+		// scratch slots until the launch of their bucket's range sums them. The highest ranges (the hashed levels) rarely hold a split bucket: their
 		// exchange starts while the heavy coarse levels are still summed.
 		NGP_CHECK(!p.bk.LD, "grid backward parts: not with bricks");
 		for (uint32_t jj = 0; jj < parts->k; ++jj) {
@@ -1156,14 +1407,15 @@ void launch_backward(uint32_t F, const GridConst& c, const Levels& lv, const Gri
 			const uint32_t v0 = j ? std::min(parts->vb_end[j - 1], p.n_buckets) : 0u;
 			const uint32_t v1 = j + 1 == parts->k ? p.n_buckets : std::min(parts->vb_end[j], p.n_buckets);
 			NGP_CHECK(v0 <= v1, "grid backward parts: bucket ranges out of order");
-			accum<<<p.max_split_blocks + (v1 - v0), p.bt, lds_a, s>>>(c, lv, p.bk, a, tot, lo, p.B, p.split_limit, p.max_split_blocks,
-			                                                           idx, val, a.grad, overwrite, split, scratch, debug, fa, fb, v0,
-			                                                           v0, v1);
+			const uint32_t nd_j = jj == 0 ? n_direct : 0u;
+			accum<<<nd_j + p.max_split_blocks + (v1 - v0), p.bt, lds_a, s>>>(c, lv, p.bk, a, tot, lo, p.B, p.split_limit, p.max_split_blocks,
+			                                                                  idx, val, a.grad, overwrite, split, scratch, debug, fa, fb, v0,
+			                                                                  v0, v1, nd_j, inline_part);
 			NGP_HIP(hipGetLastError());
 			const uint32_t sx = j == 0 ? slab_x : 0u;
 			const dim3 grid_r(p.max_split_buckets + sx, gy);
 			splitr<<<grid_r, SC_THREADS, 0, s>>>(c, lv, p.B, split, splitb, scratch, a.grad, overwrite, sj, p.max_split_buckets, fa, p.bk, bp,
-			                                     fb, p.max_split_buckets + sx, v0, v1);
+			                                     fb, p.max_split_buckets + sx, v0, v1, tot, p.split_limit, inline_part);
 			NGP_HIP(hipGetLastError());
 			if (parts->after) parts->after(parts->user, j, s);
 		}
@@ -1172,21 +1424,36 @@ void launch_backward(uint32_t F, const GridConst& c, const Levels& lv, const Gri
 		if (p.spb == 512) go(sc512, accum, splitr);
 		else go(sc1024, accum, splitr);
 	};
-#define NGP_SC_F(FF)                                                                                                 \
-	if (fa.rec) by_chunk(k_sc_scatter<D, FF, 512, 512>, k_sc_scatter<D, FF, 1024, 1024>, k_sc_accumulate<FF, SC_FUSED_ADAM>, \
-	                     k_sc_split_reduce<FF, SC_FUSED_ADAM>);                                                      \
-	else if (fa.g32) by_chunk(k_sc_scatter<D, FF, 512, 512>, k_sc_scatter<D, FF, 1024, 1024>,                       \
-	                          k_sc_accumulate<FF, SC_STORE_F32>, k_sc_split_reduce<FF, SC_STORE_F32>);              \
-	else by_chunk(k_sc_scatter<D, FF, 512, 512>, k_sc_scatter<D, FF, 1024, 1024>, k_sc_accumulate<FF, SC_STORE_F16>,  \
-	              k_sc_split_reduce<FF, SC_STORE_F16>)
+	// plans with direct levels take the accumulate instantiation that holds the direct parts (DD = D)
+	// and plans with the inline plan the three kernels' INL instantiations
+#define NGP_SC_K(FF, MM, DDD, II)                                                                                                 \
+	by_chunk(k_sc_scatter<D, FF, 512, 512, II>, k_sc_scatter<D, FF, 1024, 1024, II>, k_sc_accumulate<FF, MM, DDD, II>,            \
+	         k_sc_split_reduce<FF, MM, II>)
+#define NGP_SC_M(FF, MM)                                     \
+	if (n_direct && p.plan_inline) NGP_SC_K(FF, MM, D, true); \
+	else if (n_direct) NGP_SC_K(FF, MM, D, false);            \
+	else if (p.plan_inline) NGP_SC_K(FF, MM, 0, true);        \
+	else NGP_SC_K(FF, MM, 0, false)
+#define NGP_SC_F(FF)                                   \
+	if (fa.rec) { NGP_SC_M(FF, SC_FUSED_ADAM); }       \
+	else if (fa.g32) { NGP_SC_M(FF, SC_STORE_F32); }   \
+	else { NGP_SC_M(FF, SC_STORE_F16); }
 	switch (F) {
 		case 1: NGP_SC_F(1); break;
 		case 2: NGP_SC_F(2); break;
 		case 4: NGP_SC_F(4); break;
-		case 8: NGP_SC_F(8); break;
-		default: throw Error("grid backward: unsupported F");
+		default: break;
 	}
+#undef NGP_SC_M
+	// F = 8 has no direct levels (make_scatter_plan): the item-only instantiation
+#define NGP_SC_M(FF, MM)                                \
+	if (p.plan_inline) NGP_SC_K(FF, MM, 0, true);       \
+	else NGP_SC_K(FF, MM, 0, false)
+	if (F == 8) { NGP_SC_F(8); }
+	else if (F != 1 && F != 2 && F != 4) throw Error("grid backward: unsupported F");
 #undef NGP_SC_F
+#undef NGP_SC_M
+#undef NGP_SC_K
 }
 
 // Brick geometry for dense levels LB..LD-1 (3D). Finest level f = LD - 1: brick b covers cells
@@ -1262,7 +1529,7 @@ static BrickConst make_bricks(const GridDesc& g, uint32_t n, uint32_t B, uint32_
 
 }  // namespace
 
-ScatterPlan make_scatter_plan(const GridDesc& g, uint32_t n, bool bricks) {
+ScatterPlan make_scatter_plan(const GridDesc& g, uint32_t n, bool bricks, bool direct, bool plan_inline) {
 	ScatterPlan p;
 	const uint32_t F = g.n_features;
 	// bucket = 2^B entries of one level whose F int64 accumulators fill SC_LDS_BYTES
@@ -1272,14 +1539,30 @@ ScatterPlan make_scatter_plan(const GridDesc& g, uint32_t n, bool bricks) {
 	while (((size_t)2 << p.B) * F * 8 <= lds_budget && p.B < 16) ++p.B;
 	if (const char* e = getenv("NGP_SC_BRICK_PART")) p.brick_part = std::max(1, atoi(e));
 	if (bricks) p.bk = make_bricks(g, n, p.B, p.brick_part);
-	const Levels lv = make_levels(g, p.B, p.bk);
+	// direct levels: the leading levels of at most two buckets (level sizes never shrink, so they are a prefix and
+	// their buckets are [0, direct_buckets)); not with bricks
+	p.direct_part = 16384;  // C2: 8192 +1.9 %, 4096 slower still, 32768 +23 % (two long blocks per level half)
+	if (const char* e = getenv("NGP_SC_DIRECT")) direct = atoi(e) != 0;
+	// (F = 8 stays on items: with the direct part the F = 8 accumulate keeps arrays in scratch memory, 808 B per lane)
+	if (direct && !p.bk.LD && n > 0 && F <= 4) {
+		if (const char* e = getenv("NGP_SC_DIRECT_PART")) p.direct_part = (uint32_t)std::max(1, atoi(e));
+		while (p.direct_levels < g.n_levels && g.offsets[p.direct_levels + 1] - g.offsets[p.direct_levels] <= (2u << p.B)) {
+			p.direct_mask |= 1u << p.direct_levels;
+			++p.direct_levels;
+		}
+		p.direct_parts = p.direct_levels ? (uint32_t)div_round_up(n, p.direct_part) : 0u;
+	}
+	const Levels lv = make_levels(g, p.B, p.bk, p.direct_levels, p.direct_part, p.direct_parts);
+	p.direct_buckets = lv.vb_base[p.direct_levels];
 	p.n_buckets = lv.vb_base[g.n_levels];
+	if (const char* e = getenv("NGP_SC_PLAN_INLINE")) plan_inline = atoi(e) != 0;
+	p.plan_inline = plan_inline && !p.bk.LD && p.n_buckets <= SC_PLAN_THREADS;
 	p.max_lb = p.bk.NBK;
 	for (uint32_t l = 0; l < g.n_levels; ++l) p.max_lb = std::max(p.max_lb, lv.vb_base[l + 1] - lv.vb_base[l]);
 	NGP_CHECK((size_t)p.max_lb * 4 <= 32 * 1024, "grid backward: level too large for the bucket histogram");
 	// samples per chunk: 1024 when 512-sample chunks would average fewer than 16 items per (chunk,
 	// bucket) and the scatter block's LDS allows it
-	const uint64_t items_per_sample = ((uint64_t)(g.n_levels - (p.bk.LD - p.bk.LB)) << g.n_dims) + (p.bk.LD ? 1u : 0u);
+	const uint64_t items_per_sample = ((uint64_t)(g.n_levels - (p.bk.LD - p.bk.LB) - p.direct_levels) << g.n_dims) + (p.bk.LD ? 1u : 0u);
 	p.spb = 512;
 	if (512ull * items_per_sample < 16ull * p.n_buckets && scatter_lds_bytes(p.max_lb, 1024, g.n_dims, F) <= 160 * 1024) p.spb = 1024;
 	if (const char* e = getenv("NGP_SC_CHUNK")) p.spb = (uint32_t)atoi(e);
@@ -1294,7 +1577,8 @@ ScatterPlan make_scatter_plan(const GridDesc& g, uint32_t n, bool bricks) {
 	if (const char* e = getenv("NGP_SC_LIMIT")) p.split_limit = (uint32_t)atoi(e);
 	p.max_split_blocks = (uint32_t)(div_round_up(p.n_items, (uint64_t)p.part) + div_round_up(p.n_items, (uint64_t)p.split_limit) + 1);
 	if (p.bk.LD) p.max_split_blocks += (uint32_t)(std::min<uint64_t>(p.bk.NBK, n) + div_round_up((uint64_t)n, (uint64_t)p.brick_part));
-	p.max_split_buckets = (uint32_t)(div_round_up(p.n_items, (uint64_t)p.split_limit) + 1);
+	p.max_split_buckets = (uint32_t)(div_round_up(p.n_items, (uint64_t)p.split_limit) + 1) + p.direct_buckets;
+	const size_t n_slots = (size_t)p.direct_buckets * p.direct_parts + p.max_split_blocks;  // split list entries = scratch slabs
 	p.xcd_map = 2;
 	if (const char* e = getenv("NGP_SC_XCD")) p.xcd_map = (uint32_t)atoi(e);
 	// accumulation block: 512 threads for F = 2 (4 blocks per CU by waves; C2' 328 -> 315 us, C5 1.250 ->
@@ -1309,10 +1593,10 @@ ScatterPlan make_scatter_plan(const GridDesc& g, uint32_t n, bool bricks) {
 	p.off_cur = align(p.off_hist + len * 4);
 	p.off_tot = align(p.off_cur + len * 4);
 	p.off_split = align(p.off_tot + (size_t)p.n_buckets * 4);
-	p.off_lo = align(p.off_split + (2 + 3 * (size_t)p.max_split_blocks) * 4);
+	p.off_lo = align(p.off_split + (2 + 3 * n_slots) * 4);
 	p.off_splitb = align(p.off_lo + (size_t)p.n_buckets * 4);
 	p.off_scratch = align(p.off_splitb + 3 * (size_t)p.max_split_buckets * 4);
-	p.off_idx = align(p.off_scratch + (size_t)p.max_split_blocks * ((size_t)1 << p.B) * g.n_features * 8);
+	p.off_idx = align(p.off_scratch + n_slots * ((size_t)1 << p.B) * g.n_features * 8);
 	p.off_val = align(p.off_idx + p.n_items * 2);
 	p.off_bp = align(p.off_val + p.n_items * F * 2);
 	p.off_fb = align(p.off_bp + (size_t)p.bk.NBK * 8);
@@ -1322,12 +1606,13 @@ ScatterPlan make_scatter_plan(const GridDesc& g, uint32_t n, bool bricks) {
 
 bool scatter_hist(const GridDesc& g, const ScatterPlan& p, void* workspace, GridHist& h) {
 	if ((size_t)p.n_buckets * 4 > 48 * 1024 || p.spb != 512) return false;
-	const Levels lv = make_levels(g, p.B, p.bk);
+	const Levels lv = make_levels(g, p);
 	h.hist = (uint32_t*)((char*)workspace + p.off_hist);
 	h.B = p.B; h.n_chunks = p.n_chunks; h.chunk = p.spb;
 	for (int l = 0; l <= 32; ++l) h.vb_base[l] = lv.vb_base[l];
 	h.brick_first = p.bk.LB; h.brick_levels = p.bk.LD; h.n_bricks = p.bk.NBK; h.brick_cells = p.bk.K; h.bricks_per_dim = p.bk.NB;
 	h.brick_vb0 = p.bk.vb0;
+	h.direct_levels = p.direct_levels;
 	return true;
 }
 
@@ -1337,7 +1622,7 @@ void grid_scatter_prepare(const GridDesc& g, const GridBwdArgs& a, const Scatter
 	uint32_t* hist = (uint32_t*)(ws + p.off_hist);
 	if (!hist_done) {
 		const GridConst c = make_grid_const(g);
-		const Levels lv = make_levels(g, p.B, p.bk);
+		const Levels lv = make_levels(g, p);
 		const dim3 grid_h(p.n_chunks, g.n_levels);
 		const size_t lds_h = (size_t)p.max_lb * 4;
 		auto go = [&](auto k3, auto k2) {
@@ -1350,16 +1635,18 @@ void grid_scatter_prepare(const GridDesc& g, const GridBwdArgs& a, const Scatter
 	}
 	k_sc_scan<<<div_round_up(p.n_buckets, 64), 64 * SCAN_SEG, 0, s>>>(hist, p.n_chunks, p.n_buckets, (uint32_t*)(ws + p.off_cur), (uint32_t*)(ws + p.off_tot));
 	NGP_HIP(hipGetLastError());
+	if (p.plan_inline) return;  // the consumers derive the bucket starts and the split lists themselves (plan_scan)
 	const auto plan = p.n_buckets <= SC_PLAN_THREADS ? k_sc_plan<1> : p.n_buckets <= 8 * SC_PLAN_THREADS ? k_sc_plan<8> : k_sc_plan<32>;
 	plan<<<1, SC_PLAN_THREADS, 0, s>>>((const uint32_t*)(ws + p.off_tot), p.n_buckets, p.split_limit, p.part,
 	                                        (uint32_t*)(ws + p.off_lo), (uint32_t*)(ws + p.off_split), (uint32_t*)(ws + p.off_splitb),
 	                                        p.bk.vb0, p.bk.NBK, p.brick_part, (uint32_t*)(ws + p.off_bp),
-	                                        p.bk.LD ? (uint32_t*)(ws + p.off_fb + (size_t)g.offsets[p.bk.LD] * g.n_features * 8) : nullptr);
+	                                        p.bk.LD ? (uint32_t*)(ws + p.off_fb + (size_t)g.offsets[p.bk.LD] * g.n_features * 8) : nullptr,
+	                                        p.direct_buckets, p.direct_parts);
 	NGP_HIP(hipGetLastError());
 }
 
 uint32_t scatter_bucket_at_param(const GridDesc& g, const ScatterPlan& p, uint64_t param) {
-	const Levels lv = make_levels(g, p.B, p.bk);
+	const Levels lv = make_levels(g, p);
 	for (uint32_t vb = 0; vb < p.n_buckets; ++vb) {
 		uint32_t l = 0;
 		while (lv.vb_base[l + 1] <= vb) ++l;
@@ -1377,7 +1664,7 @@ void grid_backward_sorted(const GridDesc& g, const GridBwdArgs& b, const Scatter
 	NGP_CHECK(!parts || !parts->k || (!p.bk.LD && !(fused && fused->rec) && parts->k <= BwdParts::MAX),
 	          "grid backward parts: not with bricks or the fused update");
 	const GridConst c = make_grid_const(g);
-	const Levels lv = make_levels(g, p.B, p.bk);
+	const Levels lv = make_levels(g, p);
 	const FusedAdam fa = fused ? *fused : FusedAdam{};
 	if (g.n_dims == 3) launch_backward<3>(g.n_features, c, lv, b, p, (char*)workspace, s, overwrite, debug, slab, fa, parts);
 	else launch_backward<2>(g.n_features, c, lv, b, p, (char*)workspace, s, overwrite, debug, slab, fa, parts);

@@ -124,7 +124,8 @@ class Model:
         check(lib().ngp_model_set_option(self.handle, key.encode(), float(value)))
 
     def query(self, key):
-        """engine state (ngp_model_query): "grid_brick_levels" """
+        """engine state (ngp_model_query): "grid_brick_levels", "grid_direct_levels", "grid_direct_part" (samples per
+        direct part), "grid_plan_inline" (the current plan runs without k_sc_plan)"""
         v = C.c_double()
         check(lib().ngp_model_query(self.handle, key.encode(), C.byref(v)))
         return v.value
