@@ -290,6 +290,13 @@ int ngp_sdf_generate_training_samples(ngp_sdf_mesh* m, void* stream, uint32_t n,
                                       const float* aabb_max, float stddev, float* positions, float* distances);
 /* signed_distance_raystab semantics (triangle_bvh.cu:415-433) over every triangle */
 int ngp_sdf_signed_distance(ngp_sdf_mesh* m, void* stream, uint32_t n, const float* positions, float* distances);
+/* The same with the index that seeds each point's stab rays given in rows (device [n]) instead of taken from the
+ * point's place in the batch (the reference jitters the 32 rays of point i by rng.advance(2 i), triangle_bvh.cu:691-695;
+ * a ray can slip between two triangles, so the sign of a point close inside the surface depends on that index about
+ * once in a million). ngp_sdf_signed_distance(positions) == ngp_sdf_signed_distance_rows(positions, rows = 0..n-1).
+ * The sphere tracer passes each ray's pixel, so its ground-truth view does not depend on how rays are compacted. */
+int ngp_sdf_signed_distance_rows(ngp_sdf_mesh* m, void* stream, uint32_t n, const float* positions, const uint32_t* rows,
+                                 float* distances);
 /* shuffle<vec3> / shuffle<float> (testbed_sdf.cu:1295-1296): a bijection seeded by the training step */
 int ngp_sdf_shuffle(void* stream, uint32_t n, uint32_t seed, const float* positions, const float* distances,
                     float* positions_shuffled, float* distances_shuffled);
@@ -435,6 +442,46 @@ int ngp_nerf_renderer_set_show_accel(ngp_nerf_renderer* r, int show_accel);
 int ngp_nerf_render(ngp_nerf_renderer* r, ngp_model* model, const ngp_nerf_config* cfg, void* stream, const ngp_nerf_image* camera,
                     const uint8_t* bitfield, uint32_t spp, uint32_t sample_index, float min_transmittance,
                     const float* background_rgba, int use_inference_params, float* out_rgba);
+
+/* ---- SDF rendering (src/testbed_sdf.cu) --------------------------------------------------------- */
+/* SphereTracer + Testbed::render_sdf (testbed_sdf.cu:47-434, 508-613, 629-1063): sphere tracing of a
+ * distance function from a camera, finite-difference (FiniteDifferenceNormalsApproximator, :853-881) or analytic
+ * (Network::input_gradient dim 0, testbed.cu:4621) normals, soft shadow rays towards the sun (:233-296) and the
+ * Disney-style shading of shade_kernel_sdf (:298-374). Octree skipping, the slice plane, depth of field, foveation,
+ * the envmap and the hidden-area mask are not built. */
+typedef struct ngp_sdf_renderer ngp_sdf_renderer;
+typedef struct {   /* Testbed::Sdf (testbed.h:798-835), BRDFParams, m_sun_dir/m_up_dir (:601-602), floor (:916-917) */
+	float aabb_min[3], aabb_max[3];   /* m_aabb; the tracer's box is this inflated by zero_offset */
+	float zero_offset, distance_scale, maximum_distance, fd_normals_epsilon, shadow_sharpness;
+	uint32_t analytic_normals;        /* network path only; the mesh distance always takes finite differences */
+	uint32_t floor_enable, snap_to_pixel_centers;
+	uint32_t max_iterations;          /* MARCH_ITER (testbed_sdf.cu:37) */
+	float sun_dir[3], up_dir[3];      /* normalised by the renderer, as render_sdf does (:1041-1042) */
+	/* BRDFParams (sdf.h:62-72) */
+	float metallic, subsurface, specular, roughness, sheen, clearcoat, clearcoat_gloss;
+	float basecolor[3], ambientcolor[3];
+} ngp_sdf_render_config;
+/* the reference's defaults (aabb: the unit cube); no GPU call */
+int ngp_sdf_render_default_config(ngp_sdf_render_config* out);
+int ngp_sdf_renderer_create(ngp_sdf_renderer** out);
+void ngp_sdf_renderer_destroy(ngp_sdf_renderer* r);
+/* One view (render_sdf, :883-1063). Exactly one of model / ground_truth non-NULL: the network's distance, or the
+ * mesh's BVH signed distance (m_render_ground_truth with ESDFGroundTruthMode::SignedDistance, testbed.cu:4596-4607).
+ * camera as in ngp_nerf_render (near distance 0, the principal point as screen centre). render_mode (ERenderMode,
+ * common.h:110-119): 0 AO, 1 Shade, 2 Normals, 3 Positions, 4 Depth, 6 Cost; others return NGP_INVALID. spp samples
+ * starting at sample_index are averaged. out_rgba: device float [height x width x 4]: hits get alpha 1, misses
+ * background_rgba (host; NULL = transparent black). out_depth (nullable): device float [height x width], dot(camera
+ * forward, pos - origin), MAX_DEPTH() = 16384 on misses. Null and invalid arguments return NGP_INVALID before any
+ * HIP call. */
+int ngp_sdf_render(ngp_sdf_renderer* r, ngp_model* model, ngp_sdf_mesh* ground_truth, const ngp_sdf_render_config* cfg,
+                   void* stream, const ngp_nerf_image* camera, int render_mode, uint32_t spp, uint32_t sample_index,
+                   const float* background_rgba, int use_inference_params, float* out_rgba, float* out_depth);
+/* compare_signs_kernel without the octree and scale_iou_counters_kernel (testbed_sdf.cu:474-499), the kernels of
+ * Testbed::calculate_iou (:1329-1364): if scale_existing < 1 the eight counters become round(counter * scale_existing),
+ * then the n samples are added (distance <= 0 is inside): [0]/[1] reference inside/outside, [2]/[3] model inside/outside,
+ * [4] both inside, [5] either inside, [6] 0, [7] n. IoU = counters[4] / counters[5]. */
+int ngp_sdf_iou_accumulate(void* stream, uint32_t n, const float* distances_ref, const float* distances_model,
+                           float scale_existing, uint32_t* counters /* device [8] */);
 
 /* Data-parallel NeRF training (no counterpart in the reference, which trains on one GPU: SURVEY F7,
  * §8e). `allreduce` reduces a device buffer in place across the ranks, ordered on `stream` (the

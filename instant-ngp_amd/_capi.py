@@ -70,6 +70,19 @@ class NerfErrorMapInfo(C.Structure):
                 ("n_steps_between_updates", C.c_uint32), ("size", C.c_uint64)]
 
 
+class SdfRenderConfig(C.Structure):
+    """ngp_sdf_render_config: Testbed::Sdf render knobs, sun / up / floor and BRDFParams (testbed.h:798-835, sdf.h:62-72)."""
+    _fields_ = [
+        ("aabb_min", C.c_float * 3), ("aabb_max", C.c_float * 3), ("zero_offset", C.c_float), ("distance_scale", C.c_float),
+        ("maximum_distance", C.c_float), ("fd_normals_epsilon", C.c_float), ("shadow_sharpness", C.c_float),
+        ("analytic_normals", C.c_uint32), ("floor_enable", C.c_uint32), ("snap_to_pixel_centers", C.c_uint32),
+        ("max_iterations", C.c_uint32), ("sun_dir", C.c_float * 3), ("up_dir", C.c_float * 3),
+        ("metallic", C.c_float), ("subsurface", C.c_float), ("specular", C.c_float), ("roughness", C.c_float),
+        ("sheen", C.c_float), ("clearcoat", C.c_float), ("clearcoat_gloss", C.c_float),
+        ("basecolor", C.c_float * 3), ("ambientcolor", C.c_float * 3),
+    ]
+
+
 P = C.c_void_p
 u32, u64, f32, i32, sz = C.c_uint32, C.c_uint64, C.c_float, C.c_int, C.c_size_t
 
@@ -147,8 +160,14 @@ SIGNATURES = {
     "ngp_sdf_bvh_build": (i32, [P, u32, u32, P, C.POINTER(u32)]),
     "ngp_sdf_generate_training_samples": (i32, [P, P, u32, C.POINTER(Rng), P, P, f32, P, P]),
     "ngp_sdf_signed_distance": (i32, [P, P, u32, P, P]),
+    "ngp_sdf_signed_distance_rows": (i32, [P, P, u32, P, P, P]),
     "ngp_sdf_shuffle": (i32, [P, u32, u32, P, P, P, P]),
     "ngp_sdf_train_step": (i32, [P, P, u32, P, P, u32, P, P, P]),
+    "ngp_sdf_render_default_config": (i32, [C.POINTER(SdfRenderConfig)]),
+    "ngp_sdf_renderer_create": (i32, [C.POINTER(P)]),
+    "ngp_sdf_renderer_destroy": (None, [P]),
+    "ngp_sdf_render": (i32, [P, P, P, C.POINTER(SdfRenderConfig), P, C.POINTER(NerfImage), i32, u32, u32, P, i32, P, P]),
+    "ngp_sdf_iou_accumulate": (i32, [P, u32, P, P, f32, P]),
     "ngp_nerf_default_config": (i32, [f32, C.POINTER(NerfConfig)]),
     "ngp_nerf_dataset_create": (i32, [u32, C.POINTER(NerfImage), C.POINTER(P), C.POINTER(P)]),
     "ngp_nerf_dataset_destroy": (None, [P]),

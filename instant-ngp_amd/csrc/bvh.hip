@@ -411,7 +411,7 @@ constexpr uint32_t SIGN_T = 256;  // 8 points per block
 __global__ void __launch_bounds__(SIGN_T) k_sdf_sign(uint32_t n, const float* __restrict__ pos, const BvhNode* __restrict__ nodes,
                                                      const BvhChildBlock* __restrict__ blocks, const float* __restrict__ tris,
                                                      float* __restrict__ dist,
-                                                     unsigned long long* __restrict__ stats) {
+                                                     unsigned long long* __restrict__ stats, const uint32_t* __restrict__ rows) {
 	__shared__ uint32_t escaped[SIGN_T / 32];
 	uint32_t n_inner = 0, n_leaf = 0, n_tri = 0;  // traversal statistics (stats != nullptr: NGP_SDF_STATS)
 	extern __shared__ int stk_all[];
@@ -423,7 +423,9 @@ __global__ void __launch_bounds__(SIGN_T) k_sdf_sign(uint32_t n, const float* __
 	if (i < n) {
 		const V p = vld(pos + 3 * (size_t)i);
 		const uint64_t inc = 0xda3e39cb94b95bdbULL;  // default_rng_t advanced by 2 i
-		uint64_t st = pcg_advanced(0x853c49e6748fea9bULL, inc, 2ull * i);
+		// rows (nullable): the index that seeds point i's stab rays instead of its place in the batch, so that a caller
+		// which reorders its points between calls (the sphere tracer's compaction) gets the same sign for the same point
+		uint64_t st = pcg_advanced(0x853c49e6748fea9bULL, inc, 2ull * (rows ? rows[i] : i));
 		const float ox = pcg_next_float(st, inc), oy = pcg_next_float(st, inc);
 		StabRay r;
 		r.o = p;
@@ -489,7 +491,8 @@ __global__ void __launch_bounds__(SIGN_T) k_sdf_sign(uint32_t n, const float* __
 }
 }  // namespace
 
-void sdf_signed_distance(const SdfMeshDev& m, uint32_t n, const float* positions, float* distances, bool upper_bounds, hipStream_t s) {
+void sdf_signed_distance(const SdfMeshDev& m, uint32_t n, const float* positions, float* distances, bool upper_bounds, hipStream_t s,
+                         const uint32_t* rows) {
 	if (n == 0) return;
 	NGP_CHECK(m.qnodes && m.qtris && m.blocks, "sdf: mesh has no BVH");
 	{
@@ -505,7 +508,7 @@ void sdf_signed_distance(const SdfMeshDev& m, uint32_t n, const float* positions
 	if (want_stats && !stats) NGP_HIP(hipMalloc(&stats, 8 * sizeof(unsigned long long)));
 	if (want_stats) NGP_HIP(hipMemsetAsync(stats, 0, 8 * sizeof(unsigned long long), s));
 	k_sdf_sign<<<div_round_up(n, SIGN_T / 32), SIGN_T, lds, s>>>(n, positions, m.qnodes, m.blocks, m.qtris, distances,
-	                                                            want_stats ? stats : nullptr);
+	                                                            want_stats ? stats : nullptr, rows);
 	NGP_HIP(hipGetLastError());
 	if (want_stats) {  // diagnostics: traversal work per stab ray and per point
 		unsigned long long h[8];

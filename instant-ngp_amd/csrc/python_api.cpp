@@ -116,6 +116,7 @@ struct NerfTrainingView { Testbed* t; };
 struct NerfDatasetView { Testbed* t; };
 struct SdfView { Testbed* t; };
 struct SdfTrainingView { Testbed* t; };
+struct BrdfView { Testbed* t; };  // Testbed::Sdf::brdf (BRDFParams, sdf.h:62-72), a view into the Testbed's render config
 struct ImageView { Testbed* t; };
 struct ImageTrainingView { Testbed* t; };
 
@@ -126,6 +127,29 @@ void nerf_knob(py::class_<V>& c, const char* name, T ngp_nerf_config::*field) {
 	               [field](V& v, T x) {
 		               v.t->nerf_config().*field = x;
 		               v.t->push_nerf_config();
+	               });
+}
+
+// a float member of the SDF render configuration (Testbed::Sdf, BRDFParams)
+template <typename V>
+void sdf_knob(py::class_<V>& c, const char* name, float ngp_sdf_render_config::*field) {
+	c.def_property(name, [field](const V& v) { return v.t->m_sdf_render_cfg.*field; },
+	               [field](V& v, float x) { v.t->m_sdf_render_cfg.*field = x; });
+}
+template <typename V>
+void sdf_vec3(py::class_<V>& c, const char* name, float (ngp_sdf_render_config::*field)[3]) {
+	c.def_property(name, [field](const V& v) { const float* p = v.t->m_sdf_render_cfg.*field; return std::vector<float>(p, p + 3); },
+	               [field, name](V& v, const std::vector<float>& x) {
+		               if (x.size() != 3) throw std::runtime_error(std::string(name) + ": 3 values");
+		               std::copy(x.begin(), x.end(), v.t->m_sdf_render_cfg.*field);
+	               });
+}
+// a vec3 member of the Testbed (m_sun_dir, m_up_dir)
+void testbed_vec3(py::class_<Testbed>& c, const char* name, float (Testbed::*field)[3]) {
+	c.def_property(name, [field](const Testbed& t) { const float* p = t.*field; return std::vector<float>(p, p + 3); },
+	               [field, name](Testbed& t, const std::vector<float>& x) {
+		               if (x.size() != 3) throw std::runtime_error(std::string(name) + ": 3 values");
+		               std::copy(x.begin(), x.end(), t.*field);
 	               });
 }
 
@@ -204,6 +228,17 @@ PYBIND11_MODULE(pyngp, m) {
 		.def_readwrite("shall_train", &Testbed::m_train)
 		.def_readwrite("training_batch_size", &Testbed::m_training_batch_size)
 		.def_readwrite("render_mode", &Testbed::m_render_mode)
+		.def_readwrite("render_groundtruth", &Testbed::m_render_ground_truth)
+		.def_readwrite("render_ground_truth", &Testbed::m_render_ground_truth)
+		.def_readwrite("floor_enable", &Testbed::m_floor_enable)
+		.def_readwrite("snap_to_pixel_centers", &Testbed::m_snap_to_pixel_centers)
+		.def("calculate_iou", &Testbed::calculate_iou, py::call_guard<py::gil_scoped_release>(),
+		     "Calculate the intersection over union error value", py::arg("n_samples") = 128 * 1024 * 1024,
+		     py::arg("scale_existing_results_factor") = 0.0f, py::arg("blocking") = true, py::arg("force_use_octree") = true)
+		.def_property_readonly("aabb", [](const Testbed& t) {  // m_aabb of an SDF testbed: (min, max)
+			return py::make_tuple(std::vector<float>(t.sdf_aabb_min(), t.sdf_aabb_min() + 3),
+			                      std::vector<float>(t.sdf_aabb_max(), t.sdf_aabb_max() + 3));
+		})
 		.def_readwrite("fov_axis", &Testbed::m_fov_axis)
 		.def_readwrite("zoom", &Testbed::m_zoom)
 		.def_property(
@@ -240,6 +275,9 @@ PYBIND11_MODULE(pyngp, m) {
 		.def_property_readonly("nerf", py::cpp_function([](Testbed& t) { return NerfView{&t}; }, py::keep_alive<0, 1>()))
 		.def_property_readonly("sdf", py::cpp_function([](Testbed& t) { return SdfView{&t}; }, py::keep_alive<0, 1>()))
 		.def_property_readonly("image", py::cpp_function([](Testbed& t) { return ImageView{&t}; }, py::keep_alive<0, 1>()));
+
+	testbed_vec3(testbed, "sun_dir", &Testbed::m_sun_dir);
+	testbed_vec3(testbed, "up_dir", &Testbed::m_up_dir);
 
 	py::class_<NerfView> nerf(testbed, "Nerf");
 	nerf.def_property_readonly("training", py::cpp_function([](NerfView& v) { return NerfTrainingView{v.t}; }, py::keep_alive<0, 1>()))
@@ -293,7 +331,26 @@ PYBIND11_MODULE(pyngp, m) {
 		});
 
 	py::class_<SdfView> sdf(testbed, "Sdf");
-	sdf.def_property_readonly("training", py::cpp_function([](SdfView& v) { return SdfTrainingView{v.t}; }, py::keep_alive<0, 1>()));
+	sdf.def_property_readonly("training", py::cpp_function([](SdfView& v) { return SdfTrainingView{v.t}; }, py::keep_alive<0, 1>()))
+		.def_property("analytic_normals", [](SdfView& v) { return v.t->m_sdf_render_cfg.analytic_normals != 0; },
+		              [](SdfView& v, bool x) { v.t->m_sdf_render_cfg.analytic_normals = x ? 1 : 0; })
+		.def_property_readonly("brdf", py::cpp_function([](SdfView& v) { return BrdfView{v.t}; }, py::keep_alive<0, 1>()));
+	sdf_knob(sdf, "zero_offset", &ngp_sdf_render_config::zero_offset);
+	sdf_knob(sdf, "distance_scale", &ngp_sdf_render_config::distance_scale);
+	sdf_knob(sdf, "fd_normals_epsilon", &ngp_sdf_render_config::fd_normals_epsilon);
+	sdf_knob(sdf, "shadow_sharpness", &ngp_sdf_render_config::shadow_sharpness);
+	sdf.def_property("max_iterations", [](SdfView& v) { return v.t->m_sdf_render_cfg.max_iterations; },
+	                 [](SdfView& v, uint32_t x) { v.t->m_sdf_render_cfg.max_iterations = x; });  // engine extension: MARCH_ITER
+	py::class_<BrdfView> brdf(m, "BRDFParams");  // python_api.cu:569-580
+	sdf_knob(brdf, "metallic", &ngp_sdf_render_config::metallic);
+	sdf_knob(brdf, "subsurface", &ngp_sdf_render_config::subsurface);
+	sdf_knob(brdf, "specular", &ngp_sdf_render_config::specular);
+	sdf_knob(brdf, "roughness", &ngp_sdf_render_config::roughness);
+	sdf_knob(brdf, "sheen", &ngp_sdf_render_config::sheen);
+	sdf_knob(brdf, "clearcoat", &ngp_sdf_render_config::clearcoat);
+	sdf_knob(brdf, "clearcoat_gloss", &ngp_sdf_render_config::clearcoat_gloss);
+	sdf_vec3(brdf, "basecolor", &ngp_sdf_render_config::basecolor);
+	sdf_vec3(brdf, "ambientcolor", &ngp_sdf_render_config::ambientcolor);
 	py::class_<SdfTrainingView>(sdf, "Training")
 		.def_property("generate_sdf_data_online", [](SdfTrainingView& v) { return v.t->m_sdf_generate_online; },
 		              [](SdfTrainingView& v, bool x) { v.t->m_sdf_generate_online = x; })

@@ -12,10 +12,12 @@
 //   n_params / n_encoding_params                                         testbed.cu:4843-4856
 //   save_snapshot / load_snapshot                                        testbed.cu:4873-5057
 //   set_camera_to_training_view / render_to_cpu                          testbed.cu:848-856, python_api.cu:418-427
+//   render_sdf (through ngp_sdf_render) / calculate_iou                  testbed_sdf.cu:883-1063, 1329-1364
 // What lives elsewhere: decoding image files (JPEG/PNG/EXR) is the binding's job (python_api.cpp hands the
 // decoded pixels to load_nerf / load_image), as the reference delegates it to stb_image / tinyexr.
 #pragma once
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -208,7 +210,12 @@ struct DeviceBuffer {
 
 class Testbed {
 public:
-	explicit Testbed(ETestbedMode mode = ETestbedMode::None) { set_mode(mode); }
+	explicit Testbed(ETestbedMode mode = ETestbedMode::None) {
+		check(ngp_sdf_render_default_config(&m_sdf_render_cfg), "ngp_sdf_render_default_config");  // no GPU call
+		std::memcpy(m_sun_dir, m_sdf_render_cfg.sun_dir, sizeof(m_sun_dir));
+		std::memcpy(m_up_dir, m_sdf_render_cfg.up_dir, sizeof(m_up_dir));
+		set_mode(mode);
+	}
 	~Testbed() { free_network(); free_data(); }
 	Testbed(const Testbed&) = delete;
 	Testbed& operator=(const Testbed&) = delete;
@@ -517,6 +524,7 @@ public:
 	// averaged; Image: the network evaluated at the pixel centres.
 	std::vector<float> render(uint32_t width, uint32_t height, uint32_t spp, bool linear) {
 		if (width == 0 || height == 0 || spp == 0) throw std::runtime_error("render: empty image");
+		if (!m_model && m_testbed_mode == ETestbedMode::Sdf && m_sdf_mesh) reset_network();  // as train() does
 		if (!m_model) throw std::runtime_error("render: no network (train or load a snapshot first)");
 		std::vector<float> out((size_t)width * height * 4);
 		if (m_testbed_mode == ETestbedMode::Nerf) {
@@ -527,17 +535,7 @@ public:
 			check(ngp_nerf_renderer_set_mode(m_renderer, (int)m_render_mode), "ngp_nerf_renderer_set_mode");
 			// depth_scale = 1 / m_nerf.training.dataset.scale (render_nerf, testbed_nerf.cu:2822)
 			check(ngp_nerf_renderer_set_depth_scale(m_renderer, 1.0f / m_dataset_scale), "ngp_nerf_renderer_set_depth_scale");
-			ngp_nerf_image cam{};
-			cam.width = width;
-			cam.height = height;
-			const float res_axis = (float)(m_fov_axis == 0 ? width : height);
-			cam.focal_length[0] = m_relative_focal_length[0] * res_axis * m_zoom;
-			cam.focal_length[1] = m_relative_focal_length[1] * res_axis * m_zoom;
-			cam.principal_point[0] = 1.0f - m_screen_center[0];
-			cam.principal_point[1] = 1.0f - m_screen_center[1];
-			std::memcpy(cam.xform, m_camera, sizeof(m_camera));
-			cam.lens_mode = m_render_with_lens_distortion ? m_lens_mode : 0;
-			std::memcpy(cam.lens_params, m_lens_params, sizeof(m_lens_params));
+			const ngp_nerf_image cam = render_camera(width, height);
 			const float* g = nullptr;
 			const uint8_t* bf = nullptr;
 			const float* mean = nullptr;
@@ -570,14 +568,92 @@ public:
 				}
 				out[i * 4 + 3] = 1.0f;
 			}
+		} else if (m_testbed_mode == ETestbedMode::Sdf) {
+			// Testbed::render_frame_main's SDF branch (testbed.cu:4590-4640): the network's distance with the inference
+			// (EMA) parameters, or the mesh's own signed distance when render_ground_truth
+			if (m_render_ground_truth && !m_sdf_mesh) throw std::runtime_error("render: render_ground_truth needs a loaded mesh");
+			if (!m_sdf_renderer) check(ngp_sdf_renderer_create(&m_sdf_renderer), "ngp_sdf_renderer_create");
+			const ngp_sdf_render_config cfg = sdf_render_config();
+			const ngp_nerf_image cam = render_camera(width, height);
+			float* dev = m_render_buf.get<float>(out.size());
+			check(ngp_sdf_render(m_sdf_renderer, m_render_ground_truth ? nullptr : m_model, m_render_ground_truth ? m_sdf_mesh : nullptr, &cfg,
+			                     nullptr, &cam, (int)m_render_mode, spp, m_render_sample_index, m_background_color, 1, dev, nullptr),
+			      "ngp_sdf_render");
+			check(ngp_memcpy(out.data(), dev, out.size() * 4, 2), "ngp_memcpy");
 		} else {
-			throw std::runtime_error("render: SDF sphere tracing and volume rendering are out of scope (SURVEY §2)");
+			throw std::runtime_error("render: volume rendering is out of scope (SURVEY §2)");
 		}
 		if (!linear)
 			for (size_t i = 0; i < out.size(); i += 4)
 				for (int c = 0; c < 3; ++c) out[i + c] = linear_to_srgb(out[i + c]);
 		return out;
 	}
+
+	// Testbed::calculate_iou (testbed_sdf.cu:1329-1364) without the octree (force_use_octree is accepted and ignored):
+	// batches of 128^3 uniform positions in the aabb from m_rng (generate_training_samples_sdf's uniform_only branch:
+	// generate_random_uniform then scale_to_aabb), the mesh's and the network's distance at each, the sign counters
+	// accumulated on the device. blocking = false returns the ratio of the counters before this call's samples.
+	double calculate_iou(uint32_t n_samples, float scale_existing_results_factor, bool blocking, bool /*force_use_octree*/) {
+		if (m_testbed_mode != ETestbedMode::Sdf || !m_sdf_mesh) throw std::runtime_error("calculate_iou: no SDF mesh loaded");
+		if (!m_model) reset_network();
+		uint32_t host[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+		const bool fresh = m_iou_counters.p == nullptr;
+		uint32_t* counters = m_iou_counters.get<uint32_t>(8);
+		if (fresh) check(ngp_memcpy(counters, host, sizeof host, 1), "ngp_memcpy");
+		if (!blocking) check(ngp_memcpy(host, counters, sizeof host, 2), "ngp_memcpy");
+		float lo[3], hi[3];
+		for (int d = 0; d < 3; ++d) {
+			lo[d] = m_sdf_aabb_min[d] - m_sdf_render_cfg.zero_offset;
+			hi[d] = m_sdf_aabb_max[d] + m_sdf_render_cfg.zero_offset;
+		}
+		bool scaled = false;
+		std::vector<float> pos, dist;
+		std::vector<uint16_t> half;
+		do {
+			const uint32_t n = std::min(128u * 128u * 128u, n_samples);
+			n_samples -= n;
+			const uint32_t n_pad = (n + 255u) / 256u * 256u;
+			pos.assign((size_t)n_pad * 3, 0.5f);
+			for (size_t i = 0; i < (size_t)n; ++i)
+				for (int d = 0; d < 3; ++d) pos[i * 3 + d] = lo[d] + pcg32_next_float(m_rng) * (hi[d] - lo[d]);
+			float* dpos = m_iou_pos.get<float>((size_t)n_pad * 3);
+			float* dref = m_iou_ref.get<float>(n_pad);
+			float* dmodel = m_iou_model.get<float>(n_pad);
+			uint16_t* dout = m_render_out.get<uint16_t>((size_t)n_pad * 16);
+			check(ngp_memcpy(dpos, pos.data(), pos.size() * 4, 1), "ngp_memcpy");
+			if (n) {
+				check(ngp_sdf_signed_distance(m_sdf_mesh, nullptr, n, dpos, dref), "ngp_sdf_signed_distance");
+				// m_network->inference (:1350): SoA, so the distance is the first n_pad halves; widened to fp32 on the host
+				check(ngp_inference(m_model, nullptr, n_pad, dpos, 3, dout, n_pad, NGP_LAYOUT_SOA, 1), "ngp_inference");
+				half.resize(n);
+				dist.resize(n);
+				check(ngp_memcpy(half.data(), dout, (size_t)n * 2, 2), "ngp_memcpy");
+				for (uint32_t i = 0; i < n; ++i) dist[i] = half_to_float(half[i]);
+				check(ngp_memcpy(dmodel, dist.data(), (size_t)n * 4, 1), "ngp_memcpy");
+			}
+			check(ngp_sdf_iou_accumulate(nullptr, n, dref, dmodel, scaled ? 1.0f : scale_existing_results_factor, counters),
+			      "ngp_sdf_iou_accumulate");
+			scaled = true;
+		} while (n_samples > 0);
+		if (blocking) {
+			check(ngp_stream_synchronize(nullptr), "ngp_stream_synchronize");
+			check(ngp_memcpy(host, counters, sizeof host, 2), "ngp_memcpy");
+		}
+		return (double)host[4] / (double)host[5];
+	}
+	// the SDF render configuration in use: Testbed::Sdf's knobs with the aabb, floor, sun and up of the Testbed
+	ngp_sdf_render_config sdf_render_config() const {
+		ngp_sdf_render_config cfg = m_sdf_render_cfg;
+		std::memcpy(cfg.aabb_min, m_sdf_aabb_min, sizeof(cfg.aabb_min));
+		std::memcpy(cfg.aabb_max, m_sdf_aabb_max, sizeof(cfg.aabb_max));
+		cfg.floor_enable = m_floor_enable ? 1 : 0;
+		cfg.snap_to_pixel_centers = m_snap_to_pixel_centers ? 1 : 0;
+		std::memcpy(cfg.sun_dir, m_sun_dir, sizeof(cfg.sun_dir));
+		std::memcpy(cfg.up_dir, m_up_dir, sizeof(cfg.up_dir));
+		return cfg;
+	}
+	const float* sdf_aabb_min() const { return m_sdf_aabb_min; }
+	const float* sdf_aabb_max() const { return m_sdf_aabb_max; }
 
 	// NeRF training knobs (Testbed::Nerf::Training, testbed.h:716-785) reach a live trainer here
 	ngp_nerf_config& nerf_config() { return m_nerf_cfg; }
@@ -608,6 +684,13 @@ public:
 	float m_sdf_surface_offset_scale = 1.0f;     // Sdf::Training::surface_offset_scale
 	float m_bounding_radius = 1.0f;
 	uint32_t m_training_view = 0;
+	bool m_render_ground_truth = false;          // testbed.h:564
+	bool m_floor_enable = false;                 // testbed.h:916
+	bool m_snap_to_pixel_centers = false;        // testbed.h:984 (the SDF render; NeRF renders follow the training config)
+	float m_sun_dir[3], m_up_dir[3];             // testbed.h:601-602
+	// Testbed::Sdf's render members and its BRDFParams (testbed.h:798-835); aabb, floor, sun and up are filled in by
+	// sdf_render_config()
+	ngp_sdf_render_config m_sdf_render_cfg{};
 
 private:
 	static constexpr float ZERO = 0.f;
@@ -620,6 +703,31 @@ private:
 		r.state += seed;
 		r.state = r.state * mult + r.inc;
 		return r;
+	}
+	// tcnn::pcg32::next_float (pcg32.h): 23 random mantissa bits in [1, 2) minus 1
+	static float pcg32_next_float(ngp_rng& r) {
+		const uint64_t old = r.state;
+		r.state = old * 0x5851F42D4C957F2DULL + r.inc;
+		const uint32_t xs = (uint32_t)(((old >> 18u) ^ old) >> 27u), rot = (uint32_t)(old >> 59u);
+		const uint32_t v = ((xs >> rot) | (xs << ((~rot + 1u) & 31))) >> 9 | 0x3f800000u;
+		float f;
+		std::memcpy(&f, &v, 4);
+		return f - 1.0f;
+	}
+	// the view of render(): the Testbed's camera, relative focal length, zoom and screen centre at a resolution
+	ngp_nerf_image render_camera(uint32_t width, uint32_t height) const {
+		ngp_nerf_image cam{};
+		cam.width = width;
+		cam.height = height;
+		const float res_axis = (float)(m_fov_axis == 0 ? width : height);
+		cam.focal_length[0] = m_relative_focal_length[0] * res_axis * m_zoom;
+		cam.focal_length[1] = m_relative_focal_length[1] * res_axis * m_zoom;
+		cam.principal_point[0] = 1.0f - m_screen_center[0];
+		cam.principal_point[1] = 1.0f - m_screen_center[1];
+		std::memcpy(cam.xform, m_camera, sizeof(m_camera));
+		cam.lens_mode = m_render_with_lens_distortion ? m_lens_mode : 0;
+		std::memcpy(cam.lens_params, m_lens_params, sizeof(m_lens_params));
+		return cam;
 	}
 	void require_nerf_trainer(const char* what) {
 		if (m_testbed_mode != ETestbedMode::Nerf) throw std::runtime_error(std::string(what) + ": not a NeRF testbed");
@@ -638,6 +746,8 @@ private:
 	}
 	void free_data() {
 		if (m_renderer) ngp_nerf_renderer_destroy(m_renderer);
+		if (m_sdf_renderer) ngp_sdf_renderer_destroy(m_sdf_renderer);
+		m_sdf_renderer = nullptr;
 		if (m_nerf_dataset) ngp_nerf_dataset_destroy(m_nerf_dataset);
 		if (m_image) ngp_image_destroy(m_image);
 		if (m_sdf_mesh) ngp_sdf_mesh_destroy(m_sdf_mesh);
@@ -674,6 +784,8 @@ private:
 	uint32_t m_image_res[2] = {0, 0};
 	// SDF
 	ngp_sdf_mesh* m_sdf_mesh = nullptr;
+	ngp_sdf_renderer* m_sdf_renderer = nullptr;
+	DeviceBuffer m_iou_counters, m_iou_pos, m_iou_ref, m_iou_model;  // the training batch buffers stay as they are
 	float m_sdf_aabb_min[3] = {0, 0, 0}, m_sdf_aabb_max[3] = {1, 1, 1};
 	DeviceBuffer m_sdf_pos, m_sdf_dist, m_sdf_pos_s, m_sdf_dist_s;
 	DeviceBuffer m_loss_dev, m_render_buf, m_render_out;

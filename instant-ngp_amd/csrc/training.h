@@ -72,9 +72,11 @@ uint32_t bvh_depth(const std::vector<BvhNode>& nodes);
 // TriangleBvh4::build (triangle_bvh.cu:540-617): reorders tris [n x 9] in place, fills nodes
 void build_bvh4(float* tris, uint32_t n_triangles, uint32_t n_primitives_per_leaf, std::vector<BvhNode>& nodes);
 // signed_distance_gpu, EMeshSdfMode::Raystab (triangle_bvh.cu:436-476): upper_bounds = the distances
-// already hold upper bounds of the true distances (use_existing_distances_as_upper_bounds)
+// already hold upper bounds of the true distances (use_existing_distances_as_upper_bounds). The sign test's 32 stab
+// rays are jittered by a pcg32 advanced by twice the point's index (:691-695); rows (nullable, device [n]) gives that
+// index per point instead of its place in the batch.
 void sdf_signed_distance(const SdfMeshDev& m, uint32_t n, const float* positions, float* distances, bool upper_bounds,
-                         hipStream_t s);
+                         hipStream_t s, const uint32_t* rows = nullptr);
 struct SdfSampleArgs {
 	uint32_t n;                       // multiple of 8 (n/8 * {4 exact, 3 offset, 1 uniform})
 	HostPcg32 rng;

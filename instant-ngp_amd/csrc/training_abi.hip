@@ -257,6 +257,12 @@ int ngp_sdf_signed_distance(ngp_sdf_mesh* m, void* stream, uint32_t n, const flo
 	TRY({ sdf_signed_distance(m->dev(), n, positions, distances, false, S(stream)); });
 }
 
+int ngp_sdf_signed_distance_rows(ngp_sdf_mesh* m, void* stream, uint32_t n, const float* positions, const uint32_t* rows,
+                                 float* distances) {
+	ARG(m && (n == 0 || (positions && rows && distances)));
+	TRY({ sdf_signed_distance(m->dev(), n, positions, distances, false, S(stream), rows); });
+}
+
 int ngp_sdf_shuffle(void* stream, uint32_t n, uint32_t seed, const float* positions, const float* distances,
                     float* positions_shuffled, float* distances_shuffled) {
 	ARG(n == 0 || (positions && distances && positions_shuffled && distances_shuffled));
