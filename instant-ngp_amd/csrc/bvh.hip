@@ -23,6 +23,7 @@
 #include <stack>
 #include <vector>
 
+#include "knobs.h"
 #include "profiler.h"
 #include "training.h"
 
@@ -504,7 +505,7 @@ void sdf_signed_distance(const SdfMeshDev& m, uint32_t n, const float* positions
 	const size_t lds = (size_t)3 * std::max(m.qdepth, 1u) * SIGN_T * sizeof(int);
 	NGP_CHECK(lds <= 64 * 1024, "sdf: BVH too deep for the stab-ray stacks");
 	static unsigned long long* stats = nullptr;
-	const bool want_stats = getenv("NGP_SDF_STATS") != nullptr;
+	const bool want_stats = process_knobs().sdf_stats;
 	if (want_stats && !stats) NGP_HIP(hipMalloc(&stats, 8 * sizeof(unsigned long long)));
 	if (want_stats) NGP_HIP(hipMemsetAsync(stats, 0, 8 * sizeof(unsigned long long), s));
 	k_sdf_sign<<<div_round_up(n, SIGN_T / 32), SIGN_T, lds, s>>>(n, positions, m.qnodes, m.blocks, m.qtris, distances,

@@ -180,6 +180,8 @@ struct ngp_model {
 	bool grid_bricks = false;               // option "grid_bricks": dense levels of the bucketed backward summed per brick (off: measured slower)
 	bool grid_direct = true;                // option "grid_direct": levels of at most two buckets summed without items (ScatterPlan::direct_mask)
 	bool grid_plan_inline = false;          // option "grid_plan_inline": no k_sc_plan launch where the bucket list is small (ScatterPlan::plan_inline; off: measured slower)
+	const ScatterKnobs sc_knobs = ScatterKnobs::read();  // NGP_SC_*: a set switch overrides the three options above
+	ScatterOpts scatter_opts(bool bricks) const { return ScatterOpts{bricks, grid_direct, grid_plan_inline, sc_knobs}; }
 	hipStream_t side = nullptr;             // overlaps fragments + bucket histogram with forward + MLP,
 	                                        // and the dW slab reduction with the grid backward
 	hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_frags = nullptr, ev_mlp = nullptr, ev_red = nullptr;
@@ -243,7 +245,7 @@ struct ngp_model {
 	bool side_prepare(uint32_t n) const { return use_sorted(n) && (overlap & 1); }
 	const ScatterPlan& sc_plan_for(uint32_t n) {
 		if (sc_plan_n != n) {
-			sc_plan = make_scatter_plan(grid, n, grid_bricks, grid_direct, grid_plan_inline);
+			sc_plan = make_scatter_plan(grid, n, scatter_opts(grid_bricks));
 			sc_plan_n = n;
 			fb_dirty = true;  // the brick fallback table may now lie over bytes the previous plan used (items)
 		}
@@ -499,6 +501,7 @@ struct ngp_model {
 
 struct ngp_trainer {
 	ngp_model* model = nullptr;
+	const TrainerKnobs knobs = TrainerKnobs::read();  // at every creation (knobs.h)
 	AdamConfig cfg;
 	uint32_t step = 0;
 	uint64_t n = 0;
@@ -612,8 +615,7 @@ struct ngp_trainer {
 		// next launches. NGP_XS_PRIORITY=0: the default priority (A/B)
 		int lo = 0, hi = 0;
 		NGP_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-		const char* e = getenv("NGP_XS_PRIORITY");
-		NGP_HIP(hipStreamCreateWithPriority(&xs, hipStreamNonBlocking, e && atoi(e) == 0 ? 0 : hi));
+		NGP_HIP(hipStreamCreateWithPriority(&xs, hipStreamNonBlocking, knobs.xs_high_priority ? hi : 0));
 		for (hipEvent_t& ev : ev_part) NGP_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
 		NGP_HIP(hipEventCreateWithFlags(&ev_xs, hipEventDisableTiming));
 	}
@@ -841,7 +843,7 @@ int ngp_stream_synchronize(void* stream) { NGP_TRY(NGP_HIP(hipStreamSynchronize(
 // NGP_MODEL_OPTS="key=value,key=value": engine options applied to every model at creation (A/B runs of whole
 // programs, tools/ab.sh); an unknown key or a bad value fails the creation
 static void apply_env_options(ngp_model* m) {
-	const char* env = getenv("NGP_MODEL_OPTS");
+	const char* env = knob_model_opts();
 	if (!env || !*env) return;
 	std::string all = env;
 	size_t pos = 0;
@@ -1015,7 +1017,7 @@ int ngp_model_query(const ngp_model* m, const char* key, double* value) {
 		const std::string k = key;
 		if (k == "grid_brick_levels") *value = m->sc_plan_n ? (double)(m->sc_plan.bk.LD - m->sc_plan.bk.LB) : 0.0;
 		else if (k == "grid_direct_levels") *value = m->sc_plan_n ? (double)m->sc_plan.direct_levels : 0.0;
-		else if (k == "grid_direct_part") *value = (double)make_scatter_plan(m->grid, 4096, false).direct_part;
+		else if (k == "grid_direct_part") *value = (double)make_scatter_plan(m->grid, 4096, m->scatter_opts(false)).direct_part;
 		else if (k == "grid_plan_inline") *value = m->sc_plan_n && m->sc_plan.plan_inline ? 1.0 : 0.0;
 		else throw Error("unknown model query: " + k);
 	});
@@ -1274,7 +1276,7 @@ int ngp_trainer_create(ngp_model* m, const char* optimizer_json, uint64_t seed, 
 		auto t = std::make_unique<ngp_trainer>();
 		t->model = m;
 		if (optimizer_json) parse_optimizer(Json::parse(optimizer_json), t->cfg);
-		if (const char* e = getenv("NGP_EMA_CLOSED_FORM")) t->cfg.ema_closed_form = atoi(e) != 0;  // A/B runs
+		if (t->knobs.ema_closed_form != KNOB_UNSET) t->cfg.ema_closed_form = t->knobs.ema_closed_form != 0;  // A/B runs
 		// the betas are fixed for the trainer's lifetime (only the learning rate has a setter)
 		NGP_HIP(hipMalloc(&t->bias_tab, (size_t)BIAS_TAB_CAP * 2 * sizeof(float)));
 		adam_bias_table(t->bias_tab, t->cfg.beta1, t->cfg.beta2, nullptr);
@@ -1290,7 +1292,7 @@ int ngp_trainer_create(ngp_model* m, const char* optimizer_json, uint64_t seed, 
 		// EMA's closed-form catch-up, gpurun_out/r04cg); the eager arrays for small models. NGP_LAZY_EMA=0/1
 		// forces the choice.
 		bool lazy = n >= (1ull << 20);
-		if (const char* e = getenv("NGP_LAZY_EMA")) lazy = atoi(e) != 0;
+		if (t->knobs.lazy_ema != KNOB_UNSET) lazy = t->knobs.lazy_ema != 0;
 		lazy = lazy && n % 4 == 0;
 		const size_t brec = al((n + ngp_trainer::SHARD_PAD) / 2 * sizeof(AdamRec));
 		const size_t total = b32 + (lazy ? brec : 4 * b32) + 3 * b16 + 256 /*ctl*/;

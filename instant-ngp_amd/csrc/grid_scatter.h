@@ -1,6 +1,7 @@
 // grid_scatter.h — destination-bucketed hash-grid backward (see grid_scatter.hip).
 #pragma once
 #include "grid.h"
+#include "knobs.h"
 #include "optimizer.h"
 #include "slab_reduce.h"
 
@@ -58,7 +59,12 @@ struct ScatterPlan {
 
 // bricks: allow the brick-summed dense levels (ScatterPlan::bk; chosen only where they move fewer bytes)
 // direct: allow direct levels (ScatterPlan::direct_mask; off with bricks); plan_inline: allow ScatterPlan::plan_inline
-ScatterPlan make_scatter_plan(const GridDesc& g, uint32_t n, bool bricks = true, bool direct = true, bool plan_inline = false);
+// env: the model's environment switches; one that is set overrides the option of the same meaning
+struct ScatterOpts {
+	bool bricks = true, direct = true, plan_inline = false;
+	ScatterKnobs env;
+};
+ScatterPlan make_scatter_plan(const GridDesc& g, uint32_t n, const ScatterOpts& o);
 // Phase 1 (positions only, so it can run on a side stream while the forward pass and the MLP run):
 // bucket histogram per block of samples + per-bucket scans.
 // hist_done: the histogram was produced by the training forward (scatter_hist, grid_forward).

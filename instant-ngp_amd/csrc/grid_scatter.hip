@@ -1466,12 +1466,10 @@ void launch_backward(uint32_t F, const GridConst& c, const Levels& lv, const Gri
 // range fits the bucket's LDS tile (R <= NE) or saves bytes: the slabs (one per non-empty brick and part, R * F
 // int64, written and read once) must cost under 3/4 of the items they replace (2^D per sample and level, also
 // written and read once).
-static BrickConst make_bricks(const GridDesc& g, uint32_t n, uint32_t B, uint32_t brick_part) {
+static BrickConst make_bricks(const GridDesc& g, uint32_t n, uint32_t B, uint32_t brick_part, const ScatterKnobs& env) {
 	BrickConst best;
-	if (g.n_dims != 3) return best;
-	if (const char* e = getenv("NGP_SC_BRICKS")) { if (atoi(e) == 0) return best; }
-	double min_cells = 3.0;
-	if (const char* e = getenv("NGP_SC_BRICK_MIN_CELLS")) min_cells = atof(e);
+	if (g.n_dims != 3 || env.bricks == 0) return best;
+	const double min_cells = env.brick_min_cells;
 	const uint32_t F = g.n_features, NE = 1u << B;
 	// dense levels with T = res^3 exactly (even res: the unclamped upper corners alias modulo res^3 only,
 	// brick_entry_sums), at most 4
@@ -1529,23 +1527,24 @@ static BrickConst make_bricks(const GridDesc& g, uint32_t n, uint32_t B, uint32_
 
 }  // namespace
 
-ScatterPlan make_scatter_plan(const GridDesc& g, uint32_t n, bool bricks, bool direct, bool plan_inline) {
+ScatterPlan make_scatter_plan(const GridDesc& g, uint32_t n, const ScatterOpts& o) {
 	ScatterPlan p;
+	const ScatterKnobs& env = o.env;
 	const uint32_t F = g.n_features;
 	// bucket = 2^B entries of one level whose F int64 accumulators fill SC_LDS_BYTES
 	p.B = 0;
-	size_t lds_budget = SC_LDS_BYTES;  // experiment knob NGP_SC_LDS_KB (<= 64)
-	if (const char* e = getenv("NGP_SC_LDS_KB")) lds_budget = std::min<size_t>(SC_LDS_BYTES, (size_t)atoi(e) * 1024);
+	size_t lds_budget = SC_LDS_BYTES;
+	if (env.lds_kb != KNOB_UNSET) lds_budget = std::min<size_t>(SC_LDS_BYTES, (size_t)env.lds_kb * 1024);
 	while (((size_t)2 << p.B) * F * 8 <= lds_budget && p.B < 16) ++p.B;
-	if (const char* e = getenv("NGP_SC_BRICK_PART")) p.brick_part = std::max(1, atoi(e));
-	if (bricks) p.bk = make_bricks(g, n, p.B, p.brick_part);
+	p.brick_part = (uint32_t)env.brick_part;
+	if (o.bricks) p.bk = make_bricks(g, n, p.B, p.brick_part, env);
 	// direct levels: the leading levels of at most two buckets (level sizes never shrink, so they are a prefix and
 	// their buckets are [0, direct_buckets)); not with bricks
 	p.direct_part = 16384;  // C2: 8192 +1.9 %, 4096 slower still, 32768 +23 % (two long blocks per level half)
-	if (const char* e = getenv("NGP_SC_DIRECT")) direct = atoi(e) != 0;
+	const bool direct = env.direct != KNOB_UNSET ? env.direct != 0 : o.direct;
 	// (F = 8 stays on items: with the direct part the F = 8 accumulate keeps arrays in scratch memory, 808 B per lane)
 	if (direct && !p.bk.LD && n > 0 && F <= 4) {
-		if (const char* e = getenv("NGP_SC_DIRECT_PART")) p.direct_part = (uint32_t)std::max(1, atoi(e));
+		if (env.direct_part != KNOB_UNSET) p.direct_part = (uint32_t)std::max(1, env.direct_part);
 		while (p.direct_levels < g.n_levels && g.offsets[p.direct_levels + 1] - g.offsets[p.direct_levels] <= (2u << p.B)) {
 			p.direct_mask |= 1u << p.direct_levels;
 			++p.direct_levels;
@@ -1555,7 +1554,7 @@ ScatterPlan make_scatter_plan(const GridDesc& g, uint32_t n, bool bricks, bool d
 	const Levels lv = make_levels(g, p.B, p.bk, p.direct_levels, p.direct_part, p.direct_parts);
 	p.direct_buckets = lv.vb_base[p.direct_levels];
 	p.n_buckets = lv.vb_base[g.n_levels];
-	if (const char* e = getenv("NGP_SC_PLAN_INLINE")) plan_inline = atoi(e) != 0;
+	const bool plan_inline = env.plan_inline != KNOB_UNSET ? env.plan_inline != 0 : o.plan_inline;
 	p.plan_inline = plan_inline && !p.bk.LD && p.n_buckets <= SC_PLAN_THREADS;
 	p.max_lb = p.bk.NBK;
 	for (uint32_t l = 0; l < g.n_levels; ++l) p.max_lb = std::max(p.max_lb, lv.vb_base[l + 1] - lv.vb_base[l]);
@@ -1565,26 +1564,23 @@ ScatterPlan make_scatter_plan(const GridDesc& g, uint32_t n, bool bricks, bool d
 	const uint64_t items_per_sample = ((uint64_t)(g.n_levels - (p.bk.LD - p.bk.LB) - p.direct_levels) << g.n_dims) + (p.bk.LD ? 1u : 0u);
 	p.spb = 512;
 	if (512ull * items_per_sample < 16ull * p.n_buckets && scatter_lds_bytes(p.max_lb, 1024, g.n_dims, F) <= 160 * 1024) p.spb = 1024;
-	if (const char* e = getenv("NGP_SC_CHUNK")) p.spb = (uint32_t)atoi(e);
+	if (env.chunk != KNOB_UNSET) p.spb = (uint32_t)env.chunk;
 	NGP_CHECK(p.spb == 512 || p.spb == 1024, "grid backward: chunk must be 512 or 1024 samples");
 	NGP_CHECK(scatter_lds_bytes(p.max_lb, p.spb, g.n_dims, F) <= 160 * 1024, "grid backward: scatter chunk exceeds LDS");
 	p.n_chunks = (uint32_t)div_round_up(n, p.spb);
 	p.n_items = (uint64_t)n * items_per_sample;
 	NGP_CHECK(p.n_items < (1ull << 32), "grid backward: too many contributions for 32-bit offsets");
-	p.split_limit = 49152;
-	p.part = 49152;
-	if (const char* e = getenv("NGP_SC_PART")) p.part = (uint32_t)atoi(e);
-	if (const char* e = getenv("NGP_SC_LIMIT")) p.split_limit = (uint32_t)atoi(e);
+	p.split_limit = (uint32_t)env.limit;
+	p.part = (uint32_t)env.part;
 	p.max_split_blocks = (uint32_t)(div_round_up(p.n_items, (uint64_t)p.part) + div_round_up(p.n_items, (uint64_t)p.split_limit) + 1);
 	if (p.bk.LD) p.max_split_blocks += (uint32_t)(std::min<uint64_t>(p.bk.NBK, n) + div_round_up((uint64_t)n, (uint64_t)p.brick_part));
 	p.max_split_buckets = (uint32_t)(div_round_up(p.n_items, (uint64_t)p.split_limit) + 1) + p.direct_buckets;
 	const size_t n_slots = (size_t)p.direct_buckets * p.direct_parts + p.max_split_blocks;  // split list entries = scratch slabs
-	p.xcd_map = 2;
-	if (const char* e = getenv("NGP_SC_XCD")) p.xcd_map = (uint32_t)atoi(e);
+	p.xcd_map = (uint32_t)env.xcd;
 	// accumulation block: 512 threads for F = 2 (4 blocks per CU by waves; C2' 328 -> 315 us, C5 1.250 ->
 	// 1.235 ms), 1024 for F = 4 (C2: 144 -> 151 us at 512) (profiles/r03ce)
 	p.bt = F == 2 ? 512 : 1024;
-	if (const char* e = getenv("NGP_SC_BT")) p.bt = (uint32_t)atoi(e);
+	if (env.bt != KNOB_UNSET) p.bt = (uint32_t)env.bt;
 	NGP_CHECK(p.bt >= 64 && p.bt <= SC_BT && p.bt % 64 == 0, "grid backward: NGP_SC_BT must be a multiple of 64 up to 1024");
 	const uint64_t len = (uint64_t)p.n_buckets * p.n_chunks;
 	NGP_CHECK(len < (1ull << 31), "grid backward: bucket histogram too large");

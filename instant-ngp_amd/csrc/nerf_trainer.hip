@@ -19,6 +19,7 @@
 
 #include "engine_internal.h"
 #include "json.h"
+#include "knobs.h"
 #include "msgpack.h"
 #include "nerf.h"
 #include "profiler.h"
@@ -69,6 +70,39 @@ struct Buf {
 	~Buf() { if (p) (void)hipFree(p); }
 };
 
+// One cross-queue handoff: the producer's stream signals, the consumer's stream waits for the latest signal. By
+// event, or by value (hipStreamWriteValue32 / hipStreamWaitValue32 on signal memory): a queue idling on a pending
+// event wait starts its next kernel ~10 us after the event's work ends, on a pending value wait ~6 us; a wait that
+// finds its signal complete costs ~1.3 us by event against ~3.6 by value (tools/microbench/queue_handoff.hip,
+// profiles/r06s_queue_handoff.jsonl; sampler -> inference by value: Lego step 0.433 -> 0.428 ms, fox 0.542 -> 0.535).
+struct Handoff {
+	bool by_value = false;
+	hipEvent_t ev = nullptr;
+	uint32_t* sig = nullptr;  // signal memory: only a by-value handoff allocates it
+	uint32_t seq = 0;
+	void signal(hipStream_t producer) {
+		if (by_value) {
+			if (!sig) {
+				NGP_HIP(hipExtMallocWithFlags((void**)&sig, 8, hipMallocSignalMemory));
+				NGP_HIP(hipMemset(sig, 0, 8));
+			}
+			NGP_HIP(hipStreamWriteValue32(producer, sig, ++seq, 0));
+		} else {
+			if (!ev) NGP_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+			NGP_HIP(hipEventRecord(ev, producer));
+		}
+	}
+	void wait(hipStream_t consumer) const {
+		if (!sig && !ev) return;  // never signalled: nothing to wait for
+		if (by_value) NGP_HIP(hipStreamWaitValue32(consumer, sig, seq, hipStreamWaitValueGte, 0xFFFFFFFFu));
+		else NGP_HIP(hipStreamWaitEvent(consumer, ev, 0));
+	}
+	~Handoff() {
+		if (ev) (void)hipEventDestroy(ev);
+		if (sig) (void)hipFree(sig);
+	}
+};
+
 }  // namespace
 
 // external engine entry points used by the orchestrator
@@ -90,6 +124,7 @@ struct ngp_nerf_renderer {
 };
 
 struct ngp_nerf_trainer {
+	const NerfKnobs knobs = NerfKnobs::read();  // at creation (knobs.h)
 	ngp_model* model;
 	ngp_trainer* trainer;
 	const ngp_nerf_dataset* data;
@@ -121,29 +156,17 @@ struct ngp_nerf_trainer {
 	bool prelaunched = false;
 	uint32_t pre_R = 0, pre_max_inference = 0;
 	hipStream_t sample_stream = nullptr;
-	hipEvent_t ev_free = nullptr, ev_samp = nullptr;
-	// The sampler -> inference handoff as hipStreamWriteValue32 / hipStreamWaitValue32 on signal memory: a queue
-	// idling on a pending event wait starts its next kernel ~10 us after the event's work ends, on a pending value
-	// wait ~6 us
-	// (tools/microbench/queue_handoff.hip, profiles/r06s_queue_handoff.jsonl): Lego step 0.433 -> 0.428 ms, fox
-	// 0.542 -> 0.535 ms (gpurun_out/r06t; the release handoff by value too, NGP_NERF_WAITVAL=2: Lego 0.427, fox 0.538).
-	// NGP_NERF_WAITVAL=0: the events (A/B)
-	uint32_t* sig_samp = nullptr;
-	uint32_t* sig_free = nullptr;
-	uint32_t seq_samp = 0, seq_free = 0;
-	void ensure_signals() {
-		if (sig_samp) return;
-		NGP_HIP(hipExtMallocWithFlags((void**)&sig_samp, 8, hipMallocSignalMemory));
-		NGP_HIP(hipExtMallocWithFlags((void**)&sig_free, 8, hipMallocSignalMemory));
-		NGP_HIP(hipMemset(sig_samp, 0, 8));
-		NGP_HIP(hipMemset(sig_free, 0, 8));
-	}
+	// prelaunched sampler -> this step's inference (the consumer is usually already waiting: by value), and the step's
+	// release of the sample buffers -> the next sampler (long done when the host launches that sampler: by event; the
+	// release by value too: Lego 0.427, fox 0.538 ms; not used under early())
+	Handoff sampled{knobs.waitval != 0}, released{knobs.waitval == 2};
 	// Density-grid update pipelining: when the next step is due an update, its sample generation and bin sort read
 	// only the grid (unchanged until that update) and the grid rng, so they run on `sample_stream` under this step's
-	// training pass; the update then starts at the density evaluation (ev_gen). Discarding them restores the rng.
+	// training pass, after the update before it (grid_updated: that one wrote the grid they read and read the buffers
+	// they write); the update then starts at the density evaluation (pregenerated). Discarding them restores the rng.
 	bool grid_pregen = false;
 	uint32_t pregen_nu = 0, pregen_nn = 0;
-	hipEvent_t ev_gen = nullptr;
+	Handoff pregenerated, grid_updated;
 	HostPcg pregen_rng{1};  // grid_rng before the pregenerated samples
 	void drain() {  // the prelaunched sampler finished and discarded (state is about to change)
 		if (sample_stream) (void)hipStreamSynchronize(sample_stream);
@@ -156,10 +179,6 @@ struct ngp_nerf_trainer {
 		if (train_graph) ngp_graph_destroy(train_graph);
 		if (own_stream) (void)hipStreamDestroy(own_stream);
 		if (sample_stream) (void)hipStreamDestroy(sample_stream);
-		for (hipEvent_t e : {ev_free, ev_samp, ev_gen})
-			if (e) (void)hipEventDestroy(e);
-		for (uint32_t* p : {sig_samp, sig_free})
-			if (p) (void)hipFree(p);
 		if (host_ctr) (void)hipHostFree((void*)host_ctr);
 	}
 	// data parallelism: rank r traces global rays [R r / N, R (r+1) / N), compacts to B / N,
@@ -181,7 +200,8 @@ struct ngp_nerf_trainer {
 	// occupancy grid
 	Buf grid, grid_tmp, bitfield, mean, gpos, gidx, gdens, grid_mask, splat_scratch, gpos_sorted;
 	// training workspaces
-	Buf ray_indices, rays, numsteps, coords, mlp_out, dloss, coords_c, loss, counters, scan_tmp, tmp_u32, tmp_f32;
+	Buf mlp_out, dloss, coords_c, loss, scan_tmp, tmp_u32, tmp_f32;
+	struct SampleSet { Buf ray_indices, rays, numsteps, coords, counters; } sets[2];  // the second one: early()
 	// Early publish (one GPU): the counters are published by the loss's scan, so the host launches the next step's
 	// sampler while this step's loss pass 2, rollover and training pass still run; the sampler's outputs then
 	// alternate between two sets by step parity (the set it writes was last read two steps before), so it waits on
@@ -190,10 +210,8 @@ struct ngp_nerf_trainer {
 	// when the training pass starts keeps its one-wave-per-SIMD MLP kernel off the SIMDs (Lego 0.421 -> 0.440 ms,
 	// gpurun_out/r06bd). NGP_NERF_EARLY=1: always, 0: never (publish in the rollover, one set, the sampler waits
 	// for this step's release).
-	Buf ray_indices_b, rays_b, numsteps_b, coords_b, counters_b;
 	bool early() const {
-		static const int knob = getenv("NGP_NERF_EARLY") ? atoi(getenv("NGP_NERF_EARLY")) : -1;
-		const bool on = knob < 0 ? cfg.cone_angle_constant > 1e-5f : knob != 0;
+		const bool on = knobs.early < 0 ? cfg.cone_angle_constant > 1e-5f : knobs.early != 0;
 		return on && !dp();
 	}
 	Buf loss_state;  // compute_loss: pass 1's per-sample compositing state for pass 2 (LossArgs::state)
@@ -639,10 +657,6 @@ int ngp_nerf_trainer_buffers(ngp_nerf_trainer* t, float** grid, uint8_t** bitfie
 // writes every cell. Data parallel: the order within a bin is not deterministic, so the ranks' shards of it would not
 // partition the samples; there each rank evaluates its shard of the generated order and splats it by the binned
 // counting sort (every cell too). A/B knob NGP_SPLAT_SORT=0: memset, generated order, atomics.
-static int splat_mode() {
-	static const int m = getenv("NGP_SPLAT_SORT") ? atoi(getenv("NGP_SPLAT_SORT")) : 1;
-	return m;
-}
 static void grid_update_samples(ngp_nerf_trainer* t, hipStream_t s, uint32_t n_uniform, uint32_t n_nonuniform) {
 	const ngp_nerf_config& cfg = t->cfg;
 	const uint32_t n_cascades = cfg.max_cascade + 1;
@@ -658,7 +672,7 @@ static void grid_update_samples(ngp_nerf_trainer* t, hipStream_t s, uint32_t n_u
 	grid_generate_samples(n_nonuniform, t->grid_rng.dev(), t->ema_step, cfg, grid, n_cascades, MIN_OPTICAL_THICKNESS,
 	                      pos + (size_t)n_uniform * 3, idx + n_uniform, mask, s);
 	t->grid_rng.advance();
-	if (splat_mode() != 0 && t->world == 1)
+	if (t->knobs.splat_sort != 0 && t->world == 1)
 		grid_sort_samples(n, pos, idx, n_el, t->splat_scratch.get<uint32_t>(grid_sort_scratch_u32(n, n_el)),
 		                  t->gpos_sorted.get<float>((size_t)n * 4), s);
 }
@@ -669,8 +683,9 @@ static void grid_update_finish(ngp_nerf_trainer* t, hipStream_t s, float decay, 
 	const uint32_t n = n_uniform + n_nonuniform;
 	float* grid = (float*)t->grid.p;
 	float* tmp = t->grid_tmp.get<float>(n_el);
-	const bool sorted = splat_mode() != 0 && t->world == 1, binned = splat_mode() != 0 && t->world > 1;
-	if (splat_mode() == 0) NGP_HIP(hipMemsetAsync(tmp, 0, (size_t)n_el * 4, s));
+	const int splat_sort = t->knobs.splat_sort;
+	const bool sorted = splat_sort != 0 && t->world == 1, binned = splat_sort != 0 && t->world > 1;
+	if (splat_sort == 0) NGP_HIP(hipMemsetAsync(tmp, 0, (size_t)n_el * 4, s));
 	const uint32_t* idx = t->gidx.get<uint32_t>(n);
 	const uint32_t lo = (uint32_t)((uint64_t)n * t->rank / t->world), hi = (uint32_t)((uint64_t)n * (t->rank + 1) / t->world);
 	const uint32_t ns = hi - lo;
@@ -680,7 +695,7 @@ static void grid_update_finish(ngp_nerf_trainer* t, hipStream_t s, float decay, 
 	if (ns) {
 		// row 0 (raw density) only: the other 15 rows of the density network's output are not read
 		check_rc(ngp::density_impl(t->model, s, ns, dpos + (size_t)lo * dstride, dstride, dens, ns, ngp::DENSITY_LAYOUT_ROW0, 0));
-		if (splat_mode() == 0) grid_splat_max(ns, idx + lo, dens, cfg.density_activation, tmp, s);
+		if (splat_sort == 0) grid_splat_max(ns, idx + lo, dens, cfg.density_activation, tmp, s);
 	}
 	if (sorted)
 		grid_splat_sorted(n_el, t->splat_scratch.get<uint32_t>(grid_sort_scratch_u32(n, n_el)), dpos, dens, lo, hi,
@@ -693,8 +708,7 @@ static void grid_update_finish(ngp_nerf_trainer* t, hipStream_t s, float decay, 
 		NGP_CHECK(t->allreduce(t->allreduce_user, tmp, n_el, NGP_DTYPE_F32, NGP_REDUCE_MAX, s) == 0,
 		          "data parallel: density-grid all-reduce failed");
 	}
-	static const bool fused = !getenv("NGP_GRID_FINAL_FUSED") || atoi(getenv("NGP_GRID_FINAL_FUSED")) != 0;  // A/B knob
-	if (fused) {
+	if (t->knobs.grid_final_fused) {  // A/B knob
 		grid_ema_mean_bitfield(n_el, decay, grid, tmp, cfg.max_cascade, (float*)t->mean.p, (uint8_t*)t->bitfield.p, s);
 	} else {
 		grid_ema(n_el, decay, grid, tmp, s);
@@ -793,12 +807,12 @@ static SamplePlan sample_plan(ngp_nerf_trainer* t) {
 	if (t->measured_before_compaction_local == 0) p.max_inference = p.max_samples;
 	else p.max_inference = next_multiple(std::min(t->measured_before_compaction_local, p.max_samples), 256);
 	p.Ra = std::max(p.Rl, 1u);
-	const bool b = t->early() && (t->training_step & 1u);  // the step's sample set (ngp_nerf_trainer::early)
-	p.ray_indices = (b ? t->ray_indices_b : t->ray_indices).get<uint32_t>(p.Ra);
-	p.rays = (b ? t->rays_b : t->rays).get<float>((size_t)p.Ra * 6);
-	p.numsteps = (b ? t->numsteps_b : t->numsteps).get<uint32_t>((size_t)p.Ra * 2);
-	p.coords = (b ? t->coords_b : t->coords).get<float>((size_t)p.max_samples * 7);
-	p.ctr = (b ? t->counters_b : t->counters).get<uint32_t>(4);  // rays kept, steps, compacted steps
+	auto& set = t->sets[t->early() && (t->training_step & 1u)];  // the step's sample set (ngp_nerf_trainer::early)
+	p.ray_indices = set.ray_indices.get<uint32_t>(p.Ra);
+	p.rays = set.rays.get<float>((size_t)p.Ra * 6);
+	p.numsteps = set.numsteps.get<uint32_t>((size_t)p.Ra * 2);
+	p.coords = set.coords.get<float>((size_t)p.max_samples * 7);
+	p.ctr = set.counters.get<uint32_t>(4);  // rays kept, steps, compacted steps
 	return p;
 }
 static void launch_sampler(ngp_nerf_trainer* t, const SamplePlan& p, hipStream_t s) {
@@ -904,22 +918,19 @@ int ngp_nerf_trainer_set_pipeline(ngp_nerf_trainer* t, int enable) {
 	});
 }
 
-// The pipelined sampler's stream. Experiment knobs (A/B): NGP_SAMPLER_PRIO / NGP_MAIN_PRIO -1 low,
+// The trainer's streams. Experiment knobs (A/B): NGP_SAMPLER_PRIO / NGP_MAIN_PRIO -1 low,
 // 1 high (HSA queue priority: which queue's workgroups the dispatcher places first); NGP_SAMPLER_CU_KEEP k in 1..7:
 // the sampler's queue may use k of every 8 CUs (CU mask), so the training pass's one-block-per-CU MLP kernel
 // finds whole CUs free on the rest.
-static int env_prio(const char* name) {
-	const char* v = getenv(name);
-	if (!v || !*v) return 0;
-	const int p = atoi(v);
+static int stream_prio(int knob) {
+	if (!knob) return 0;
 	int least = 0, greatest = 0;
 	NGP_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-	return p < 0 ? least : (p > 0 ? greatest : 0);  // lower number = higher priority
+	return knob < 0 ? least : greatest;  // lower number = higher priority
 }
-static hipStream_t make_sampler_stream() {
+static hipStream_t make_sampler_stream(const NerfKnobs& knobs) {
 	hipStream_t s = nullptr;
-	const char* keep = getenv("NGP_SAMPLER_CU_KEEP");
-	const int k = keep ? atoi(keep) : 0;
+	const int k = knobs.sampler_cu_keep;
 	if (k > 0 && k < 8) {
 		int dev = 0, n_cu = 0;
 		NGP_HIP(hipGetDevice(&dev));
@@ -930,235 +941,256 @@ static hipStream_t make_sampler_stream() {
 		NGP_HIP(hipExtStreamCreateWithCUMask(&s, (uint32_t)mask.size(), mask.data()));
 		return s;
 	}
-	const int prio = env_prio("NGP_SAMPLER_PRIO");
+	const int prio = stream_prio(knobs.sampler_prio);
 	if (prio) NGP_HIP(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, prio));
 	else NGP_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
 	return s;
 }
+// the step's stream: the caller's, or a private blocking one (ordered after the null stream's earlier work)
+static hipStream_t step_stream(ngp_nerf_trainer* t, void* stream) {
+	if (stream) return S(stream);
+	if (!t->own_stream) {
+		const int prio = stream_prio(t->knobs.main_prio);
+		if (prio) NGP_HIP(hipStreamCreateWithPriority(&t->own_stream, hipStreamDefault, prio));
+		else NGP_HIP(hipStreamCreate(&t->own_stream));
+	}
+	return t->own_stream;
+}
 
-// 1: the sampler -> inference handoff by value (default); 2: the buffer release too; 0: events only (A/B)
-static int nerf_waitval() {
-	static const int v = getenv("NGP_NERF_WAITVAL") ? atoi(getenv("NGP_NERF_WAITVAL")) : 1;
-	return v;
+// ---- the stages of ngp_nerf_train_step, in the order they run ---------------------------------------------------
+// What the stages of one step share: its sampling plan, its workspaces and its mode.
+struct Step {
+	bool pre = false;       // the sampler was launched under the last step's training pass
+	bool get_loss = false;
+	SamplePlan sp;
+	f16 *mlp_out = nullptr, *dloss = nullptr;
+	float *coords_c = nullptr, *loss = nullptr;
+	ngp_rng rng;            // the step's rays (the training pass advances the trainer's)
+	bool dp = false;
+	bool early_pub = false;     // the loss's scan publishes the counters (ngp_nerf_trainer::early)
+	bool can_pipeline = false;  // the next step's sampler may run under this step's training pass: the exchange is
+	                            // stream-ordered (single GPU, or the engine's RCCL communicator)
+};
+
+// training_prep_nerf (a prelaunched sampler implies no update was due at this step)
+static void step_density_grid(ngp_nerf_trainer* t, hipStream_t s, const Step& c) {
+	if (c.pre || !density_grid_update_due(t->training_step)) return;
+	{
+		ProfScope ps("nerf_density_grid", s);
+		uint32_t nu, nn;
+		grid_update_counts(t, t->training_step, &nu, &nn);
+		if (t->grid_pregen) {  // the samples were generated (and sorted) under the last step's training pass
+			NGP_CHECK(nu == t->pregen_nu && nn == t->pregen_nn, "nerf: pregenerated density-grid samples are stale");
+			t->grid_pregen = false;
+			t->pregenerated.wait(s);
+			grid_update_finish(t, s, 0.95f, nu, nn);
+		} else {
+			update_density_grid(t, s, 0.95f, nu, nn);
+		}
+	}
+	t->grid_updated.signal(s);
+}
+
+// train_nerf_step's sizes and workspaces (testbed_nerf.cu:3867-3953)
+static void step_plan(ngp_nerf_trainer* t, Step& c) {
+	c.sp = sample_plan(t);
+	const SamplePlan& sp = c.sp;
+	if (t->training_step == 0) t->n_rays_total = 0;
+	t->n_rays_total += sp.R;
+	c.mlp_out = t->mlp_out.get<f16>((size_t)std::max(sp.Bl, sp.max_samples) * 16);
+	c.dloss = t->dloss.get<f16>((size_t)sp.Bl * 16);
+	c.coords_c = t->coords_c.get<float>((size_t)sp.Bl * 7);
+	c.loss = t->loss.get<float>(sp.Ra);
+	c.rng = ngp_rng{t->rng.state, t->rng.inc};
+	c.dp = t->dp();
+	c.early_pub = t->early() && sp.Rl > 0;
+	c.can_pipeline = t->pipeline && (!c.dp || t->dp_capturable);
+}
+
+// The step's samples (launched here, or awaited from the prelaunch) and the network's output for every one of them.
+// Global ray ids (rng.advance(i * 16), image_idx(i, R)) so the shards draw the 1-GPU rays.
+static void step_sample_and_infer(ngp_nerf_trainer* t, hipStream_t s, const Step& c) {
+	const SamplePlan& sp = c.sp;
+	if (c.pre) {
+		NGP_CHECK(sp.R == t->pre_R && sp.max_inference == t->pre_max_inference, "nerf: prelaunched sampler is stale");
+		t->sampled.wait(s);
+	} else {
+		launch_sampler(t, sp, s);
+	}
+	ProfScope ps("nerf_inference", s);
+	// only the 4 live outputs (raw rgb, raw density): compute_loss reads nothing else
+	check_rc(ngp_inference(t->model, s, sp.max_inference, sp.coords, 7, c.mlp_out, 4, NGP_LAYOUT_AOS_RGBD, 0));
+}
+
+// Loss and compaction, rollover, and the step's counters to the host. The counters are final here (the training
+// pass does not touch them): published before the training pass, the host can size the next step while it runs.
+static void step_loss_and_publish(ngp_nerf_trainer* t, hipStream_t s, const Step& c) {
+	const SamplePlan& sp = c.sp;
+	const uint32_t R = sp.R, Rl = sp.Rl, Bl = sp.Bl;
+	uint32_t* ctr = sp.ctr;
+	// dL/doutput is scaled by 128 / R (global), so the shards' summed gradient is the 1-GPU gradient
+	const float loss_scale_local = 128.0f * (float)Rl / (float)R;
+	float* error_map = error_map_window(t, s);
+	if (!t->host_ctr) {
+		void* p = nullptr;
+		NGP_HIP(hipHostMalloc(&p, 64, hipHostMallocCoherent | hipHostMallocMapped));
+		t->host_ctr = (volatile uint32_t*)p;
+		memset(p, 0, 64);
+	}
+	const uint32_t pub_seq = c.dp ? 0u : ++t->publish_seq;
+	{
+		ProfScope ps("nerf_loss", s);
+		// pass 1 keeps each composited sample's state for pass 2 (indexed like the sampler's samples, at most max_samples)
+		float* lstate = t->knobs.loss_state ? t->loss_state.get<float>((size_t)5 * sp.max_samples) : nullptr;
+		check_rc(nerf_compute_loss(t->data, &t->cfg, s, Rl, R, c.rng, Bl, ctr, c.mlp_out, 4, sp.ray_indices, sp.rays, sp.numsteps,
+		                           sp.coords, c.coords_c, c.dloss, c.loss, ctr + 2, (const float*)t->mean.p,
+		                           c.dp ? loss_scale_local : 128.0f, true, error_map, t->em_w, t->em_h, lstate, sp.max_samples,
+		                           c.early_pub ? t->host_ctr : nullptr, pub_seq));
+	}
+	if (!c.dp) {
+		// single GPU: the rollover launch (fill_rollover_and_rescale + fill_rollover) also publishes the counters
+		// (early_pub: already published) and writes the optimizer control block the training graph reads (a separate
+		// publish kernel and ngp_graph_launch's k_set_ctl before: two launches less per step)
+		StepPublish pub{};
+		pub.ctr = ctr;
+		pub.host = c.early_pub ? nullptr : t->host_ctr;
+		pub.seq = pub_seq;
+		trainer_ctl_values(t->trainer, &pub.ctl, &pub.step, &pub.cfg_off, &pub.cfg_words, pub.cfg);
+		fill_rollover_pair_publish(Bl, ctr + 2, c.dloss, 16, c.coords_c, 7, pub, s);
+	} else {
+		fill_rollover_pair(Bl, ctr + 2, c.dloss, 16, c.coords_c, 7, s);  // fill_rollover_and_rescale + fill_rollover
+		// NerfCounters::update_after_training on the global batch: this shard's counters and loss
+		// all-reduced on the stream, then published like the single-GPU counters (no copies, no sync)
+		ProfScope ps("nerf_dp_counters", s);
+		float* d = t->dp_scalars.get<float>(8);
+		k_dp_pack<<<1, 1024, 0, s>>>(ctr, c.loss, c.get_loss ? Rl : 0u, (float)Rl / (float)R, d);
+		NGP_HIP(hipGetLastError());
+		NGP_CHECK(t->allreduce(t->allreduce_user, d, 5, NGP_DTYPE_F32, NGP_REDUCE_SUM, s) == 0,
+		          "data parallel: counter all-reduce failed");
+		k_dp_publish<<<1, 64, 0, s>>>(d, ctr, t->host_ctr, ++t->publish_seq);
+	}
+	NGP_HIP(hipGetLastError());
+}
+
+// The sample buffers and counters are free for the next step's sampler (early(): nothing to release, that sampler
+// writes the other sample set)
+static void step_release_samples(ngp_nerf_trainer* t, hipStream_t s, const Step& c) {
+	if (!c.can_pipeline) return;
+	if (!t->sample_stream) t->sample_stream = make_sampler_stream(t->knobs);
+	if (!t->early()) t->released.signal(s);
+}
+
+static void step_train_pass(ngp_nerf_trainer* t, hipStream_t s, const Step& c) {
+	const uint32_t Bl = c.sp.Bl;
+	ProfScope ps("nerf_train_pass", s);
+	if (!c.dp || t->dp_capturable) {
+		// one HIP graph per step: forward_backward [+ the gradient all-reduce, RCCL] + optimizer. Re-record
+		// when the graph's buffers moved: the sample buffers, or any model workspace (a density-grid
+		// update through ngp_density can grow the encoding workspace after a snapshot load)
+		if (!t->train_graph || t->graph_in != c.coords_c || t->graph_dl != c.dloss || t->graph_n != Bl ||
+		    t->graph_epoch != ngp_model_workspace_epoch(t->model)) {
+			if (t->train_graph) ngp_graph_destroy(t->train_graph);
+			t->train_graph = nullptr;
+			// data parallel: the shards' dL/doutput is scaled by 128 / R_global, so the summed gradient is the
+			// 1-GPU gradient: world factor 1 in the optimizer
+			check_rc(capture_training_step_with(t->trainer, s, Bl, c.coords_c, 7, c.dloss, 16, 128.0f, 1, 1, t->exchange(),
+			                                    &t->train_graph));
+			t->graph_in = c.coords_c;
+			t->graph_dl = c.dloss;
+			t->graph_n = Bl;
+			t->graph_epoch = ngp_model_workspace_epoch(t->model);
+		}
+		if (c.dp) check_rc(ngp_graph_launch(t->train_graph, s));
+		else graph_launch_ctl_written(t->train_graph, s);  // the control block was written by the rollover launch
+	} else {
+		// host-callback exchange (gloo): not capturable; the same step body, launched eagerly
+		check_rc(train_step_with(t->trainer, s, Bl, c.coords_c, 7, c.dloss, 16, 128.0f, t->exchange()));
+	}
+	t->rng.advance();  // m_rng.advance() (testbed_nerf.cu:4127)
+}
+
+// NerfCounters::update_after_training (testbed_nerf.cu:3583-3609): the host reads the step's counters and adapts
+// rays_per_batch to the measured batch. Returns the step's loss (get_loss).
+static float step_read_counters(ngp_nerf_trainer* t, hipStream_t s, const Step& c) {
+	const uint32_t B = t->cfg.target_batch_size, Rl = c.sp.Rl;
+	uint32_t h[4];
+	double loss_sum = 0;
+	if (c.get_loss && Rl && !c.dp) {
+		std::vector<float> hl(Rl);
+		NGP_HIP(hipMemcpyAsync(hl.data(), c.loss, (size_t)Rl * 4, hipMemcpyDeviceToHost, s));
+		NGP_HIP(hipStreamSynchronize(s));
+		for (float v : hl) loss_sum += v;
+	} else {
+		wait_published(t->host_ctr, t->publish_seq, s);
+	}
+	for (int k = 0; k < 4; ++k) h[k] = t->host_ctr[k];
+	if (c.dp) {
+		const uint32_t lb = t->host_ctr[5];
+		float lv;
+		memcpy(&lv, &lb, 4);
+		loss_sum = lv;
+		t->measured_before_compaction_local = t->host_ctr[6];
+	} else {
+		t->measured_before_compaction_local = h[1];
+	}
+	float loss_scalar = 0.f;
+	t->measured_batch_size = 0;
+	t->measured_before_compaction = 0;
+	if (h[1] != 0 && h[2] != 0) {
+		t->measured_before_compaction = h[1];
+		t->measured_batch_size = h[2];
+		if (c.get_loss) t->loss_scalar = loss_scalar = (float)(loss_sum * (double)t->measured_batch_size / (double)B);
+		uint32_t r = (uint32_t)((float)t->rays_per_batch * (float)B / (float)t->measured_batch_size);
+		t->rays_per_batch = std::min(next_multiple(r, 256), 1u << 18);
+	}
+	return loss_scalar;
+}
+
+// next step's sampler, concurrent with this step's training pass (no density-grid update due first)
+static void step_prelaunch_sampler(ngp_nerf_trainer* t, const Step& c) {
+	if (!c.can_pipeline || t->measured_batch_size == 0 || density_grid_update_due(t->training_step)) return;
+	const SamplePlan np = sample_plan(t);
+	// early(): the sampler writes the other sample set, which the step before last read (complete: this step's
+	// counters are published), so it waits on nothing
+	if (!t->early()) t->released.wait(t->sample_stream);
+	launch_sampler(t, np, t->sample_stream);
+	t->sampled.signal(t->sample_stream);
+	t->pre_R = np.R;
+	t->pre_max_inference = np.max_inference;
+	t->prelaunched = true;
+}
+
+// next step's density-grid update: its samples now, under this step's training pass (one GPU)
+static void step_pregenerate_grid_samples(ngp_nerf_trainer* t, const Step& c) {
+	if (!t->knobs.grid_pregen || !c.can_pipeline || c.dp || t->training_step == 0 || !density_grid_update_due(t->training_step)) return;
+	grid_update_counts(t, t->training_step, &t->pregen_nu, &t->pregen_nn);
+	t->pregen_rng = t->grid_rng;
+	// complete by now (the host has read this step's counters, published after the update)
+	t->grid_updated.wait(t->sample_stream);
+	grid_update_samples(t, t->sample_stream, t->pregen_nu, t->pregen_nn);
+	t->pregenerated.signal(t->sample_stream);
+	t->grid_pregen = true;
 }
 
 int ngp_nerf_train_step(ngp_nerf_trainer* t, void* stream, int get_loss, ngp_nerf_stats* st) {
 	if (!t) return NGP_INVALID;
 	NERF_TRY({
-		hipStream_t s = S(stream);
-		if (!s) {  // a private blocking stream (ordered after the null stream's earlier work)
-			if (!t->own_stream) {
-				const int prio = env_prio("NGP_MAIN_PRIO");
-				if (prio) NGP_HIP(hipStreamCreateWithPriority(&t->own_stream, hipStreamDefault, prio));
-				else NGP_HIP(hipStreamCreate(&t->own_stream));
-			}
-			s = t->own_stream;
-		}
-		const ngp_nerf_config& cfg = t->cfg;
-		const uint32_t B = cfg.target_batch_size;
-		const bool pre = t->prelaunched;
+		hipStream_t s = step_stream(t, stream);
+		Step c;
+		c.pre = t->prelaunched;
+		c.get_loss = get_loss != 0;
 		t->prelaunched = false;
-		// training_prep_nerf (a prelaunched sampler implies no update was due at this step)
-		if (!pre && density_grid_update_due(t->training_step)) {
-			ProfScope ps("nerf_density_grid", s);
-			uint32_t nu, nn;
-			grid_update_counts(t, t->training_step, &nu, &nn);
-			if (t->grid_pregen) {  // the samples were generated (and sorted) under the last step's training pass
-				NGP_CHECK(nu == t->pregen_nu && nn == t->pregen_nn, "nerf: pregenerated density-grid samples are stale");
-				t->grid_pregen = false;
-				NGP_HIP(hipStreamWaitEvent(s, t->ev_gen, 0));
-				grid_update_finish(t, s, 0.95f, nu, nn);
-			} else {
-				update_density_grid(t, s, 0.95f, nu, nn);
-			}
-		}
-		// train_nerf_step (testbed_nerf.cu:3867-4132)
-		const SamplePlan sp = sample_plan(t);
-		const uint32_t R = sp.R, Rl = sp.Rl, Bl = sp.Bl, max_inference = sp.max_inference, Ra = sp.Ra;
-		if (t->training_step == 0) t->n_rays_total = 0;
-		t->n_rays_total += R;
-		uint32_t* ray_indices = sp.ray_indices;
-		float* rays = sp.rays;
-		uint32_t* numsteps = sp.numsteps;
-		float* coords = sp.coords;
-		uint32_t* ctr = sp.ctr;
-		f16* mlp_out = t->mlp_out.get<f16>((size_t)std::max(Bl, sp.max_samples) * 16);
-		f16* dloss = t->dloss.get<f16>((size_t)Bl * 16);
-		float* coords_c = t->coords_c.get<float>((size_t)Bl * 7);
-		float* loss = t->loss.get<float>(Ra);
-		ngp_rng rng{t->rng.state, t->rng.inc};
-		// global ray ids (rng.advance(i * 16), image_idx(i, R)) so the shards draw the 1-GPU rays;
-		// dL/doutput is scaled by 128 / R (global), so the summed gradient is the 1-GPU gradient
-		if (pre) {
-			NGP_CHECK(sp.R == t->pre_R && sp.max_inference == t->pre_max_inference, "nerf: prelaunched sampler is stale");
-			if (nerf_waitval()) NGP_HIP(hipStreamWaitValue32(s, t->sig_samp, t->seq_samp, hipStreamWaitValueGte, 0xFFFFFFFFu));
-			else NGP_HIP(hipStreamWaitEvent(s, t->ev_samp, 0));
-		} else {
-			launch_sampler(t, sp, s);
-		}
-		{
-		ProfScope ps("nerf_inference", s);
-		// only the 4 live outputs (raw rgb, raw density): compute_loss reads nothing else
-		check_rc(ngp_inference(t->model, s, max_inference, coords, 7, mlp_out, 4, NGP_LAYOUT_AOS_RGBD, 0));
-		}
-		const bool dp = t->dp();
-		const float loss_scale_local = 128.0f * (float)Rl / (float)R;
-		float* error_map = error_map_window(t, s);
-		if (!t->host_ctr) {
-			void* p = nullptr;
-			NGP_HIP(hipHostMalloc(&p, 64, hipHostMallocCoherent | hipHostMallocMapped));
-			t->host_ctr = (volatile uint32_t*)p;
-			memset(p, 0, 64);
-		}
-		const bool early_pub = t->early() && Rl > 0;
-		const uint32_t pub_seq = dp ? 0u : ++t->publish_seq;
-		{
-		ProfScope ps("nerf_loss", s);
-		// pass 1 keeps each composited sample's state for pass 2 (indexed like the sampler's samples, at most max_samples)
-		static const bool keep_state = !getenv("NGP_LOSS_STATE") || atoi(getenv("NGP_LOSS_STATE")) != 0;  // A/B knob
-		float* lstate = keep_state ? t->loss_state.get<float>((size_t)5 * sp.max_samples) : nullptr;
-		check_rc(nerf_compute_loss(t->data, &cfg, s, Rl, R, rng, Bl, ctr, mlp_out, 4, ray_indices, rays, numsteps, coords, coords_c,
-		                               dloss, loss, ctr + 2, (const float*)t->mean.p, dp ? loss_scale_local : 128.0f, true,
-		                               error_map, t->em_w, t->em_h, lstate, sp.max_samples, early_pub ? t->host_ctr : nullptr,
-		                               pub_seq));
-		}
-		// the step's counters are final here (the training pass does not touch them): publish them before
-		// the training pass so the host can size the next step while it runs (early_pub: already published)
-		if (!dp) {
-			// single GPU: the rollover launch (fill_rollover_and_rescale + fill_rollover) also publishes the counters
-			// and writes the optimizer control block the training graph reads (a separate publish kernel and
-			// ngp_graph_launch's k_set_ctl before: two launches less per step)
-			StepPublish pub{};
-			pub.ctr = ctr;
-			pub.host = early_pub ? nullptr : t->host_ctr;
-			pub.seq = pub_seq;
-			trainer_ctl_values(t->trainer, &pub.ctl, &pub.step, &pub.cfg_off, &pub.cfg_words, pub.cfg);
-			fill_rollover_pair_publish(Bl, ctr + 2, dloss, 16, coords_c, 7, pub, s);
-		} else {
-			fill_rollover_pair(Bl, ctr + 2, dloss, 16, coords_c, 7, s);  // fill_rollover_and_rescale + fill_rollover
-		}
-		if (dp) {
-			// NerfCounters::update_after_training on the global batch: this shard's counters and loss
-			// all-reduced on the stream, then published like the single-GPU counters (no copies, no sync)
-			ProfScope ps("nerf_dp_counters", s);
-			float* d = t->dp_scalars.get<float>(8);
-			k_dp_pack<<<1, 1024, 0, s>>>(ctr, loss, get_loss ? Rl : 0u, (float)Rl / (float)R, d);
-			NGP_HIP(hipGetLastError());
-			NGP_CHECK(t->allreduce(t->allreduce_user, d, 5, NGP_DTYPE_F32, NGP_REDUCE_SUM, s) == 0,
-			          "data parallel: counter all-reduce failed");
-			k_dp_publish<<<1, 64, 0, s>>>(d, ctr, t->host_ctr, ++t->publish_seq);
-		}
-		NGP_HIP(hipGetLastError());
-		// the next step's sampler may run under this step's training pass when the exchange is
-		// stream-ordered (single GPU, or the engine's RCCL communicator)
-		const bool can_pipeline = t->pipeline && (!dp || t->dp_capturable);
-		if (can_pipeline) {
-			if (!t->sample_stream) {
-				t->sample_stream = make_sampler_stream();
-				NGP_HIP(hipEventCreateWithFlags(&t->ev_free, hipEventDisableTiming));
-				NGP_HIP(hipEventCreateWithFlags(&t->ev_samp, hipEventDisableTiming));
-			}
-			// sample buffers and counters released: an event (by the time the host launches the next sampler this
-			// is long done, and a completed event's wait costs ~1.3 us against ~3.6 for a value wait)
-			if (t->early()) {
-				// nothing to release: the next sampler writes the other sample set
-			} else if (nerf_waitval() == 2) {
-				t->ensure_signals();
-				NGP_HIP(hipStreamWriteValue32(s, t->sig_free, ++t->seq_free, 0));
-			} else {
-				NGP_HIP(hipEventRecord(t->ev_free, s));
-			}
-		}
-		{
-		ProfScope ps("nerf_train_pass", s);
-		if (!dp || t->dp_capturable) {
-			// one HIP graph per step: forward_backward [+ the gradient all-reduce, RCCL] + optimizer. Re-record
-			// when the graph's buffers moved: the sample buffers, or any model workspace (a density-grid
-			// update through ngp_density can grow the encoding workspace after a snapshot load)
-			if (!t->train_graph || t->graph_in != coords_c || t->graph_dl != dloss || t->graph_n != Bl ||
-			    t->graph_epoch != ngp_model_workspace_epoch(t->model)) {
-				if (t->train_graph) ngp_graph_destroy(t->train_graph);
-				t->train_graph = nullptr;
-				// data parallel: the shards' dL/doutput is scaled by 128 / R_global, so the summed gradient is the
-				// 1-GPU gradient: world factor 1 in the optimizer
-				check_rc(capture_training_step_with(t->trainer, s, Bl, coords_c, 7, dloss, 16, 128.0f, 1, 1, t->exchange(),
-				                                    &t->train_graph));
-				t->graph_in = coords_c;
-				t->graph_dl = dloss;
-				t->graph_n = Bl;
-				t->graph_epoch = ngp_model_workspace_epoch(t->model);
-			}
-			if (dp) check_rc(ngp_graph_launch(t->train_graph, s));
-			else graph_launch_ctl_written(t->train_graph, s);  // the control block was written by the rollover launch
-		} else {
-			// host-callback exchange (gloo): not capturable; the same step body, launched eagerly
-			check_rc(train_step_with(t->trainer, s, Bl, coords_c, 7, dloss, 16, 128.0f, t->exchange()));
-		}
-		t->rng.advance();  // m_rng.advance() (testbed_nerf.cu:4127)
-		}
+		step_density_grid(t, s, c);
+		step_plan(t, c);
+		step_sample_and_infer(t, s, c);
+		step_loss_and_publish(t, s, c);
+		step_release_samples(t, s, c);
+		step_train_pass(t, s, c);
 		++t->training_step;
-		// NerfCounters::update_after_training (testbed_nerf.cu:3583-3609): host sync
-		uint32_t h[4];
-		double loss_sum = 0;
-		if (get_loss && Rl && !dp) {
-			std::vector<float> hl(Rl);
-			NGP_HIP(hipMemcpyAsync(hl.data(), loss, (size_t)Rl * 4, hipMemcpyDeviceToHost, s));
-			NGP_HIP(hipStreamSynchronize(s));
-			for (float v : hl) loss_sum += v;
-		} else {
-			wait_published(t->host_ctr, t->publish_seq, s);
-		}
-		for (int k = 0; k < 4; ++k) h[k] = t->host_ctr[k];
-		if (dp) {
-			const uint32_t lb = t->host_ctr[5];
-			float lv;
-			memcpy(&lv, &lb, 4);
-			loss_sum = lv;
-			t->measured_before_compaction_local = t->host_ctr[6];
-		} else {
-			t->measured_before_compaction_local = h[1];
-		}
-		float loss_scalar = 0.f;
-		t->measured_batch_size = 0;
-		t->measured_before_compaction = 0;
-		if (h[1] != 0 && h[2] != 0) {
-			t->measured_before_compaction = h[1];
-			t->measured_batch_size = h[2];
-			if (get_loss) t->loss_scalar = loss_scalar = (float)(loss_sum * (double)t->measured_batch_size / (double)B);
-			uint32_t r = (uint32_t)((float)t->rays_per_batch * (float)B / (float)t->measured_batch_size);
-			t->rays_per_batch = std::min(next_multiple(r, 256), 1u << 18);
-		}
+		const float loss_scalar = step_read_counters(t, s, c);
 		error_map_step_done(t, s);
-		// next step's sampler, concurrent with this step's training pass (no density-grid update due first)
-		if (can_pipeline && t->measured_batch_size > 0 && !density_grid_update_due(t->training_step)) {
-			const SamplePlan np = sample_plan(t);
-			// early(): the sampler writes the other sample set, which the step before last read (complete: this step's
-			// counters are published), so it waits on nothing
-			if (!t->early()) {
-				if (nerf_waitval() == 2) NGP_HIP(hipStreamWaitValue32(t->sample_stream, t->sig_free, t->seq_free, hipStreamWaitValueGte, 0xFFFFFFFFu));
-				else NGP_HIP(hipStreamWaitEvent(t->sample_stream, t->ev_free, 0));
-			}
-			launch_sampler(t, np, t->sample_stream);
-			if (nerf_waitval()) {
-				t->ensure_signals();
-				NGP_HIP(hipStreamWriteValue32(t->sample_stream, t->sig_samp, ++t->seq_samp, 0));
-			} else {
-				NGP_HIP(hipEventRecord(t->ev_samp, t->sample_stream));
-			}
-			t->pre_R = np.R;
-			t->pre_max_inference = np.max_inference;
-			t->prelaunched = true;
-		}
-		// next step's density-grid update: its samples now, under this step's training pass (one GPU)
-		static const bool pregen_on = !getenv("NGP_GRID_PREGEN") || atoi(getenv("NGP_GRID_PREGEN")) != 0;  // A/B knob
-		if (pregen_on && can_pipeline && !dp && t->training_step > 0 && density_grid_update_due(t->training_step)) {
-			if (!t->ev_gen) NGP_HIP(hipEventCreateWithFlags(&t->ev_gen, hipEventDisableTiming));
-			grid_update_counts(t, t->training_step, &t->pregen_nu, &t->pregen_nn);
-			t->pregen_rng = t->grid_rng;
-			grid_update_samples(t, t->sample_stream, t->pregen_nu, t->pregen_nn);
-			NGP_HIP(hipEventRecord(t->ev_gen, t->sample_stream));
-			t->grid_pregen = true;
-		}
+		step_prelaunch_sampler(t, c);
+		step_pregenerate_grid_samples(t, c);
 		if (st) {
 			st->step = t->training_step;
 			st->rays_per_batch = t->rays_per_batch;

@@ -3,7 +3,8 @@ the default sorts the update's samples by 8192-cell bin before the density evalu
 LDS (every cell written, no memset); NGP_SPLAT_SORT=0 is the reference's form (memset, density in generated order,
 scattered atomicMax). Max is order-independent and each sample's density does not depend on its neighbours, so 300
 training steps (every-step updates, then the step-256 switch to every 16th with the 0.01 threshold) must leave the
-density grid, bitfield, mean and parameters bit-identical. Each mode runs in its own process (the knob is read once)."""
+density grid, bitfield, mean and parameters bit-identical. Each mode runs in its own process (the knob is read when the NeRF
+trainer is created)."""
 import os
 import subprocess
 import sys
