@@ -483,6 +483,55 @@ int ngp_sdf_render(ngp_sdf_renderer* r, ngp_model* model, ngp_sdf_mesh* ground_t
 int ngp_sdf_iou_accumulate(void* stream, uint32_t n, const float* distances_ref, const float* distances_model,
                            float scale_existing, uint32_t* counters /* device [8] */);
 
+/* ---- mesh extraction (src/marching_cubes.cu; Testbed::marching_cubes, testbed.h:472) ---------------------- */
+/* Marching cubes over the model sampled on a regular grid. Unlike marching_cubes_gpu (marching_cubes.cu:776-804),
+ * which appends through global atomic counters, the output order is a function of the grid alone: two runs give
+ * byte-identical buffers. Grid arguments: res[3] points per axis (each >= 2, fewer than 2^32 in all), the box
+ * aabb_min / aabb_max (host float[3], positive sides); grid point (x, y, z) lies at aabb_min + (x, y, z) *
+ * (aabb_max - aabb_min) / (res - 1), x fastest in memory. aabb_to_local (nullable host float[9], row-major 3x3) is
+ * applied to positions as its transpose (gen_vertices, :283); NULL skips the multiply. Null and invalid arguments
+ * return NGP_INVALID before any HIP call. */
+typedef struct ngp_mesh ngp_mesh;
+enum { NGP_MC_NERF = 0, NGP_MC_SDF = 1, NGP_MC_RAW = 2 };
+/* The case table (engine extension; gen_faces embeds its own, marching_cubes.cu:363-684), generated on the host at
+ * first use: triangle_table [256][16] edge ids, three per triangle, -1 terminated, at most 5 triangles, wound
+ * counter-clockwise seen from the outside (f <= thresh); edge_masks [256]: bit e set when edge e changes sign. Bit c of
+ * a case: corner c inside (f > thresh); corners 0-3 counter-clockwise on z = 0, 4-7 above them; edges 0-3 bottom, 4-7
+ * top, 8-11 vertical (:225-261). Host only. */
+int ngp_mc_tables(int8_t* triangle_table, uint16_t* edge_masks);
+/* get_marching_cubes_res (marching_cubes.cu:42-49): res_1d points along the box's longest side, every axis rounded up
+ * to a multiple of 16. res_out: host uint32[3]. Host only. */
+int ngp_marching_cubes_res(uint32_t res_1d, const float* aabb_min, const float* aabb_max, uint32_t* res_out);
+/* Testbed::get_density_on_grid (testbed.h:472 marching_cubes' first step): density_out (device float [res.z][res.y][res.x])
+ * = the model at every grid point, evaluated in batches of `batch` points. kind NGP_MC_NERF: a NerfNetwork's
+ * network_to_density(float(density row 0), density_activation) at positions warped into warp_aabb (the training box;
+ * NULL: positions as they are) like the renderer's inputs; NGP_MC_SDF: minus a 3-input network's output row 0, so that
+ * inside is f > 0; NGP_MC_RAW: float(row 0) of ngp_density (NerfNetwork) or ngp_inference (3 inputs). */
+int ngp_density_on_grid(ngp_model* model, void* stream, int kind, const uint32_t* res, const float* aabb_min, const float* aabb_max,
+                        const float* aabb_to_local, const float* warp_aabb_min, const float* warp_aabb_max,
+                        uint32_t density_activation, uint32_t batch, int use_inference_params, float* density_out);
+/* marching_cubes_gpu (marching_cubes.cu:776-804) and compute_mesh_1ring's normals (:313-348, 702-708): density (device,
+ * as ngp_density_on_grid writes it), inside where density > thresh. The mesh holds exact counts (no padding to 128):
+ * vertices (coord + dt) * scale + offset with dt = (thresh - f0) / (f1 - f0) (:282-283), area-weighted outward vertex
+ * normals (not normalised) and int32 triangles. More than 2^29 vertices fail. */
+int ngp_marching_cubes(void* stream, const float* density, const uint32_t* res, const float* aabb_min, const float* aabb_max,
+                       const float* aabb_to_local, float thresh, ngp_mesh** out);
+/* Testbed::compute_mesh_vertex_colors (testbed.h:472 marching_cubes' last step): NGP_MC_NERF: the NerfNetwork at the
+ * vertices (warped into warp_aabb, nullable) seen along minus the normal, network_to_rgb(rgb_activation), then
+ * linear_to_srgb; NGP_MC_SDF: 0.5 n + 0.5 of the normalised normal (model unused). */
+int ngp_mesh_vertex_colors(ngp_mesh* mesh, ngp_model* model, void* stream, int kind, const float* warp_aabb_min,
+                           const float* warp_aabb_max, uint32_t rgb_activation, int use_inference_params);
+int ngp_mesh_counts(const ngp_mesh* mesh, uint32_t* n_verts, uint32_t* n_tris);
+/* copies to host arrays (each nullable): float [n_verts x 3] vertices, normals, colours; int32 [n_tris x 3] */
+int ngp_mesh_read(const ngp_mesh* mesh, void* stream, float* verts_host, float* normals_host, float* colors_host, int32_t* faces_host);
+/* save_mesh (marching_cubes.cu:806-956) without the UV unwrap, from host arrays (normals / colours nullable): vertices
+ * as (p - offset) / scale (offset NULL = 0), non-finite positions and colours replaced by 0 and normals by +y, normals
+ * normalised, colours clamped. A path ending in .ply (any case) gives ASCII PLY, anything else OBJ; faces keep the
+ * outward winding of the triangle array. Host only. */
+int ngp_mesh_save(const char* path, uint32_t n_verts, const float* verts_host, const float* normals_host, const float* colors_host,
+                  uint32_t n_tris, const int32_t* faces_host, float scale, const float* offset);
+void ngp_mesh_destroy(ngp_mesh* mesh);
+
 /* Data-parallel NeRF training (no counterpart in the reference, which trains on one GPU: SURVEY F7,
  * §8e). `allreduce` reduces a device buffer in place across the ranks, ordered on `stream` (the
  * caller's RCCL/torch.distributed binding); it is called for the fp16 gradient buffer (sum, before

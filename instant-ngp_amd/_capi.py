@@ -168,6 +168,15 @@ SIGNATURES = {
     "ngp_sdf_renderer_destroy": (None, [P]),
     "ngp_sdf_render": (i32, [P, P, P, C.POINTER(SdfRenderConfig), P, C.POINTER(NerfImage), i32, u32, u32, P, i32, P, P]),
     "ngp_sdf_iou_accumulate": (i32, [P, u32, P, P, f32, P]),
+    "ngp_mc_tables": (i32, [P, P]),
+    "ngp_marching_cubes_res": (i32, [u32, P, P, P]),
+    "ngp_density_on_grid": (i32, [P, P, i32, P, P, P, P, P, P, u32, u32, i32, P]),
+    "ngp_marching_cubes": (i32, [P, P, P, P, P, P, f32, C.POINTER(P)]),
+    "ngp_mesh_vertex_colors": (i32, [P, P, P, i32, P, P, u32, i32]),
+    "ngp_mesh_counts": (i32, [P, C.POINTER(u32), C.POINTER(u32)]),
+    "ngp_mesh_read": (i32, [P, P, P, P, P, P]),
+    "ngp_mesh_save": (i32, [C.c_char_p, u32, P, P, P, u32, P, f32, P]),
+    "ngp_mesh_destroy": (None, [P]),
     "ngp_nerf_default_config": (i32, [f32, C.POINTER(NerfConfig)]),
     "ngp_nerf_dataset_create": (i32, [u32, C.POINTER(NerfImage), C.POINTER(P), C.POINTER(P)]),
     "ngp_nerf_dataset_destroy": (None, [P]),

@@ -68,8 +68,13 @@ void load_training_data(Testbed& tb, const std::string& path) {
 		}
 		const float aabb_scale = d.attr("aabb_scale").cast<float>();
 		const float scale = py::hasattr(d, "scale") ? d.attr("scale").cast<float>() : 1.0f;
+		float offset[3] = {0.5f, 0.5f, 0.5f};
+		if (py::hasattr(d, "offset")) {
+			const std::vector<float> o = d.attr("offset").cast<std::vector<float>>();
+			if (o.size() == 3) std::copy(o.begin(), o.end(), offset);
+		}
 		py::gil_scoped_release nogil;
-		tb.load_nerf(meta, ptrs, aabb_scale, scale);
+		tb.load_nerf(meta, ptrs, aabb_scale, scale, offset);
 		break;
 	}
 	case ETestbedMode::Image: {
@@ -108,6 +113,26 @@ void load_file(Testbed& tb, const std::string& path) {
 	const bool had_data = tb.training_data_available();
 	load_training_data(tb, path);
 	if (!had_data) tb.m_train = true;  // testbed.cu:363-371
+}
+
+// the (min, max) pair of a box argument; None: the model's own box
+struct BoxArg {
+	bool given = false;
+	float lo[3], hi[3];
+	explicit BoxArg(const py::object& aabb) {
+		if (aabb.is_none()) return;
+		const auto pair = aabb.cast<std::pair<std::vector<float>, std::vector<float>>>();
+		if (pair.first.size() != 3 || pair.second.size() != 3) throw std::runtime_error("aabb: a (min, max) pair of 3 values each");
+		std::copy(pair.first.begin(), pair.first.end(), lo);
+		std::copy(pair.second.begin(), pair.second.end(), hi);
+		given = true;
+	}
+};
+std::vector<uint32_t> resolution_arg(const std::vector<int>& res) {
+	if (res.size() != 3) throw std::runtime_error("resolution: 3 values");
+	for (int r : res)
+		if (r < 0) throw std::runtime_error("resolution: negative value");
+	return std::vector<uint32_t>(res.begin(), res.end());
 }
 
 // views of the Testbed's nested members (Testbed::Nerf, ::Sdf, ::Image and their ::Training)
@@ -235,6 +260,44 @@ PYBIND11_MODULE(pyngp, m) {
 		.def("calculate_iou", &Testbed::calculate_iou, py::call_guard<py::gil_scoped_release>(),
 		     "Calculate the intersection over union error value", py::arg("n_samples") = 128 * 1024 * 1024,
 		     py::arg("scale_existing_results_factor") = 0.0f, py::arg("blocking") = true, py::arg("force_use_octree") = true)
+		.def("compute_marching_cubes_mesh",
+		     [](Testbed& t, const std::vector<int>& resolution, py::object aabb, float thresh) {
+			     const std::vector<uint32_t> res = resolution_arg(resolution);
+			     const BoxArg box(aabb);
+			     Testbed::Mesh mesh;
+			     {
+				     py::gil_scoped_release nogil;
+				     mesh = t.compute_marching_cubes_mesh(res.data(), box.given ? box.lo : nullptr, box.given ? box.hi : nullptr, thresh);
+			     }
+			     const py::ssize_t nv = (py::ssize_t)(mesh.V.size() / 3), nt = (py::ssize_t)(mesh.F.size() / 3);
+			     py::array_t<float> V({nv, (py::ssize_t)3}), N({nv, (py::ssize_t)3}), C({nv, (py::ssize_t)3});
+			     py::array_t<int32_t> F({nt, (py::ssize_t)3});
+			     if (nv) {
+				     std::memcpy(V.mutable_data(), mesh.V.data(), mesh.V.size() * sizeof(float));
+				     std::memcpy(N.mutable_data(), mesh.N.data(), mesh.N.size() * sizeof(float));
+				     std::memcpy(C.mutable_data(), mesh.C.data(), mesh.C.size() * sizeof(float));
+			     }
+			     if (nt) std::memcpy(F.mutable_data(), mesh.F.data(), mesh.F.size() * sizeof(int32_t));
+			     py::dict d;
+			     d["V"] = V; d["N"] = N; d["C"] = C; d["F"] = F;
+			     return d;
+		     },
+		     py::arg("resolution") = std::vector<int>{128, 128, 128}, py::arg("aabb") = py::none(), py::arg("thresh") = 2.5f,
+		     "Compute a marching cubes mesh from the current SDF or NeRF model. Returns a python dict with numpy arrays V "
+		     "(vertices), N (vertex normals), C (vertex colors), and F (triangular faces).")
+		.def("compute_and_save_marching_cubes_mesh",
+		     [](Testbed& t, const std::string& filename, const std::vector<int>& resolution, py::object aabb, float thresh,
+		        bool generate_uvs_for_obj_file) {
+			     const std::vector<uint32_t> res = resolution_arg(resolution);
+			     const BoxArg box(aabb);
+			     py::gil_scoped_release nogil;
+			     t.compute_and_save_marching_cubes_mesh(filename, res.data(), box.given ? box.lo : nullptr, box.given ? box.hi : nullptr, thresh,
+			                                            generate_uvs_for_obj_file);
+		     },
+		     py::arg("filename"), py::arg("resolution") = std::vector<int>{128, 128, 128}, py::arg("aabb") = py::none(),
+		     py::arg("thresh") = 2.5f, py::arg("generate_uvs_for_obj_file") = false,
+		     "Compute a marching cubes mesh from the current SDF or NeRF model and save it to an .obj or .ply file. "
+		     "UV generation is not supported.")
 		.def_property_readonly("aabb", [](const Testbed& t) {  // m_aabb of an SDF testbed: (min, max)
 			return py::make_tuple(std::vector<float>(t.sdf_aabb_min(), t.sdf_aabb_min() + 3),
 			                      std::vector<float>(t.sdf_aabb_max(), t.sdf_aabb_max() + 3));

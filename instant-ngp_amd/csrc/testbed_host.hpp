@@ -13,6 +13,7 @@
 //   save_snapshot / load_snapshot                                        testbed.cu:4873-5057
 //   set_camera_to_training_view / render_to_cpu                          testbed.cu:848-856, python_api.cu:418-427
 //   render_sdf (through ngp_sdf_render) / calculate_iou                  testbed_sdf.cu:883-1063, 1329-1364
+//   compute_marching_cubes_mesh / compute_and_save_marching_cubes_mesh   testbed.h:472, python_api.cu:101-125
 // What lives elsewhere: decoding image files (JPEG/PNG/EXR) is the binding's job (python_api.cpp hands the
 // decoded pixels to load_nerf / load_image), as the reference delegates it to stb_image / tinyexr.
 #pragma once
@@ -248,7 +249,7 @@ public:
 	// Testbed::load_nerf + load_nerf_post (testbed_nerf.cu:3093-3109): decoded images (RGBA8 sRGB) with their
 	// metadata after nerf_matrix_to_ngp, and the dataset's aabb_scale
 	void load_nerf(const std::vector<ngp_nerf_image>& images, const std::vector<const void*>& rgba8, float aabb_scale,
-	               float dataset_scale = 1.0f) {
+	               float dataset_scale = 1.0f, const float* dataset_offset = nullptr) {
 		set_mode(ETestbedMode::Nerf);
 		if (images.empty() || images.size() != rgba8.size()) throw std::runtime_error("load_nerf: one RGBA8 buffer per image");
 		free_network();
@@ -257,6 +258,7 @@ public:
 		m_nerf_images = images;
 		m_aabb_scale = aabb_scale;
 		m_dataset_scale = dataset_scale;  // NerfDataset::scale (nerf_loader.cu:388): Depth renders in its units
+		for (int d = 0; d < 3; ++d) m_dataset_offset[d] = dataset_offset ? dataset_offset[d] : 0.5f;  // NerfDataset::offset
 		check(ngp_nerf_default_config(aabb_scale, &m_nerf_cfg), "ngp_nerf_default_config");
 		m_training_data_available = true;
 		set_camera_to_training_view(0);
@@ -641,6 +643,66 @@ public:
 		}
 		return (double)host[4] / (double)host[5];
 	}
+	// ---- mesh extraction (Testbed::marching_cubes, testbed.h:472; python_api.cu:101-125) -----------------------------
+	struct Mesh {
+		std::vector<float> V, N, C;  // [n x 3] each; N normalised
+		std::vector<int32_t> F;      // [m x 3], counter-clockwise seen from outside
+	};
+	// The model sampled on res3d points over the box (null: the model's own), marching cubes at thresh (SDF: 0, as
+	// testbed_sdf.cu:1146 sets it), vertex normals and colours, with the inference (EMA) parameters as render() uses.
+	Mesh compute_marching_cubes_mesh(const uint32_t* res3d, const float* aabb_min, const float* aabb_max, float thresh) {
+		if (m_testbed_mode != ETestbedMode::Nerf && m_testbed_mode != ETestbedMode::Sdf)
+			throw std::runtime_error("compute_marching_cubes_mesh: only NeRF and SDF models have a mesh");
+		if (!m_model || !m_trainer) throw std::runtime_error("compute_marching_cubes_mesh: no network (train or load a snapshot first)");
+		const bool nerf = m_testbed_mode == ETestbedMode::Nerf;
+		if ((aabb_min == nullptr) != (aabb_max == nullptr)) throw std::runtime_error("compute_marching_cubes_mesh: half a box");
+		if (!aabb_min) {
+			aabb_min = nerf ? m_nerf_cfg.aabb_min : m_sdf_aabb_min;
+			aabb_max = nerf ? m_nerf_cfg.aabb_max : m_sdf_aabb_max;
+		}
+		if (!nerf) thresh = 0.f;
+		uint64_t n = 1;
+		for (int d = 0; d < 3; ++d) {
+			if (res3d[d] < 2) throw std::runtime_error("compute_marching_cubes_mesh: every resolution must be at least 2");
+			n *= res3d[d];
+			if (n >= (1ull << 32)) throw std::runtime_error("compute_marching_cubes_mesh: grids of 2^32 points or more are not supported");
+		}
+		float* density = m_mc_density.get<float>(n);
+		check(ngp_density_on_grid(m_model, nullptr, nerf ? NGP_MC_NERF : NGP_MC_SDF, res3d, aabb_min, aabb_max, nullptr,
+		                          nerf ? m_nerf_cfg.aabb_min : nullptr, nerf ? m_nerf_cfg.aabb_max : nullptr,
+		                          nerf ? m_nerf_cfg.density_activation : 0u, 1u << 20, 1, density),
+		      "ngp_density_on_grid");
+		ngp_mesh* mesh = nullptr;
+		check(ngp_marching_cubes(nullptr, density, res3d, aabb_min, aabb_max, nullptr, thresh, &mesh), "ngp_marching_cubes");
+		struct Guard { ngp_mesh* m; ~Guard() { ngp_mesh_destroy(m); } } guard{mesh};
+		check(ngp_mesh_vertex_colors(mesh, m_model, nullptr, nerf ? NGP_MC_NERF : NGP_MC_SDF, nerf ? m_nerf_cfg.aabb_min : nullptr,
+		                             nerf ? m_nerf_cfg.aabb_max : nullptr, nerf ? m_nerf_cfg.rgb_activation : 0u, 1),
+		      "ngp_mesh_vertex_colors");
+		uint32_t nv = 0, nt = 0;
+		check(ngp_mesh_counts(mesh, &nv, &nt), "ngp_mesh_counts");
+		Mesh out;
+		out.V.resize((size_t)nv * 3); out.N.resize((size_t)nv * 3); out.C.resize((size_t)nv * 3); out.F.resize((size_t)nt * 3);
+		check(ngp_mesh_read(mesh, nullptr, out.V.data(), out.N.data(), out.C.data(), out.F.data()), "ngp_mesh_read");
+		for (size_t i = 0; i < nv; ++i) {  // python_api.cu:119-122
+			float* v = &out.N[i * 3];
+			const float len = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+			if (len > 0.f) for (int d = 0; d < 3; ++d) v[d] /= len;
+		}
+		return out;
+	}
+	// Testbed::compute_and_save_marching_cubes_mesh: a NeRF's vertices go back to the dataset's units through its scale
+	// and offset (save_mesh's nerf_scale / nerf_offset, marching_cubes.cu:895, 912). The UV unwrap is not built.
+	void compute_and_save_marching_cubes_mesh(const std::string& path, const uint32_t* res3d, const float* aabb_min, const float* aabb_max,
+	                                          float thresh, bool unwrap_it) {
+		if (unwrap_it) throw std::runtime_error("compute_and_save_marching_cubes_mesh: generate_uvs_for_obj_file is not supported (no UV unwrap)");
+		const Mesh m = compute_marching_cubes_mesh(res3d, aabb_min, aabb_max, thresh);
+		const bool nerf = m_testbed_mode == ETestbedMode::Nerf;
+		const float zero[3] = {0.f, 0.f, 0.f};
+		check(ngp_mesh_save(path.c_str(), (uint32_t)(m.V.size() / 3), m.V.data(), m.N.data(), m.C.data(), (uint32_t)(m.F.size() / 3),
+		                    m.F.data(), nerf ? m_dataset_scale : 1.0f, nerf ? m_dataset_offset : zero),
+		      "ngp_mesh_save");
+	}
+
 	// the SDF render configuration in use: Testbed::Sdf's knobs with the aabb, floor, sun and up of the Testbed
 	ngp_sdf_render_config sdf_render_config() const {
 		ngp_sdf_render_config cfg = m_sdf_render_cfg;
@@ -776,6 +838,7 @@ private:
 	std::vector<ngp_nerf_image> m_nerf_images;
 	float m_aabb_scale = 1.f;
 	float m_dataset_scale = 1.f;
+	float m_dataset_offset[3] = {0.5f, 0.5f, 0.5f};
 	uint32_t m_lens_mode = 0;
 	float m_lens_params[4] = {0, 0, 0, 0};
 	// image
@@ -788,7 +851,7 @@ private:
 	DeviceBuffer m_iou_counters, m_iou_pos, m_iou_ref, m_iou_model;  // the training batch buffers stay as they are
 	float m_sdf_aabb_min[3] = {0, 0, 0}, m_sdf_aabb_max[3] = {1, 1, 1};
 	DeviceBuffer m_sdf_pos, m_sdf_dist, m_sdf_pos_s, m_sdf_dist_s;
-	DeviceBuffer m_loss_dev, m_render_buf, m_render_out;
+	DeviceBuffer m_loss_dev, m_render_buf, m_render_out, m_mc_density;
 };
 
 }  // namespace ngp_host
