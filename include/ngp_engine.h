@@ -633,6 +633,92 @@ int ngp_trainer_set_data_parallel(ngp_trainer* t, uint32_t rank, uint32_t world,
  * whole optimizer state again. A no-op unless a sharded step left them partial. */
 int ngp_trainer_gather_shards(ngp_trainer* t, void* stream);
 
+/* ---- NeRF camera pose refinement (nerf.training.optimize_extrinsics) ------------------------------------------ */
+/* ngp_trainer_train_step that also writes dL/dinput (fp32 AoS [n x dL_dinput_stride]: the position rows through the
+ * grid and, for a NerfNetwork, the direction rows through SH, as ngp_backward does; NerfNetwork::backward's dL_dinput,
+ * nerf_network.h). The gradient is taken with respect to the weights the forward used: it runs before the grid's
+ * fused optimizer update (ngp_trainer_fused_update_active). dL_dinput must not alias input. */
+int ngp_trainer_train_step_input_gradient(ngp_trainer* t, void* stream, uint32_t n, const float* input, uint32_t input_stride,
+                                          const void* dL_doutput, uint32_t dL_stride, float loss_scale, float* dL_dinput,
+                                          uint32_t dL_dinput_stride);
+/* compute_cam_gradient_train_nerf (testbed_nerf.cu:2014-2123), extrinsics only (uv_pdf 1; no distortion map, no focal
+ * length). Inputs: the compacted batch after the loss pass (numsteps [R x 2] = {n, base}, coords [B x 7]), its input
+ * gradient (fp32 rows of gradient_stride >= 7 floats: 0..2 position, 4..6 direction), the kept rays' ids (ascending)
+ * and unnormalised rays [R x 6], the device ray counter and the training box of cfg. Per kept ray with n > 0 the
+ * samples' position gradients (divided by the box's sides) sum to the origin gradient, and position gradient x
+ * distance to the origin + 0.5 x direction gradient to the direction gradient gd; pos_gradient[img] += origin gradient,
+ * rot_gradient[img] += cross(normalize(d), gd), both device float [n_images x 3], accumulated onto their content.
+ * Unlike the reference, which adds every ray with float atomics, each ray's six floats are stored and every image's
+ * rays (one contiguous run of the kept rays) are summed in ray order: two calls on the same inputs give the same
+ * bytes. n_rays_total * n_images must stay below 2^32. Null and invalid arguments return NGP_INVALID before any HIP
+ * call. */
+int ngp_nerf_camera_gradients(const ngp_nerf_config* cfg, void* stream, uint32_t n_rays_total, uint32_t n_images,
+                              const uint32_t* ray_counter, const uint32_t* ray_indices, const float* rays,
+                              const uint32_t* numsteps, const float* coords, const float* coords_gradient,
+                              uint32_t gradient_stride, float* pos_gradient, float* rot_gradient);
+/* The per-camera optimisers of Testbed::Nerf::Training (cam_pos_offset: AdamOptimizer<vec3>, cam_rot_offset:
+ * RotationAdamOptimizer; adam_optimizer.h:128-309): n_images pairs of Adam states, beta1 0.9, beta2 0.99, epsilon 1e-8,
+ * initial learning rate 1e-4 (testbed_nerf.cu:3037-3038). Host only: no GPU call. The rotation variable is updated as
+ * rotvec(rotmat(-step) * rotmat(variable)) (common_device.cuh:698-722) with the angle taken as 2 atan2(|xyz|, w) of
+ * the product's quaternion, not 2 acos(w), which loses the 1e-4 rad rotations this optimiser makes. */
+typedef struct ngp_pose_optimizer ngp_pose_optimizer;
+typedef struct {   /* the members VarAdamOptimizer::to_json writes (adam_optimizer.h:174-183) */
+	uint32_t iter;
+	float first_moment[3], second_moment[3], variable[3];
+	float learning_rate, epsilon, beta1, beta2;
+} ngp_adam_state;
+int ngp_pose_optimizer_create(uint32_t n_images, ngp_pose_optimizer** out);
+void ngp_pose_optimizer_destroy(ngp_pose_optimizer* o);
+uint32_t ngp_pose_optimizer_n_images(const ngp_pose_optimizer* o);
+/* reset_state of every camera / of one (testbed_nerf.cu:2921-2933, 2911-2912): moments, variable and iter to 0 */
+int ngp_pose_optimizer_reset(ngp_pose_optimizer* o);
+int ngp_pose_optimizer_reset_one(ngp_pose_optimizer* o, uint32_t i);
+/* One update of every camera (testbed_nerf.cu:3784-3805) from the accumulated gradients (host float [n_images x 3]
+ * each): gradient * n_images / 128 / n_steps_between + l2_reg * variable, learning rate max(extrinsic_lr *
+ * 0.33^(iter / 128), network_lr / 1000) with the integer quotient of the camera's iter before the step. */
+int ngp_pose_optimizer_step(ngp_pose_optimizer* o, const float* pos_grad, const float* rot_grad, uint32_t n_steps_between,
+                            float extrinsic_lr, float l2_reg, float network_lr);
+int ngp_pose_optimizer_get(const ngp_pose_optimizer* o, uint32_t i, ngp_adam_state* pos, ngp_adam_state* rot);  /* each nullable */
+int ngp_pose_optimizer_set_state(ngp_pose_optimizer* o, uint32_t i, const ngp_adam_state* pos, const ngp_adam_state* rot);
+/* rotvec(rotmat(a) * rotmat(b)): the composition the rotation optimiser applies. float[3] each, host only. */
+int ngp_pose_compose_rotation(const float* a, const float* b, float* out);
+/* Training::update_transforms for one image (testbed_nerf.cu:2998-3019): xform (camera-to-world mat4x3, column-major
+ * float[12]) with its rotation divided by cbrt(det) when |det - 1| > 0.01, then rotmat(rot_offset) * rotation and
+ * translation + pos_offset. Zero offsets return a proper rotation's xform bit for bit. Host only. */
+int ngp_pose_apply(const float* xform, const float* rot_offset, const float* pos_offset, float* out);
+/* Testbed::Nerf::Training's camera optimisation knobs (testbed.h:716-785; python_api.cu:618-653) and their defaults. */
+typedef struct {
+	uint32_t optimize_extrinsics;           /* 0 */
+	uint32_t n_steps_between_cam_updates;   /* 16 */
+	float extrinsic_l2_reg;                 /* 1e-4 */
+	float extrinsic_learning_rate;          /* 1e-3 */
+} ngp_nerf_camera_training;
+/* With optimize_extrinsics the training step also takes the compacted batch's input gradient (with respect to the
+ * forward's weights), sums it per image (ngp_nerf_camera_gradients; testbed_nerf.cu:3641-3644, 4071-4125) and, every
+ * n_steps_between_cam_updates steps, steps the per-camera optimisers and rebuilds the cameras the sampler traces
+ * (:3754-3809, update_transforms :2980-3024); the next step's rays come from the new poses. Off (default): the step
+ * issues exactly the launches it would without this call. Single GPU: enabling it on a trainer with an exchange hook,
+ * or setting a hook while it is on, fails (the per-image sums would need their own all-reduce). */
+int ngp_nerf_trainer_set_camera_training(ngp_nerf_trainer* t, const ngp_nerf_camera_training* c);
+int ngp_nerf_trainer_get_camera_training(const ngp_nerf_trainer* t, ngp_nerf_camera_training* out);
+/* Training::transforms[i].start (get_camera_extrinsics, :2973-2978, before ngp_matrix_to_nerf): image i's refined
+ * camera-to-world transform in NGP space, float[12] column-major; the dataset's own, bit for bit, while the offsets
+ * are zero. */
+int ngp_nerf_trainer_camera_extrinsics(const ngp_nerf_trainer* t, uint32_t i, float* out);
+/* set_camera_extrinsics (:2896-2919) with an NGP-space transform: replaces image i's transform in this trainer (the
+ * dataset is not modified) and resets that image's optimiser state. Discards a prelaunched sampler. */
+int ngp_nerf_trainer_set_camera_extrinsics(ngp_nerf_trainer* t, uint32_t i, const float* xform);
+/* reset_camera_extrinsics (:2921-2933): every camera's optimiser state to zero, cameras rebuilt. */
+int ngp_nerf_trainer_reset_camera_extrinsics(ngp_nerf_trainer* t);
+/* Engine extension (inspection): the last step's sampler call on a single-GPU trainer: its rng, ray count and sample
+ * budget (the arguments ngp_nerf_generate_training_samples would take, with the trainer's bitfield) and the device
+ * buffers it wrote: ray_indices [n_rays], rays [n_rays x 6], counters [>= 2]. They hold that step's rays until a
+ * later sampler writes them: with pipelining on, that may be as soon as the step returns. Outputs nullable. */
+int ngp_nerf_trainer_last_samples(const ngp_nerf_trainer* t, ngp_rng* rng, uint32_t* n_rays, uint32_t* max_samples,
+                                  const uint32_t** ray_indices, const float** rays, const uint32_t** counters);
+/* cam_pos_offset[i] / cam_rot_offset[i] (each nullable) */
+int ngp_nerf_trainer_pose_optimizer_state(const ngp_nerf_trainer* t, uint32_t i, ngp_adam_state* pos, ngp_adam_state* rot);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -70,6 +70,19 @@ class NerfErrorMapInfo(C.Structure):
                 ("n_steps_between_updates", C.c_uint32), ("size", C.c_uint64)]
 
 
+class AdamState(C.Structure):
+    """ngp_adam_state: one per-camera Adam state with its hyperparameters (adam_optimizer.h:174-183)."""
+    _fields_ = [("iter", C.c_uint32), ("first_moment", C.c_float * 3), ("second_moment", C.c_float * 3),
+                ("variable", C.c_float * 3), ("learning_rate", C.c_float), ("epsilon", C.c_float), ("beta1", C.c_float),
+                ("beta2", C.c_float)]
+
+
+class NerfCameraTraining(C.Structure):
+    """ngp_nerf_camera_training: the camera optimisation knobs of Testbed::Nerf::Training."""
+    _fields_ = [("optimize_extrinsics", C.c_uint32), ("n_steps_between_cam_updates", C.c_uint32),
+                ("extrinsic_l2_reg", C.c_float), ("extrinsic_learning_rate", C.c_float)]
+
+
 class SdfRenderConfig(C.Structure):
     """ngp_sdf_render_config: Testbed::Sdf render knobs, sun / up / floor and BRDFParams (testbed.h:798-835, sdf.h:62-72)."""
     _fields_ = [
@@ -226,6 +239,26 @@ SIGNATURES = {
     "ngp_nerf_renderer_destroy": (None, [P]),
     "ngp_nerf_renderer_set_mode": (i32, [P, i32]),
     "ngp_nerf_render": (i32, [P, P, C.POINTER(NerfConfig), P, C.POINTER(NerfImage), P, u32, u32, f32, P, i32, P]),
+    "ngp_trainer_train_step_input_gradient": (i32, [P, P, u32, P, u32, P, u32, f32, P, u32]),
+    "ngp_nerf_camera_gradients": (i32, [C.POINTER(NerfConfig), P, u32, u32, P, P, P, P, P, P, u32, P, P]),
+    "ngp_pose_optimizer_create": (i32, [u32, C.POINTER(P)]),
+    "ngp_pose_optimizer_destroy": (None, [P]),
+    "ngp_pose_optimizer_n_images": (u32, [P]),
+    "ngp_pose_optimizer_reset": (i32, [P]),
+    "ngp_pose_optimizer_reset_one": (i32, [P, u32]),
+    "ngp_pose_optimizer_step": (i32, [P, P, P, u32, f32, f32, f32]),
+    "ngp_pose_optimizer_get": (i32, [P, u32, C.POINTER(AdamState), C.POINTER(AdamState)]),
+    "ngp_pose_optimizer_set_state": (i32, [P, u32, C.POINTER(AdamState), C.POINTER(AdamState)]),
+    "ngp_pose_compose_rotation": (i32, [P, P, P]),
+    "ngp_pose_apply": (i32, [P, P, P, P]),
+    "ngp_nerf_trainer_set_camera_training": (i32, [P, C.POINTER(NerfCameraTraining)]),
+    "ngp_nerf_trainer_get_camera_training": (i32, [P, C.POINTER(NerfCameraTraining)]),
+    "ngp_nerf_trainer_camera_extrinsics": (i32, [P, u32, P]),
+    "ngp_nerf_trainer_set_camera_extrinsics": (i32, [P, u32, P]),
+    "ngp_nerf_trainer_reset_camera_extrinsics": (i32, [P]),
+    "ngp_nerf_trainer_last_samples": (i32, [P, C.POINTER(Rng), C.POINTER(u32), C.POINTER(u32), C.POINTER(P), C.POINTER(P),
+                                            C.POINTER(P)]),
+    "ngp_nerf_trainer_pose_optimizer_state": (i32, [P, u32, C.POINTER(AdamState), C.POINTER(AdamState)]),
 }
 
 

@@ -408,9 +408,12 @@ struct ngp_model {
 		const MlpMode mode = ex.density_only ? MLP_DENSITY_TRAIN : MLP_TRAIN;
 		run_mlp(s, mode, n, in, stride, encbuf, out, out_stride, AoS, (const f16*)dL, dL_stride, dL_denc, slab, ex.inference, &ex,
 		        dsh);
-		// dL/dinput through the grid (position rows) and the SH encoding (direction rows, NerfNetwork). Run
-		// last: dL_dinput may alias the input (the reference passes positions_matrix for both,
-		// testbed_nerf.cu:2616), which the grid backward still reads
+		// dL/dinput through the grid (position rows) and the SH encoding (direction rows, NerfNetwork). Where
+		// dL_dinput aliases the input (the reference passes positions_matrix for both, testbed_nerf.cu:2616) it runs
+		// last, because the grid backward still reads the input. Otherwise it runs before the grid backward: with the
+		// optimizer update fused into that backward (fopt->rec) the table holds the next step's weights afterwards,
+		// and the gradient is with respect to the forward's
+		const bool dinput_aliases = (const float*)ex.dL_dinput == in;
 		auto input_gradient = [&]() {
 			if (!ex.dL_dinput) return;
 			ProfScope ps("input_gradient", s);
@@ -465,9 +468,10 @@ struct ngp_model {
 			fmlp.fragmap = d_fragmap;
 			fopt = &fmlp;
 		}
+		if (!dinput_aliases) input_gradient();
 		scatter_grid_grad(s, b, grad_mode != NGP_GRAD_ACCUMULATE, fused ? &sj : nullptr, fopt);
 		if (ovl) NGP_HIP(hipStreamWaitEvent(s, ev_red, 0));
-		input_gradient();
+		if (dinput_aliases) input_gradient();
 	}
 	// Hash-grid backward: destination-bucketed exact sums (n >= 4096, or mode 3), else tcnn-style direct
 	// packed-f16 atomics (small batches, where the bucket plan costs more than the atomics).
@@ -1233,8 +1237,9 @@ int ngp_forward_backward(ngp_model* m, void* stream, uint32_t n, const float* in
 // captured training steps, ngp_trainer_fused_update)
 int ngp::forward_backward_with(ngp_model* m, void* stream, uint32_t n, const float* input, uint32_t input_stride, void* output,
                                uint32_t output_stride, const void* dL_doutput, uint32_t dL_stride, int grad_mode,
-                               const FusedAdam* fopt) {
+                               const FusedAdam* fopt, float* dL_dinput, uint32_t dL_dinput_stride) {
 	NGP_ARG(m && (n == 0 || (input && dL_doutput)));
+	if (check_dinput(m, dL_dinput, dL_dinput_stride) != NGP_OK) return NGP_INVALID;
 	NGP_TRY({
 		if (n == 0) return NGP_OK;
 		m->require_params(false);
@@ -1242,8 +1247,9 @@ int ngp::forward_backward_with(ngp_model* m, void* stream, uint32_t n, const flo
 		m->generation++;
 		m->prepare_grid_backward_async(S(stream), n, input, input_stride);
 		m->encode(S(stream), n, input, input_stride, e, m->enc_width, AoS, false, true);
-		m->train_pass(S(stream), n, input, input_stride, e, (f16*)output, output_stride, dL_doutput, dL_stride, grad_mode,
-		              BwdExtra{}, fopt);
+		BwdExtra ex;
+		ex.dL_dinput = dL_dinput; ex.dinput_stride = dL_dinput_stride;
+		m->train_pass(S(stream), n, input, input_stride, e, (f16*)output, output_stride, dL_doutput, dL_stride, grad_mode, ex, fopt);
 	});
 }
 extern "C" {
@@ -1398,7 +1404,8 @@ int ngp_trainer_capture_training_step(ngp_trainer* t, void* stream, uint32_t n, 
 // hyperparameters read from the ctl block) or nullptr (eager: host step + k).
 static int train_step_body(ngp_trainer* t, void* stream, uint32_t n, const float* input, uint32_t input_stride,
                            const void* dL_doutput, uint32_t dL_stride, float loss_scale, int with_optimizer,
-                           const Exchange& ex, bool fuse, const uint32_t* step_base, uint32_t k) {
+                           const Exchange& ex, bool fuse, const uint32_t* step_base, uint32_t k, float* dL_dinput,
+                           uint32_t dL_dinput_stride) {
 	ngp_model* m = t->model;
 	FusedAdam fa;
 	if (fuse) {
@@ -1429,7 +1436,7 @@ static int train_step_body(ngp_trainer* t, void* stream, uint32_t n, const float
 	}
 	if (rc == NGP_OK)
 		rc = forward_backward_with(m, stream, n, input, input_stride, nullptr, 0, dL_doutput, dL_stride, NGP_GRAD_OVERWRITE,
-		                           fuse || direct32 ? &fa : nullptr);
+		                           fuse || direct32 ? &fa : nullptr, dL_dinput, dL_dinput_stride);
 	m->bwd_parts = nullptr;
 	if (rc == NGP_OK && ex.fn) {
 		try {
@@ -1455,14 +1462,16 @@ static int train_step_body(ngp_trainer* t, void* stream, uint32_t n, const float
 }
 
 int ngp::train_step_with(ngp_trainer* t, void* stream, uint32_t n, const float* input, uint32_t input_stride,
-                         const void* dL_doutput, uint32_t dL_stride, float loss_scale, const Exchange& ex) {
-	NGP_ARG(t && n > 0 && input && dL_doutput && loss_scale > 0.f);
+                         const void* dL_doutput, uint32_t dL_stride, float loss_scale, const Exchange& ex, float* dL_dinput,
+                         uint32_t dL_dinput_stride) {
+	NGP_ARG(t && n > 0 && input && dL_doutput && loss_scale > 0.f && (const float*)dL_dinput != input);
 	NGP_TRY({
 		ngp_model* m = t->model;
 		m->require_params(false);
 		NGP_CHECK(m->gradients == t->g16, "train_step: the model's gradient buffer must be this trainer's");
 		const bool fuse = !ex.fn && t->fused_update_ok(n);
-		if (train_step_body(t, stream, n, input, input_stride, dL_doutput, dL_stride, loss_scale, 1, ex, fuse, nullptr, 0) != NGP_OK)
+		if (train_step_body(t, stream, n, input, input_stride, dL_doutput, dL_stride, loss_scale, 1, ex, fuse, nullptr, 0, dL_dinput,
+		                    dL_dinput_stride) != NGP_OK)
 			throw Error(g_last_error);
 		t->step++;
 	});
@@ -1473,6 +1482,14 @@ int ngp_trainer_train_step(ngp_trainer* t, void* stream, uint32_t n, const float
                            const void* dL_doutput, uint32_t dL_stride, float loss_scale) {
 	NGP_ARG(t);
 	return ngp::train_step_with(t, stream, n, input, input_stride, dL_doutput, dL_stride, loss_scale, t->exchange());
+}
+
+int ngp_trainer_train_step_input_gradient(ngp_trainer* t, void* stream, uint32_t n, const float* input, uint32_t input_stride,
+                                          const void* dL_doutput, uint32_t dL_stride, float loss_scale, float* dL_dinput,
+                                          uint32_t dL_dinput_stride) {
+	NGP_ARG(t && dL_dinput);
+	return ngp::train_step_with(t, stream, n, input, input_stride, dL_doutput, dL_stride, loss_scale, t->exchange(), dL_dinput,
+	                            dL_dinput_stride);
 }
 
 int ngp_trainer_fused_update_active(const ngp_trainer* t, uint32_t n_batch) {
@@ -1486,13 +1503,16 @@ int ngp_trainer_fused_update_active(const ngp_trainer* t, uint32_t n_batch) {
 // 1-GPU gradient).
 int ngp::capture_training_step_with(ngp_trainer* t, void* stream, uint32_t n, const float* input, uint32_t input_stride,
                                     const void* dL_doutput, uint32_t dL_stride, float loss_scale, uint32_t n_steps,
-                                    int with_optimizer, const Exchange& ex, ngp_graph** out) {
-	NGP_ARG(t && out && stream && n > 0 && input && dL_doutput && loss_scale > 0.f && n_steps >= 1 && ex.world >= 1);
+                                    int with_optimizer, const Exchange& ex, ngp_graph** out, float* dL_dinput,
+                                    uint32_t dL_dinput_stride) {
+	NGP_ARG(t && out && stream && n > 0 && input && dL_doutput && loss_scale > 0.f && n_steps >= 1 && ex.world >= 1 &&
+	        (const float*)dL_dinput != input);
 	NGP_TRY({
 		ngp_model* m = t->model;
 		m->require_params(false);
 		NGP_CHECK(m->gradients == t->g16, "capture: the model's gradient buffer must be this trainer's");
 		m->reserve(n);
+		if (dL_dinput && m->nerf) m->dsh_ws.get((size_t)n * 16 * sizeof(f16));  // train_pass: dL/d(SH) of the input gradient
 		hipStream_t s = S(stream);
 		auto g = std::make_unique<ngp_graph>();
 		g->trainer = t;
@@ -1503,7 +1523,7 @@ int ngp::capture_training_step_with(ngp_trainer* t, void* stream, uint32_t n, co
 		int rc = NGP_OK;
 		for (uint32_t k = 0; k < n_steps && rc == NGP_OK; ++k)
 			rc = train_step_body(t, stream, n, input, input_stride, dL_doutput, dL_stride, loss_scale, with_optimizer, ex, fuse,
-			                     t->ctl, k);  // step = device base (set per launch) + k
+			                     t->ctl, k, dL_dinput, dL_dinput_stride);  // step = device base (set per launch) + k
 		hipGraph_t graph = nullptr;
 		const hipError_t end = hipStreamEndCapture(s, &graph);
 		g->ws_epoch = m->ws_epoch;

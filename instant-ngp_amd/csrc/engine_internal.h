@@ -18,14 +18,17 @@ struct Exchange {
 	bool rank_known = false;  // set_data_parallel (sharding possible) vs set_allreduce (all-reduce only)
 };
 void widen_f16(const _Float16* a, float* b, uint64_t n, hipStream_t s);  // dp_comm.hip
-// ngp_forward_backward with the grid's lazy optimizer update fused into the backward (fopt may be NULL)
+// ngp_forward_backward with the grid's lazy optimizer update fused into the backward (fopt may be NULL). dL_dinput
+// (here and below; NULL: none, and then exactly the launches without it): fp32 AoS [n x dL_dinput_stride], the input
+// gradient with respect to the forward's weights (BwdExtra::dL_dinput); must not alias the input in a training step
 int forward_backward_with(ngp_model* m, void* stream, uint32_t n, const float* input, uint32_t input_stride, void* output,
-                          uint32_t output_stride, const void* dL_doutput, uint32_t dL_stride, int grad_mode, const FusedAdam* fopt);
+                          uint32_t output_stride, const void* dL_doutput, uint32_t dL_stride, int grad_mode, const FusedAdam* fopt,
+                          float* dL_dinput = nullptr, uint32_t dL_dinput_stride = 0);
 // ngp_trainer_capture_training_step with an explicit gradient exchange hook: `allreduce` (may be NULL)
 // runs on the gradient buffer between backward and optimizer, which scales by loss_scale * world.
 int capture_training_step_with(ngp_trainer* t, void* stream, uint32_t n, const float* input, uint32_t input_stride,
                                const void* dL_doutput, uint32_t dL_stride, float loss_scale, uint32_t n_steps, int with_optimizer,
-                               const Exchange& ex, ngp_graph** out);
+                               const Exchange& ex, ngp_graph** out, float* dL_dinput = nullptr, uint32_t dL_dinput_stride = 0);
 // The values ngp_graph_launch writes into the trainer's device control block before a launch of its graph (set_device_ctl:
 // step at ctl[0], the AdamConfig at ctl + CTL_CFG), for a caller that writes them in a kernel of its own, and
 // the launch without that write (the rest of ngp_graph_launch: workspace check, step and staleness bookkeeping).
@@ -38,5 +41,6 @@ int density_impl(ngp_model* m, void* stream, uint32_t n, const float* input, uin
                  uint32_t output_stride, uint32_t output_layout, int use_inference_params);
 // One eager step of what capture_training_step_with records (the host-callback exchange of gloo ranks)
 int train_step_with(ngp_trainer* t, void* stream, uint32_t n, const float* input, uint32_t input_stride, const void* dL_doutput,
-                    uint32_t dL_stride, float loss_scale, const Exchange& ex);
+                    uint32_t dL_stride, float loss_scale, const Exchange& ex, float* dL_dinput = nullptr,
+                    uint32_t dL_dinput_stride = 0);
 }  // namespace ngp

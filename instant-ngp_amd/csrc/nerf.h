@@ -50,6 +50,7 @@ struct Dataset {
 	Camera* d_cams = nullptr;
 	uint32_t* d_pixels = nullptr;  // RGBA8 packed, sRGB
 	std::vector<Camera> cams;
+	std::vector<float> xforms;  // [n_images x 12] the raw (start) transforms, as uploaded after the pixels
 	~Dataset();
 };
 
@@ -102,7 +103,9 @@ struct LossArgs {
 };
 
 // The kernels (each cites its reference kernel in nerf.hip).
-void sample_rays(const Dataset& ds, const ngp_nerf_config& cfg, const SampleArgs& a, uint32_t* tmp_u32, float* tmp_f32, hipStream_t s);
+// cams (optional): the device cameras to trace instead of the dataset's (a trainer's refined poses)
+void sample_rays(const Dataset& ds, const ngp_nerf_config& cfg, const SampleArgs& a, uint32_t* tmp_u32, float* tmp_f32, hipStream_t s,
+                 const Camera* cams = nullptr);
 size_t sample_tmp_u32(uint32_t n_rays);  // u32 of sample_rays' tmp_u32 (counts, count-wave sums and prefixes)
 void compute_loss(const Dataset& ds, const ngp_nerf_config& cfg, const LossArgs& a, uint32_t* tmp_u32, float* tmp_f32, hipStream_t s);
 void fill_rollover_f16(uint32_t n_elements, uint32_t stride, const uint32_t* n_input, f16* data, bool rescale, hipStream_t s);

@@ -1085,8 +1085,10 @@ static uint32_t sample_count_waves(uint32_t n_rays, uint32_t rgk) {
 }
 size_t sample_tmp_u32(uint32_t n_rays) { return n_rays + 4 * (size_t)sample_count_waves(n_rays, std::max(RG, sampler_rg<true>())); }
 
-void sample_rays(const Dataset& ds, const ngp_nerf_config& cfg, const SampleArgs& a, uint32_t* tmp, float* tmpf, hipStream_t s) {
+void sample_rays(const Dataset& ds, const ngp_nerf_config& cfg, const SampleArgs& a, uint32_t* tmp, float* tmpf, hipStream_t s,
+                 const Camera* cams) {
 	if (a.n_rays == 0) return;
+	if (!cams) cams = ds.d_cams;
 	NGP_CHECK(tmpf != nullptr, "sample_rays: float scratch of sample_tmp_f32(n_rays) floats required");
 	const bool cone0 = cfg.cone_angle_constant <= 1e-5f;
 	const uint32_t rgk = cone0 ? sampler_rg<true>() : RG;
@@ -1102,10 +1104,10 @@ void sample_rays(const Dataset& ds, const ngp_nerf_config& cfg, const SampleArgs
 	{
 		ProfScope ps("sample_count", s);
 		if (cone0)
-			k_sample_count<true><<<blocks0, NGP_SAMPLER_BLOCK, 0, s>>>(ds.d_cams, ds.d_pixels, ds.n_images, cfg, a, nsteps, tbuf, geo, cone,
+			k_sample_count<true><<<blocks0, NGP_SAMPLER_BLOCK, 0, s>>>(cams, ds.d_pixels, ds.n_images, cfg, a, nsteps, tbuf, geo, cone,
 			                                                          wsum);
 		else
-			k_sample_count<false><<<blocks, NGP_SAMPLER_BLOCK, 0, s>>>(ds.d_cams, ds.d_pixels, ds.n_images, cfg, a, nsteps, tbuf, geo, cone,
+			k_sample_count<false><<<blocks, NGP_SAMPLER_BLOCK, 0, s>>>(cams, ds.d_pixels, ds.n_images, cfg, a, nsteps, tbuf, geo, cone,
 			                                                           wsum);
 		NGP_HIP(hipGetLastError());
 	}

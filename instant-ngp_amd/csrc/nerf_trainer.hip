@@ -22,6 +22,7 @@
 #include "knobs.h"
 #include "msgpack.h"
 #include "nerf.h"
+#include "nerf_camera.h"
 #include "profiler.h"
 
 using namespace ngp;
@@ -180,6 +181,9 @@ struct ngp_nerf_trainer {
 		if (own_stream) (void)hipStreamDestroy(own_stream);
 		if (sample_stream) (void)hipStreamDestroy(sample_stream);
 		if (host_ctr) (void)hipHostFree((void*)host_ctr);
+		if (d_cams) (void)hipFree(d_cams);
+		if (d_raw) (void)hipFree(d_raw);
+		ngp_pose_optimizer_destroy(pose);
 	}
 	// data parallelism: rank r traces global rays [R r / N, R (r+1) / N), compacts to B / N,
 	// evaluates 1/N of the density-grid samples; the exchange steps go through `allreduce`
@@ -214,7 +218,33 @@ struct ngp_nerf_trainer {
 		const bool on = knobs.early < 0 ? cfg.cone_angle_constant > 1e-5f : knobs.early != 0;
 		return on && !dp();
 	}
+	// The sampler's outputs alternate between the two sets: under early publish, and with camera pose refinement, whose
+	// gradient kernels read the ray buffers after the training pass: the next sampler, prelaunched under that pass,
+	// then writes the other set (last read by the step before this one, complete once this step's counters are
+	// published) instead of waiting for this step's release
+	bool two_sets() const { return early() || (cam.optimize_extrinsics != 0 && !dp()); }
 	Buf loss_state;  // compute_loss: pass 1's per-sample compositing state for pass 2 (LossArgs::state)
+	// Camera pose refinement (Testbed::Nerf::Training::optimize_extrinsics and its neighbours, testbed.h:716-785). The
+	// trainer traces its own device copy of the cameras: the dataset's array to begin with (bit for bit), rebuilt from
+	// `xforms` and the per-camera offsets (ngp_pose_apply, then effective_camera_matrix) whenever those change; d_raw
+	// is the raw-transform array mark_untrained_density_grid reads, refreshed the same way.
+	ngp_nerf_camera_training cam{0, 16, 1e-4f, 1e-3f};
+	ngp_pose_optimizer* pose = nullptr;
+	std::vector<float> xforms;   // [n_images x 12] the transforms the offsets apply to (set_camera_extrinsics writes them)
+	std::vector<Camera> cams;    // host mirror of d_cams
+	Camera* d_cams = nullptr;
+	float* d_raw = nullptr;
+	uint32_t n_steps_since_cam_update = 0;
+	Buf cam_grad, cam_ray_grad, dinput;  // [2][n_images x 3] accumulators {pos, rot}; per-ray workspace; dL/dinput [B x 7]
+	const float* graph_dinput = nullptr;  // the gradient pointer the training graph was captured with
+	// the last step's sampler call, for ngp_nerf_trainer_last_samples
+	ngp_rng last_rng{0, 0};
+	uint32_t last_n_rays = 0, last_max_samples = 0;
+	const uint32_t* last_ray_indices = nullptr;
+	const float* last_rays = nullptr;
+	const uint32_t* last_counters = nullptr;
+	void refined_xform(uint32_t i, float out[12]) const;
+	void rebuild_cameras(hipStream_t s);
 	// training error map (Testbed::Nerf::Training::ErrorMap and its update window, testbed.h:668-677, 736-738)
 	Buf em_data, em_cdf_x, em_cdf_y, em_cdf_img;
 	uint32_t em_w = 0, em_h = 0, em_cdf_w = 0, em_cdf_h = 0;
@@ -345,6 +375,7 @@ int ngp_nerf_dataset_create(uint32_t n_images, const ngp_nerf_image* images, con
 		std::vector<float> raw(12 * n_images);
 		for (uint32_t i = 0; i < n_images; ++i) memcpy(&raw[12 * i], images[i].xform, 48);
 		NGP_HIP(hipMemcpy(d->ds.d_pixels + total, raw.data(), raw.size() * 4, hipMemcpyHostToDevice));
+		d->ds.xforms = raw;
 		NGP_HIP(hipMalloc(&d->ds.d_cams, n_images * sizeof(Camera)));
 		NGP_HIP(hipMemcpy(d->ds.d_cams, cams.data(), n_images * sizeof(Camera), hipMemcpyHostToDevice));
 		d->ds.cams = cams;
@@ -354,15 +385,11 @@ int ngp_nerf_dataset_create(uint32_t n_images, const ngp_nerf_image* images, con
 
 void ngp_nerf_dataset_destroy(ngp_nerf_dataset* d) { delete d; }
 
-static const float* raw_xforms(const Dataset& ds) {
-	const Camera& last = ds.cams.back();
-	return (const float*)(ds.d_pixels + last.pixel_offset + (uint64_t)last.width * last.height);
-}
-
-int ngp_nerf_generate_training_samples(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
-                                       uint32_t ray_offset, uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples,
-                                       const uint8_t* bitfield, uint32_t* ray_indices, float* rays, uint32_t* numsteps,
-                                       float* coords, uint32_t* counters) {
+// ngp_nerf_generate_training_samples, optionally tracing `cams` instead of the dataset's cameras
+static int generate_training_samples(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
+                                     uint32_t ray_offset, uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples,
+                                     const uint8_t* bitfield, uint32_t* ray_indices, float* rays, uint32_t* numsteps,
+                                     float* coords, uint32_t* counters, const Camera* cams) {
 	if (!ds || !cfg || !bitfield || !ray_indices || !rays || !numsteps || !coords || !counters) return NGP_INVALID;
 	NERF_TRY({
 		SampleArgs a{};
@@ -371,8 +398,15 @@ int ngp_nerf_generate_training_samples(const ngp_nerf_dataset* ds, const ngp_ner
 		a.ray_indices = ray_indices; a.rays = rays; a.numsteps = numsteps; a.coords = coords; a.counters = counters;
 		static thread_local Buf tmp, tmpf;
 		if (n_rays == 0) { NGP_HIP(hipMemsetAsync(counters, 0, 8, S(stream))); return NGP_OK; }
-		sample_rays(ds->ds, *cfg, a, tmp.get<uint32_t>(sample_tmp_u32(n_rays)), tmpf.get<float>(sample_tmp_f32(n_rays)), S(stream));
+		sample_rays(ds->ds, *cfg, a, tmp.get<uint32_t>(sample_tmp_u32(n_rays)), tmpf.get<float>(sample_tmp_f32(n_rays)), S(stream), cams);
 	});
+}
+int ngp_nerf_generate_training_samples(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
+                                       uint32_t ray_offset, uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples,
+                                       const uint8_t* bitfield, uint32_t* ray_indices, float* rays, uint32_t* numsteps,
+                                       float* coords, uint32_t* counters) {
+	return generate_training_samples(ds, cfg, stream, n_rays, ray_offset, n_rays_total, rng, max_samples, bitfield, ray_indices, rays,
+	                                 numsteps, coords, counters, nullptr);
 }
 
 static int nerf_compute_loss(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
@@ -498,6 +532,15 @@ int ngp_nerf_trainer_create(ngp_model* model, ngp_trainer* trainer, const ngp_ne
 		NGP_HIP(hipMemset(t->grid.get<float>(n_el), 0, (size_t)n_el * 4));
 		NGP_HIP(hipMemset(t->bitfield.get<uint8_t>(BITFIELD_BYTES), 0, BITFIELD_BYTES));
 		NGP_HIP(hipMemset(t->mean.get<float>(1 + 512), 0, (1 + 512) * 4));
+		// the trainer's cameras: the dataset's, verbatim
+		const Dataset& d = ds->ds;
+		t->cams = d.cams;
+		t->xforms = d.xforms;
+		NGP_HIP(hipMalloc((void**)&t->d_cams, d.n_images * sizeof(Camera)));
+		NGP_HIP(hipMemcpy(t->d_cams, d.d_cams, d.n_images * sizeof(Camera), hipMemcpyDeviceToDevice));
+		NGP_HIP(hipMalloc((void**)&t->d_raw, (size_t)d.n_images * 12 * sizeof(float)));
+		NGP_HIP(hipMemcpy(t->d_raw, d.xforms.data(), (size_t)d.n_images * 12 * sizeof(float), hipMemcpyHostToDevice));
+		if (ngp_pose_optimizer_create(d.n_images, &t->pose) != NGP_OK) throw Error(ngp_last_error());
 		*out = t.release();
 	});
 }
@@ -528,6 +571,98 @@ int ngp_nerf_trainer_set_config(ngp_nerf_trainer* t, const ngp_nerf_config* cfg)
 }
 
 static void check_rc(int rc) { if (rc != NGP_OK) throw Error(ngp_last_error()); }
+
+// ---- camera pose refinement: the trainer's cameras -----------------------------------------------------------------
+// Training::update_transforms (testbed_nerf.cu:2980-3024) for image i: its transform with the optimisers' offsets
+void ngp_nerf_trainer::refined_xform(uint32_t i, float out[12]) const {
+	ngp_adam_state p, r;
+	check_rc(ngp_pose_optimizer_get(pose, i, &p, &r));
+	ngp::pose::apply(&xforms[(size_t)12 * i], r.variable, p.variable, out);
+}
+// ... for every image, into the cameras the sampler traces and the raw transforms mark_untrained_density_grid reads.
+// Uploaded on `s` and waited for: the caller launches the next sampler afterwards, on any stream.
+void ngp_nerf_trainer::rebuild_cameras(hipStream_t s) {
+	const uint32_t n = (uint32_t)cams.size();
+	std::vector<float> raw((size_t)12 * n);
+	for (uint32_t i = 0; i < n; ++i) {
+		refined_xform(i, &raw[(size_t)12 * i]);
+		effective_camera_matrix(&raw[(size_t)12 * i], cams[i].m);
+	}
+	NGP_HIP(hipMemcpyAsync(d_cams, cams.data(), n * sizeof(Camera), hipMemcpyHostToDevice, s));
+	NGP_HIP(hipMemcpyAsync(d_raw, raw.data(), raw.size() * sizeof(float), hipMemcpyHostToDevice, s));
+	NGP_HIP(hipStreamSynchronize(s));
+}
+// the poses are about to change outside a step: nothing may still trace, or be launched to trace, the old ones
+static void cameras_quiesce(ngp_nerf_trainer* t) {
+	t->drain();
+	NGP_HIP(hipDeviceSynchronize());
+}
+
+int ngp_nerf_trainer_get_camera_training(const ngp_nerf_trainer* t, ngp_nerf_camera_training* out) {
+	if (!t || !out) return NGP_INVALID;
+	*out = t->cam;
+	return NGP_OK;
+}
+
+int ngp_nerf_trainer_set_camera_training(ngp_nerf_trainer* t, const ngp_nerf_camera_training* c) {
+	if (!t || !c || c->n_steps_between_cam_updates == 0 || !(c->extrinsic_learning_rate >= 0.f) || !(c->extrinsic_l2_reg >= 0.f))
+		return NGP_INVALID;
+	NERF_TRY({
+		NGP_CHECK(!c->optimize_extrinsics || !t->dp(),
+		          "camera pose refinement is single-GPU: the per-image gradient sums of a data-parallel trainer would need "
+		          "their own all-reduce");
+		const bool toggled = (c->optimize_extrinsics != 0) != (t->cam.optimize_extrinsics != 0);
+		if (toggled) {
+			// the training pass is re-captured with (or without) the input gradient; a prelaunched sampler was
+			// released under the other rule (step_release_samples)
+			cameras_quiesce(t);
+			t->n_steps_since_cam_update = 0;
+		}
+		t->cam = *c;
+	});
+}
+
+int ngp_nerf_trainer_camera_extrinsics(const ngp_nerf_trainer* t, uint32_t i, float* out) {
+	if (!t || !out || i >= t->cams.size()) return NGP_INVALID;
+	NERF_TRY(t->refined_xform(i, out));
+}
+
+int ngp_nerf_trainer_set_camera_extrinsics(ngp_nerf_trainer* t, uint32_t i, const float* xform) {
+	if (!t || !xform || i >= t->cams.size()) return NGP_INVALID;
+	NERF_TRY({
+		cameras_quiesce(t);
+		memcpy(&t->xforms[(size_t)12 * i], xform, 48);
+		check_rc(ngp_pose_optimizer_reset_one(t->pose, i));
+		t->rebuild_cameras(nullptr);
+	});
+}
+
+int ngp_nerf_trainer_reset_camera_extrinsics(ngp_nerf_trainer* t) {
+	if (!t) return NGP_INVALID;
+	NERF_TRY({
+		cameras_quiesce(t);
+		check_rc(ngp_pose_optimizer_reset(t->pose));
+		t->n_steps_since_cam_update = 0;
+		t->rebuild_cameras(nullptr);
+	});
+}
+
+int ngp_nerf_trainer_last_samples(const ngp_nerf_trainer* t, ngp_rng* rng, uint32_t* n_rays, uint32_t* max_samples,
+                                  const uint32_t** ray_indices, const float** rays, const uint32_t** counters) {
+	if (!t || !t->last_ray_indices || t->world != 1) return NGP_INVALID;
+	if (rng) *rng = t->last_rng;
+	if (n_rays) *n_rays = t->last_n_rays;
+	if (max_samples) *max_samples = t->last_max_samples;
+	if (ray_indices) *ray_indices = t->last_ray_indices;
+	if (rays) *rays = t->last_rays;
+	if (counters) *counters = t->last_counters;
+	return NGP_OK;
+}
+
+int ngp_nerf_trainer_pose_optimizer_state(const ngp_nerf_trainer* t, uint32_t i, ngp_adam_state* pos, ngp_adam_state* rot) {
+	if (!t || i >= t->cams.size()) return NGP_INVALID;
+	return ngp_pose_optimizer_get(t->pose, i, pos, rot);
+}
 
 // ---- rendering ---------------------------------------------------------------------------------
 int ngp_nerf_renderer_create(ngp_nerf_renderer** out) {
@@ -612,6 +747,10 @@ int ngp_nerf_render(ngp_nerf_renderer* r, ngp_model* model, const ngp_nerf_confi
 
 int ngp_nerf_trainer_set_data_parallel(ngp_nerf_trainer* t, uint32_t rank, uint32_t world, ngp_allreduce_fn allreduce, void* user) {
 	if (!t || world == 0 || rank >= world || (world > 1 && !allreduce)) return NGP_INVALID;
+	if (allreduce && t->cam.optimize_extrinsics) {
+		nerf_set_error("camera pose refinement is single-GPU: turn optimize_extrinsics off before setting an exchange hook");
+		return NGP_ERROR;
+	}
 	t->drain();
 	// the sample-set choice (ngp_nerf_trainer::early) depends on the exchange: the last step's passes finish first
 	if (hipDeviceSynchronize() != hipSuccess) return NGP_ERROR;
@@ -721,7 +860,7 @@ static void update_density_grid(ngp_nerf_trainer* t, hipStream_t s, float decay,
 		t->ema_step = 0;
 		const Dataset& ds = t->data->ds;
 		const uint32_t n_el = GRID_N_CELLS * (t->cfg.max_cascade + 1);
-		k_mark_untrained<<<div_round_up(n_el, 128), 128, 0, s>>>(n_el, (float*)t->grid.p, ds.n_images, ds.d_cams, raw_xforms(ds), true);
+		k_mark_untrained<<<div_round_up(n_el, 128), 128, 0, s>>>(n_el, (float*)t->grid.p, ds.n_images, t->d_cams, t->d_raw, true);
 		NGP_HIP(hipGetLastError());
 	}
 	grid_update_samples(t, s, n_uniform, n_nonuniform);
@@ -807,7 +946,7 @@ static SamplePlan sample_plan(ngp_nerf_trainer* t) {
 	if (t->measured_before_compaction_local == 0) p.max_inference = p.max_samples;
 	else p.max_inference = next_multiple(std::min(t->measured_before_compaction_local, p.max_samples), 256);
 	p.Ra = std::max(p.Rl, 1u);
-	auto& set = t->sets[t->early() && (t->training_step & 1u)];  // the step's sample set (ngp_nerf_trainer::early)
+	auto& set = t->sets[t->two_sets() && (t->training_step & 1u)];  // the step's sample set (ngp_nerf_trainer::two_sets)
 	p.ray_indices = set.ray_indices.get<uint32_t>(p.Ra);
 	p.rays = set.rays.get<float>((size_t)p.Ra * 6);
 	p.numsteps = set.numsteps.get<uint32_t>((size_t)p.Ra * 2);
@@ -818,8 +957,8 @@ static SamplePlan sample_plan(ngp_nerf_trainer* t) {
 static void launch_sampler(ngp_nerf_trainer* t, const SamplePlan& p, hipStream_t s) {
 	ProfScope ps("nerf_sample", s);
 	const ngp_rng rng{t->rng.state, t->rng.inc};
-	check_rc(ngp_nerf_generate_training_samples(t->data, &t->cfg, s, p.Rl, p.r_lo, p.R, rng, p.max_inference,
-	                                            (const uint8_t*)t->bitfield.p, p.ray_indices, p.rays, p.numsteps, p.coords, p.ctr));
+	check_rc(generate_training_samples(t->data, &t->cfg, s, p.Rl, p.r_lo, p.R, rng, p.max_inference, (const uint8_t*)t->bitfield.p,
+	                                   p.ray_indices, p.rays, p.numsteps, p.coords, p.ctr, t->d_cams));
 }
 static bool density_grid_update_due(uint32_t step) {
 	const uint32_t skip = std::min(std::max(step / 16u, 1u), 16u);
@@ -970,6 +1109,9 @@ struct Step {
 	bool early_pub = false;     // the loss's scan publishes the counters (ngp_nerf_trainer::early)
 	bool can_pipeline = false;  // the next step's sampler may run under this step's training pass: the exchange is
 	                            // stream-ordered (single GPU, or the engine's RCCL communicator)
+	bool cam = false;           // camera pose refinement: the training pass also writes dL/dinput
+	float* dinput = nullptr;    // [Bl x 7]
+	bool cam_updated = false;   // this step ended with a pose update (step_camera_update)
 };
 
 // training_prep_nerf (a prelaunched sampler implies no update was due at this step)
@@ -1005,6 +1147,10 @@ static void step_plan(ngp_nerf_trainer* t, Step& c) {
 	c.dp = t->dp();
 	c.early_pub = t->early() && sp.Rl > 0;
 	c.can_pipeline = t->pipeline && (!c.dp || t->dp_capturable);
+	c.cam = t->cam.optimize_extrinsics != 0;
+	t->last_rng = c.rng; t->last_n_rays = sp.R; t->last_max_samples = sp.max_inference;
+	t->last_ray_indices = sp.ray_indices; t->last_rays = sp.rays; t->last_counters = sp.ctr;
+	c.dinput = c.cam ? t->dinput.get<float>((size_t)sp.Bl * 7) : nullptr;
 }
 
 // The step's samples (launched here, or awaited from the prelaunch) and the network's output for every one of them.
@@ -1077,7 +1223,7 @@ static void step_loss_and_publish(ngp_nerf_trainer* t, hipStream_t s, const Step
 static void step_release_samples(ngp_nerf_trainer* t, hipStream_t s, const Step& c) {
 	if (!c.can_pipeline) return;
 	if (!t->sample_stream) t->sample_stream = make_sampler_stream(t->knobs);
-	if (!t->early()) t->released.signal(s);
+	if (!t->two_sets()) t->released.signal(s);
 }
 
 static void step_train_pass(ngp_nerf_trainer* t, hipStream_t s, const Step& c) {
@@ -1088,14 +1234,15 @@ static void step_train_pass(ngp_nerf_trainer* t, hipStream_t s, const Step& c) {
 		// when the graph's buffers moved: the sample buffers, or any model workspace (a density-grid
 		// update through ngp_density can grow the encoding workspace after a snapshot load)
 		if (!t->train_graph || t->graph_in != c.coords_c || t->graph_dl != c.dloss || t->graph_n != Bl ||
-		    t->graph_epoch != ngp_model_workspace_epoch(t->model)) {
+		    t->graph_dinput != c.dinput || t->graph_epoch != ngp_model_workspace_epoch(t->model)) {
 			if (t->train_graph) ngp_graph_destroy(t->train_graph);
 			t->train_graph = nullptr;
 			// data parallel: the shards' dL/doutput is scaled by 128 / R_global, so the summed gradient is the
 			// 1-GPU gradient: world factor 1 in the optimizer
 			check_rc(capture_training_step_with(t->trainer, s, Bl, c.coords_c, 7, c.dloss, 16, 128.0f, 1, 1, t->exchange(),
-			                                    &t->train_graph));
+			                                    &t->train_graph, c.dinput, 7));
 			t->graph_in = c.coords_c;
+			t->graph_dinput = c.dinput;
 			t->graph_dl = c.dloss;
 			t->graph_n = Bl;
 			t->graph_epoch = ngp_model_workspace_epoch(t->model);
@@ -1107,6 +1254,41 @@ static void step_train_pass(ngp_nerf_trainer* t, hipStream_t s, const Step& c) {
 		check_rc(train_step_with(t->trainer, s, Bl, c.coords_c, 7, c.dloss, 16, 128.0f, t->exchange()));
 	}
 	t->rng.advance();  // m_rng.advance() (testbed_nerf.cu:4127)
+}
+
+// Camera pose refinement, device part (testbed_nerf.cu:3641-3644, 4071-4125): the compacted batch's input gradient summed per
+// image into the trainer's accumulators, which start from zero after every pose update.
+static void step_camera_gradients(ngp_nerf_trainer* t, hipStream_t s, const Step& c) {
+	if (!c.cam) return;
+	ProfScope ps("nerf_camera_gradients", s);
+	const uint32_t n_images = t->data->ds.n_images;
+	float* acc = t->cam_grad.get<float>((size_t)6 * n_images);
+	if (t->n_steps_since_cam_update == 0) NGP_HIP(hipMemsetAsync(acc, 0, (size_t)6 * n_images * sizeof(float), s));
+	const SamplePlan& sp = c.sp;
+	CamGradArgs a{};
+	a.n_rays_cap = sp.Rl; a.n_rays_total = sp.R; a.n_images = n_images;
+	a.ray_counter = sp.ctr; a.ray_indices = sp.ray_indices; a.rays = sp.rays; a.numsteps = sp.numsteps;
+	a.coords = c.coords_c; a.coords_grad = c.dinput; a.grad_stride = 7;
+	for (int k = 0; k < 3; ++k) { a.aabb_min[k] = t->cfg.aabb_min[k]; a.aabb_max[k] = t->cfg.aabb_max[k]; }
+	a.ray_grad = t->cam_ray_grad.get<float>((size_t)sp.Ra * 6);
+	a.pos_grad = acc; a.rot_grad = acc + (size_t)3 * n_images;
+	camera_gradients(a, CAM_GRAD_LANES, s);
+}
+
+// Camera pose refinement, host part (testbed_nerf.cu:3754-3809): every n_steps_between_cam_updates steps the sums come
+// back, every camera's optimisers step and the cameras are rebuilt and uploaded before any later sampler is launched.
+static void step_camera_update(ngp_nerf_trainer* t, hipStream_t s, Step& c) {
+	if (!c.cam) return;
+	if (++t->n_steps_since_cam_update < std::max(t->cam.n_steps_between_cam_updates, 1u)) return;
+	const uint32_t n_images = t->data->ds.n_images;
+	std::vector<float> g((size_t)6 * n_images);
+	NGP_HIP(hipMemcpyAsync(g.data(), t->cam_grad.p, g.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+	NGP_HIP(hipStreamSynchronize(s));
+	check_rc(ngp_pose_optimizer_step(t->pose, g.data(), g.data() + (size_t)3 * n_images, std::max(t->cam.n_steps_between_cam_updates, 1u),
+	                                 t->cam.extrinsic_learning_rate, t->cam.extrinsic_l2_reg, ngp_trainer_learning_rate(t->trainer)));
+	t->rebuild_cameras(s);
+	t->n_steps_since_cam_update = 0;
+	c.cam_updated = true;
 }
 
 // NerfCounters::update_after_training (testbed_nerf.cu:3583-3609): the host reads the step's counters and adapts
@@ -1148,11 +1330,12 @@ static float step_read_counters(ngp_nerf_trainer* t, hipStream_t s, const Step& 
 
 // next step's sampler, concurrent with this step's training pass (no density-grid update due first)
 static void step_prelaunch_sampler(ngp_nerf_trainer* t, const Step& c) {
-	if (!c.can_pipeline || t->measured_batch_size == 0 || density_grid_update_due(t->training_step)) return;
+	// (nor a pose update: that step's cameras are uploaded on the step's stream, where the next sampler then runs)
+	if (!c.can_pipeline || t->measured_batch_size == 0 || density_grid_update_due(t->training_step) || c.cam_updated) return;
 	const SamplePlan np = sample_plan(t);
 	// early(): the sampler writes the other sample set, which the step before last read (complete: this step's
 	// counters are published), so it waits on nothing
-	if (!t->early()) t->released.wait(t->sample_stream);
+	if (!t->two_sets()) t->released.wait(t->sample_stream);
 	launch_sampler(t, np, t->sample_stream);
 	t->sampled.signal(t->sample_stream);
 	t->pre_R = np.R;
@@ -1186,8 +1369,10 @@ int ngp_nerf_train_step(ngp_nerf_trainer* t, void* stream, int get_loss, ngp_ner
 		step_loss_and_publish(t, s, c);
 		step_release_samples(t, s, c);
 		step_train_pass(t, s, c);
+		step_camera_gradients(t, s, c);
 		++t->training_step;
 		const float loss_scalar = step_read_counters(t, s, c);
+		step_camera_update(t, s, c);
 		error_map_step_done(t, s);
 		step_prelaunch_sampler(t, c);
 		step_pregenerate_grid_samples(t, c);
@@ -1272,6 +1457,36 @@ Value load_network_config(const char* path) {  // Testbed::load_network_config (
 Value vec3(const float* v) {
 	Value a = Value::array();
 	for (int k = 0; k < 3; ++k) a.arr.push_back(Value::real(v[k]));
+	return a;
+}
+
+// one per-camera optimiser with the reference's member names (adam_optimizer.h:174-194)
+Value adam_to_value(const ngp_adam_state& a) {
+	Value v = Value::object();
+	v["iter"] = Value::uint(a.iter);
+	v["first_moment"] = vec3(a.first_moment);
+	v["second_moment"] = vec3(a.second_moment);
+	v["variable"] = vec3(a.variable);
+	v["learning_rate"] = Value::real(a.learning_rate);
+	v["epsilon"] = Value::real(a.epsilon);
+	v["beta1"] = Value::real(a.beta1);
+	v["beta2"] = Value::real(a.beta2);
+	return v;
+}
+ngp_adam_state adam_from_value(const Value& v) {
+	ngp_adam_state a;
+	a.iter = (uint32_t)v.at("iter").number();
+	const char* names[3] = {"first_moment", "second_moment", "variable"};
+	float* dst[3] = {a.first_moment, a.second_moment, a.variable};
+	for (int m = 0; m < 3; ++m) {
+		const Value& x = v.at(names[m]);
+		NGP_CHECK(x.type == Value::Array && x.arr.size() == 3, "snapshot: a camera optimiser's vectors hold three numbers");
+		for (int k = 0; k < 3; ++k) dst[m][k] = (float)x.arr[k].number();
+	}
+	a.learning_rate = (float)v.at("learning_rate").number();
+	a.epsilon = (float)v.at("epsilon").number();
+	a.beta1 = (float)v.at("beta1").number();
+	a.beta2 = (float)v.at("beta2").number();
 	return a;
 }
 
@@ -1391,6 +1606,18 @@ int ngp_nerf_save_snapshot(ngp_nerf_trainer* t, void* stream, const char* path, 
 		nerf["rgb"]["rays_per_batch"] = Value::uint(t->rays_per_batch);
 		nerf["rgb"]["measured_batch_size"] = Value::uint(t->measured_batch_size);
 		nerf["rgb"]["measured_batch_size_before_compaction"] = Value::uint(t->measured_before_compaction);
+		// the per-camera optimisers, as VarAdamOptimizer::to_json writes them (testbed.cu:4891-4892)
+		{
+			Value pos = Value::array(), rot = Value::array();
+			for (uint32_t i = 0; i < t->cams.size(); ++i) {
+				ngp_adam_state p, r;
+				check_ok(ngp_pose_optimizer_get(t->pose, i, &p, &r));
+				pos.arr.push_back(adam_to_value(p));
+				rot.arr.push_back(adam_to_value(r));
+			}
+			nerf["cam_pos_offset"] = pos;
+			nerf["cam_rot_offset"] = rot;
+		}
 		snap["training_step"] = Value::uint(t->training_step);
 		snap["loss"] = Value::real(t->loss_scalar);
 		snap["aabb"]["min"] = vec3(t->cfg.aabb_min);
@@ -1435,6 +1662,28 @@ int ngp_nerf_load_snapshot(ngp_nerf_trainer* t, void* stream, const char* path) 
 		t->training_step = (uint32_t)snap.at("training_step").number();
 		t->loss_scalar = (float)snap.number_or("loss", 0.0);
 		t->ema_step = (uint32_t)snap.number_or("density_grid_ema_step", (double)t->training_step);
+		// the refined poses (testbed.cu:5048-5051): the optimisers where the snapshot has them for this many images,
+		// zero offsets otherwise; then the cameras from them
+		{
+			const Value& nerf = snap.at("nerf");
+			const Value* pos = nerf.find("cam_pos_offset");
+			const Value* rot = nerf.find("cam_rot_offset");
+			const size_t n = t->cams.size();
+			check_ok(ngp_pose_optimizer_reset(t->pose));
+			if (pos && pos->type == Value::Array && pos->arr.size() == n)
+				for (uint32_t i = 0; i < n; ++i) {
+					const ngp_adam_state st = adam_from_value(pos->arr[i]);
+					check_ok(ngp_pose_optimizer_set_state(t->pose, i, &st, nullptr));
+				}
+			if (rot && rot->type == Value::Array && rot->arr.size() == n)
+				for (uint32_t i = 0; i < n; ++i) {
+					const ngp_adam_state st = adam_from_value(rot->arr[i]);
+					check_ok(ngp_pose_optimizer_set_state(t->pose, i, nullptr, &st));
+				}
+			t->n_steps_since_cam_update = 0;
+			NGP_HIP(hipDeviceSynchronize());
+			t->rebuild_cameras(s);
+		}
 		NGP_HIP(hipStreamSynchronize(s));
 	});
 }

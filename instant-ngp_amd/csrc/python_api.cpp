@@ -364,6 +364,61 @@ PYBIND11_MODULE(pyngp, m) {
 	ntr.def_property("loss_type", [](NerfTrainingView& v) { return (ELossType)v.t->nerf_config().loss_type; },
 	                 [](NerfTrainingView& v, ELossType l) { v.t->nerf_config().loss_type = (uint32_t)l; v.t->push_nerf_config(); })
 		.def_property_readonly("n_images_for_training", [](NerfTrainingView& v) { return v.t->n_training_views(); })
+		// camera pose refinement (python_api.cu:618-653)
+		.def_property("optimize_extrinsics", [](NerfTrainingView& v) { return v.t->camera_training().optimize_extrinsics != 0; },
+		              [](NerfTrainingView& v, bool x) {
+			              const uint32_t was = v.t->camera_training().optimize_extrinsics;
+			              v.t->camera_training().optimize_extrinsics = x ? 1u : 0u;
+			              try { v.t->push_camera_training(); } catch (...) { v.t->camera_training().optimize_extrinsics = was; throw; }
+		              })
+		.def_property("n_steps_between_cam_updates", [](NerfTrainingView& v) { return v.t->camera_training().n_steps_between_cam_updates; },
+		              [](NerfTrainingView& v, uint32_t x) {
+			              if (x == 0) throw std::runtime_error("n_steps_between_cam_updates: at least 1");
+			              v.t->camera_training().n_steps_between_cam_updates = x;
+			              v.t->push_camera_training();
+		              })
+		.def_property("extrinsic_l2_reg", [](NerfTrainingView& v) { return v.t->camera_training().extrinsic_l2_reg; },
+		              [](NerfTrainingView& v, float x) { v.t->camera_training().extrinsic_l2_reg = x; v.t->push_camera_training(); })
+		.def_property("extrinsic_learning_rate", [](NerfTrainingView& v) { return v.t->camera_training().extrinsic_learning_rate; },
+		              [](NerfTrainingView& v, float x) { v.t->camera_training().extrinsic_learning_rate = x; v.t->push_camera_training(); })
+		.def("get_camera_extrinsics",
+		     [](NerfTrainingView& v, int frame_idx) {
+			     float m[12];
+			     v.t->get_camera_extrinsics(frame_idx, m);
+			     py::array_t<float> a({3, 4});
+			     std::memcpy(a.mutable_data(), m, sizeof m);
+			     return a;
+		     },
+		     py::arg("frame_idx"), "The refined camera-to-world [3 x 4] of a training image, in the dataset's (NeRF) convention.")
+		.def("set_camera_extrinsics",
+		     [](NerfTrainingView& v, int frame_idx, py::array_t<float, py::array::c_style | py::array::forcecast> m, bool convert_to_ngp) {
+			     if (m.ndim() != 2 || m.shape(0) < 3 || m.shape(1) != 4) throw std::runtime_error("set_camera_extrinsics: a [3 x 4] camera_to_world");
+			     v.t->set_camera_extrinsics(frame_idx, m.data(), convert_to_ngp);
+		     },
+		     py::arg("frame_idx"), py::arg("camera_to_world"), py::arg("convert_to_ngp") = true,
+		     "Replace a training image's camera-to-world [3 x 4] and reset its pose optimiser; convert_to_ngp: given in the NeRF convention.")
+		.def("reset_camera_extrinsics", [](NerfTrainingView& v) { v.t->reset_camera_extrinsics(); })
+		// engine extension: cam_pos_offset[frame_idx] / cam_rot_offset[frame_idx] as dicts with the snapshot's member names
+		.def("camera_optimizer_state",
+		     [](NerfTrainingView& v, int frame_idx) {
+			     ngp_adam_state st[2];
+			     v.t->camera_optimizer_state(frame_idx, &st[0], &st[1]);
+			     py::list out;
+			     for (const ngp_adam_state& a : st) {
+				     py::dict d;
+				     d["iter"] = a.iter;
+				     d["first_moment"] = std::vector<float>(a.first_moment, a.first_moment + 3);
+				     d["second_moment"] = std::vector<float>(a.second_moment, a.second_moment + 3);
+				     d["variable"] = std::vector<float>(a.variable, a.variable + 3);
+				     d["learning_rate"] = a.learning_rate;
+				     d["epsilon"] = a.epsilon;
+				     d["beta1"] = a.beta1;
+				     d["beta2"] = a.beta2;
+				     out.append(d);
+			     }
+			     return py::make_tuple(out[0], out[1]);
+		     },
+		     py::arg("frame_idx"))
 		.def_property_readonly("dataset", py::cpp_function([](NerfTrainingView& v) { return NerfDatasetView{v.t}; }, py::keep_alive<0, 1>()));
 
 	py::class_<NerfDatasetView>(m, "NerfDataset")

@@ -381,6 +381,7 @@ public:
 				check(ngp_nerf_trainer_buffers(m_nerf_trainer, &g, &b, &m), "ngp_nerf_trainer_buffers");
 				check(ngp_memcpy(g, kept_grid.data(), kept_grid.size() * 4, 1 /* host to device */), "ngp_memcpy");
 			}
+			push_camera_training();
 		}
 	}
 	uint64_t n_params() const { return m_model ? ngp_model_n_params(m_model) : 0; }
@@ -510,7 +511,7 @@ public:
 	void set_camera_to_training_view(uint32_t i) {
 		if (i >= m_nerf_images.size()) throw std::runtime_error("set_camera_to_training_view: no such training view");
 		const ngp_nerf_image& im = m_nerf_images[i];
-		std::memcpy(m_camera, im.xform, sizeof(m_camera));
+		training_view_xform(i, m_camera);  // m_nerf.training.transforms[i].start: the refined pose
 		const float res_axis = (float)(m_fov_axis == 0 ? im.width : im.height);
 		m_relative_focal_length[0] = im.focal_length[0] / res_axis;
 		m_relative_focal_length[1] = im.focal_length[1] / res_axis;
@@ -722,6 +723,66 @@ public:
 	void push_nerf_config() {
 		if (m_nerf_trainer) check(ngp_nerf_trainer_set_config(m_nerf_trainer, &m_nerf_cfg), "ngp_nerf_trainer_set_config");
 	}
+	// ---- camera pose refinement (Testbed::Nerf::Training, python_api.cu:618-653) -----------------------------
+	ngp_nerf_camera_training& camera_training() { return m_cam_training; }
+	void push_camera_training() {
+		if (m_nerf_trainer) check(ngp_nerf_trainer_set_camera_training(m_nerf_trainer, &m_cam_training), "ngp_nerf_trainer_set_camera_training");
+	}
+	// Training::transforms[i].start: the trainer's refined transform, or the dataset's before there is a trainer
+	void training_view_xform(uint32_t i, float out[12]) const {
+		if (i >= m_nerf_images.size()) throw std::runtime_error("no such training view");
+		if (m_nerf_trainer) check(ngp_nerf_trainer_camera_extrinsics(m_nerf_trainer, i, out), "ngp_nerf_trainer_camera_extrinsics");
+		else std::memcpy(out, m_nerf_images[i].xform, 12 * sizeof(float));
+	}
+	// NerfDataset::nerf_matrix_to_ngp (nerf_loader.h:120-140, non-mitsuba branch) and its inverse ngp_matrix_to_nerf
+	// (:142) with the dataset's scale and offset; m: [3 x 4] row-major, x: mat4x3 column-major
+	void nerf_matrix_to_ngp(const float m[12], float x[12]) const {
+		for (int c = 0; c < 4; ++c)
+			for (int k = 0; k < 3; ++k) {
+				float v = m[k * 4 + c];
+				if (c == 1 || c == 2) v = -v;
+				if (c == 3) v = v * m_dataset_scale + m_dataset_offset[k];
+				x[c * 3 + (k + 2) % 3] = v;  // cycle axes xyz <- yzx
+			}
+	}
+	void ngp_matrix_to_nerf(const float x[12], float m[12]) const {
+		for (int c = 0; c < 4; ++c)
+			for (int k = 0; k < 3; ++k) {
+				float v = x[c * 3 + (k + 2) % 3];
+				if (c == 1 || c == 2) v = -v;
+				if (c == 3) v = (v - m_dataset_offset[k]) / m_dataset_scale;
+				m[k * 4 + c] = v;
+			}
+	}
+	// get_camera_extrinsics (testbed_nerf.cu:2973-2978): [3 x 4] row-major, NeRF convention
+	void get_camera_extrinsics(int frame_idx, float m[12]) const {
+		if (frame_idx < 0 || (size_t)frame_idx >= m_nerf_images.size()) {  // mat4x3(1.0f)
+			for (int k = 0; k < 12; ++k) m[k] = k % 5 == 0 ? 1.f : 0.f;
+			return;
+		}
+		float x[12];
+		training_view_xform((uint32_t)frame_idx, x);
+		ngp_matrix_to_nerf(x, m);
+	}
+	// set_camera_extrinsics (:2896-2919): m [3 x 4] row-major; out-of-range frames are ignored, as there
+	void set_camera_extrinsics(int frame_idx, const float m[12], bool convert_to_ngp) {
+		if (frame_idx < 0 || (size_t)frame_idx >= m_nerf_images.size()) return;
+		require_nerf_trainer("set_camera_extrinsics");
+		float x[12];
+		if (convert_to_ngp) nerf_matrix_to_ngp(m, x);
+		else
+			for (int c = 0; c < 4; ++c)
+				for (int k = 0; k < 3; ++k) x[c * 3 + k] = m[k * 4 + c];
+		check(ngp_nerf_trainer_set_camera_extrinsics(m_nerf_trainer, (uint32_t)frame_idx, x), "ngp_nerf_trainer_set_camera_extrinsics");
+	}
+	void reset_camera_extrinsics() {
+		if (m_nerf_trainer) check(ngp_nerf_trainer_reset_camera_extrinsics(m_nerf_trainer), "ngp_nerf_trainer_reset_camera_extrinsics");
+	}
+	// cam_pos_offset[i] / cam_rot_offset[i]
+	void camera_optimizer_state(int frame_idx, ngp_adam_state* pos, ngp_adam_state* rot) {
+		require_nerf_trainer("camera_optimizer_state");
+		check(ngp_nerf_trainer_pose_optimizer_state(m_nerf_trainer, (uint32_t)frame_idx, pos, rot), "ngp_nerf_trainer_pose_optimizer_state");
+	}
 	ngp_image_config& image_config() { return m_image_cfg; }
 	const std::vector<ngp_nerf_image>& nerf_images() const { return m_nerf_images; }
 	float aabb_scale() const { return m_aabb_scale; }
@@ -833,6 +894,7 @@ private:
 	// NeRF
 	ngp_nerf_dataset* m_nerf_dataset = nullptr;
 	ngp_nerf_trainer* m_nerf_trainer = nullptr;
+	ngp_nerf_camera_training m_cam_training{0, 16, 1e-4f, 1e-3f};  // testbed.h:716-785 defaults
 	ngp_nerf_renderer* m_renderer = nullptr;
 	ngp_nerf_config m_nerf_cfg{};
 	std::vector<ngp_nerf_image> m_nerf_images;

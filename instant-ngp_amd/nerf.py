@@ -13,7 +13,7 @@ import os
 import numpy as np
 import torch
 
-from ._capi import NerfConfig, NerfErrorMapInfo, NerfImage, NerfStats, Rng, check, lib
+from ._capi import AdamState, NerfCameraTraining, NerfConfig, NerfErrorMapInfo, NerfImage, NerfStats, Rng, check, lib
 from .network import _ptr, _stream, wrap_device
 
 NERF_GRIDSIZE = 128
@@ -214,6 +214,105 @@ def grid_mean_and_bitfield(grid, max_cascade, stream=None):
     return mean, bf
 
 
+# ---- camera pose refinement ---------------------------------------------------------------------
+def camera_gradients(cfg, n_rays_total, n_images, samples, coords_compacted, coords_gradient, pos_gradient, rot_gradient,
+                     stream=None):
+    """compute_cam_gradient_train_nerf (testbed_nerf.cu:2014-2123), extrinsics only, without float atomics: the per-image
+    sums of the compacted batch's input gradient are ADDED onto pos_gradient / rot_gradient (float32 [n_images, 3]).
+    samples: the dict of generate_training_samples after compute_loss rewrote its numsteps (counters[0]: rays kept);
+    coords_gradient: float32 [B, stride >= 7] (rows 0..2 position, 4..6 direction)."""
+    for t in (coords_compacted, coords_gradient, pos_gradient, rot_gradient):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("camera_gradients: contiguous float32 tensors")
+    if pos_gradient.numel() != 3 * n_images or rot_gradient.numel() != 3 * n_images:
+        raise ValueError("camera_gradients: pos_gradient / rot_gradient are [n_images, 3]")
+    if coords_gradient.shape[0] < coords_compacted.shape[0] or coords_compacted.shape[1] != 7:
+        raise ValueError("camera_gradients: one gradient row per compacted coordinate")
+    check(lib().ngp_nerf_camera_gradients(
+        C.byref(cfg), _stream(stream), int(n_rays_total), int(n_images), _ptr(samples["counters"]),
+        _ptr(samples["ray_indices"]), _ptr(samples["rays"]), _ptr(samples["numsteps"]), _ptr(coords_compacted),
+        _ptr(coords_gradient), coords_gradient.shape[1], _ptr(pos_gradient), _ptr(rot_gradient)))
+
+
+def _adam_dict(s):
+    return {"iter": int(s.iter), "first_moment": np.array(s.first_moment[:], np.float32),
+            "second_moment": np.array(s.second_moment[:], np.float32), "variable": np.array(s.variable[:], np.float32),
+            "learning_rate": float(s.learning_rate), "epsilon": float(s.epsilon), "beta1": float(s.beta1),
+            "beta2": float(s.beta2)}
+
+
+def _adam_struct(d):
+    s = AdamState()
+    s.iter = int(d["iter"])
+    for k in ("first_moment", "second_moment", "variable"):
+        getattr(s, k)[:] = [float(v) for v in d[k]]
+    for k in ("learning_rate", "epsilon", "beta1", "beta2"):
+        setattr(s, k, float(d[k]))
+    return s
+
+
+def _f3(v):
+    return np.ascontiguousarray(np.asarray(v, np.float32).reshape(3))
+
+
+def pose_apply(xform12, rot_offset, pos_offset):
+    """Training::update_transforms for one image (testbed_nerf.cu:2998-3019). Host only."""
+    x = np.ascontiguousarray(np.asarray(xform12, np.float32).reshape(12))
+    r, p, out = _f3(rot_offset), _f3(pos_offset), np.zeros(12, np.float32)
+    check(lib().ngp_pose_apply(x.ctypes.data, r.ctypes.data, p.ctypes.data, out.ctypes.data))
+    return out
+
+
+def pose_compose_rotation(a, b):
+    """rotvec(rotmat(a) * rotmat(b)) (common_device.cuh:698-722). Host only."""
+    a, b, out = _f3(a), _f3(b), np.zeros(3, np.float32)
+    check(lib().ngp_pose_compose_rotation(a.ctypes.data, b.ctypes.data, out.ctypes.data))
+    return out
+
+
+class PoseOptimizer:
+    """n_images pairs of (AdamOptimizer<vec3>, RotationAdamOptimizer) (adam_optimizer.h:128-309) with the update rule
+    of Testbed::train_nerf (testbed_nerf.cu:3784-3805). Host only: no GPU call."""
+
+    def __init__(self, n_images):
+        h = C.c_void_p()
+        check(lib().ngp_pose_optimizer_create(int(n_images), C.byref(h)))
+        self.handle, self.n_images = h, int(n_images)
+
+    def step(self, pos_grad, rot_grad, n_steps_between=16, extrinsic_lr=1e-3, l2_reg=1e-4, network_lr=1e-2):
+        pg = np.ascontiguousarray(np.asarray(pos_grad, np.float32).reshape(self.n_images, 3))
+        rg = np.ascontiguousarray(np.asarray(rot_grad, np.float32).reshape(self.n_images, 3))
+        check(lib().ngp_pose_optimizer_step(self.handle, pg.ctypes.data, rg.ctypes.data, int(n_steps_between),
+                                            float(extrinsic_lr), float(l2_reg), float(network_lr)))
+
+    def get(self, i):
+        """(position state, rotation state) of camera i as dicts."""
+        p, r = AdamState(), AdamState()
+        check(lib().ngp_pose_optimizer_get(self.handle, int(i), C.byref(p), C.byref(r)))
+        return _adam_dict(p), _adam_dict(r)
+
+    def set_state(self, i, pos=None, rot=None):
+        ps = _adam_struct(pos) if pos is not None else None
+        rs = _adam_struct(rot) if rot is not None else None
+        check(lib().ngp_pose_optimizer_set_state(self.handle, int(i), C.byref(ps) if ps else None,
+                                                 C.byref(rs) if rs else None))
+
+    def reset(self):
+        check(lib().ngp_pose_optimizer_reset(self.handle))
+
+    def reset_one(self, i):
+        check(lib().ngp_pose_optimizer_reset_one(self.handle, int(i)))
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h:
+            try:
+                lib().ngp_pose_optimizer_destroy(h)
+            except Exception:
+                pass
+            self.handle = None
+
+
 # ---- Testbed-level training -------------------------------------------------------------------
 class NerfTraining:
     """Testbed::train for NeRF: density-grid update + one training step per call (testbed.cu:4285-4370)."""
@@ -319,6 +418,57 @@ class NerfTraining:
                 a = a.reshape(shapes[name])
             out[name] = a
         return out
+
+    # ---- camera pose refinement (nerf.training.optimize_extrinsics, python_api.cu:618-653) ----
+    def camera_training(self):
+        """The camera optimisation knobs as a dict (ngp_nerf_camera_training)."""
+        c = NerfCameraTraining()
+        check(lib().ngp_nerf_trainer_get_camera_training(self.handle, C.byref(c)))
+        return {k: getattr(c, k) for k, _ in NerfCameraTraining._fields_}
+
+    def set_camera_training(self, **kw):
+        """optimize_extrinsics (default 0), n_steps_between_cam_updates (16), extrinsic_l2_reg (1e-4),
+        extrinsic_learning_rate (1e-3); knobs not named keep their value. Single GPU only."""
+        c = NerfCameraTraining()
+        check(lib().ngp_nerf_trainer_get_camera_training(self.handle, C.byref(c)))
+        for k, v in kw.items():
+            if k not in dict(NerfCameraTraining._fields_):
+                raise TypeError(f"set_camera_training: unknown knob {k!r}")
+            setattr(c, k, int(v) if k in ("optimize_extrinsics", "n_steps_between_cam_updates") else float(v))
+        check(lib().ngp_nerf_trainer_set_camera_training(self.handle, C.byref(c)))
+
+    def camera_extrinsics(self, i):
+        """Image i's refined camera-to-world transform in NGP space: the 12 floats of the column-major mat4x3."""
+        out = np.zeros(12, np.float32)
+        check(lib().ngp_nerf_trainer_camera_extrinsics(self.handle, int(i), out.ctypes.data))
+        return out
+
+    def set_camera_extrinsics(self, i, m):
+        """Replace image i's transform (12 floats, NGP space, as nerf_matrix_to_ngp returns) in this trainer and reset
+        its optimiser state (set_camera_extrinsics, testbed_nerf.cu:2896-2919)."""
+        m = np.ascontiguousarray(np.asarray(m, np.float32).reshape(12))
+        check(lib().ngp_nerf_trainer_set_camera_extrinsics(self.handle, int(i), m.ctypes.data))
+
+    def reset_camera_extrinsics(self):
+        check(lib().ngp_nerf_trainer_reset_camera_extrinsics(self.handle))
+
+    def last_samples(self):
+        """The last step's sampler call (ngp_nerf_trainer_last_samples): {"rng", "n_rays", "max_samples"} and views of
+        the "ray_indices", "rays" and "counters" it wrote (valid until a later sampler runs: turn pipelining off)."""
+        rng, n, ms = Rng(), C.c_uint32(), C.c_uint32()
+        ri, ry, ct = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(lib().ngp_nerf_trainer_last_samples(self.handle, C.byref(rng), C.byref(n), C.byref(ms), C.byref(ri),
+                                                  C.byref(ry), C.byref(ct)))
+        return {"rng": rng, "n_rays": n.value, "max_samples": ms.value,
+                "ray_indices": wrap_device(ri.value, n.value, torch.float32).view(torch.int32),
+                "rays": wrap_device(ry.value, n.value * 6, torch.float32).view(n.value, 6),
+                "counters": wrap_device(ct.value, 2, torch.float32).view(torch.int32)}
+
+    def pose_optimizer_state(self, i):
+        """(cam_pos_offset[i], cam_rot_offset[i]) as dicts with the reference's member names."""
+        p, r = AdamState(), AdamState()
+        check(lib().ngp_nerf_trainer_pose_optimizer_state(self.handle, int(i), C.byref(p), C.byref(r)))
+        return _adam_dict(p), _adam_dict(r)
 
     def train_step(self, get_loss=True, stream=None):
         st = NerfStats()

@@ -370,10 +370,18 @@ class Trainer:
         """Collective: every rank gets the whole (sharded) optimizer state again (ngp_trainer_gather_shards)."""
         check(lib().ngp_trainer_gather_shards(self.handle, _stream(stream)))
 
-    def train_step(self, x, dL_doutput, loss_scale=128.0, stream=None):
+    def train_step(self, x, dL_doutput, loss_scale=128.0, stream=None, dL_dinput=None):
         """Engine extension: one eager step of what capture_training_step records (forward_backward with the
-        grid's update fused into the backward where possible, the exchange hook, optimizer_step)."""
+        grid's update fused into the backward where possible, the exchange hook, optimizer_step). dL_dinput: optional
+        fp32 [n x >= input_width] tensor (not x) that receives the input gradient with respect to the weights the
+        forward used, as Network.backward writes it."""
         _check_input(x, self.model.input_width())
+        if dL_dinput is not None:
+            assert dL_dinput.dtype == torch.float32 and dL_dinput.shape[0] == x.shape[0]
+            check(lib().ngp_trainer_train_step_input_gradient(
+                self.handle, _stream(stream), x.shape[0], _ptr(x), x.stride(0), _ptr(dL_doutput), dL_doutput.stride(0),
+                float(loss_scale), _ptr(dL_dinput), dL_dinput.stride(0)))
+            return
         check(lib().ngp_trainer_train_step(self.handle, _stream(stream), x.shape[0], _ptr(x), x.stride(0),
                                            _ptr(dL_doutput), dL_doutput.stride(0), float(loss_scale)))
 
