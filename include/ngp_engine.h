@@ -381,6 +381,49 @@ int ngp_nerf_compute_loss_error_map(const ngp_nerf_dataset* ds, const ngp_nerf_c
                                     const float* rays, uint32_t* numsteps, const float* coords_in, float* coords_out,
                                     void* dloss_doutput, float* loss, uint32_t* compacted_counter, const float* mean_density,
                                     float loss_scale, float* error_map, uint32_t em_width, uint32_t em_height);
+/* Error-driven ray sampling (Training::sample_focal_plane_proportional_to_error / sample_image_proportional_to_error,
+ * testbed.h:733-734; sample_cdf_2d and image_idx, testbed_nerf.cu:1232-1338). The CDFs of a closed error map window
+ * as the trainer builds them (ngp_nerf_trainer_error_map): DEVICE floats cdf_x_cond_y [n_images][height][width], cdf_y
+ * [n_images][height], cdf_img [n_images]. cdf_img NULL leaves the image choice uniform; cdf_x_cond_y NULL leaves the
+ * position in the image uniform (cdf_y, width and height are then not looked at; with it they are required). A ray's
+ * image is the first entry of cdf_img not below ld_random_val(global ray index, 0xdeadbeef); half of the positions
+ * (first pcg float below 0.5) stay uniform, the other half pick a cell by cdf_y then cdf_x_cond_y and a uniform point
+ * in it. img_pdf = pmf_img * n_images, uv_pdf = pmf_x * pmf_y * width * height, both 1 where the choice was uniform.
+ * Every search result is clamped to the last entry, so no load leaves its CDF row whatever the entries are. */
+typedef struct {
+	const float* cdf_x_cond_y;
+	const float* cdf_y;
+	const float* cdf_img;
+	uint32_t width, height;
+} ngp_nerf_error_cdfs;
+/* ngp_nerf_generate_training_samples with the rays' pixels drawn from cdfs. cdfs NULL, or with every pointer NULL:
+ * the same kernels and the same bytes as ngp_nerf_generate_training_samples. */
+int ngp_nerf_generate_training_samples_cdf(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream,
+                                           uint32_t n_rays, uint32_t ray_offset, uint32_t n_rays_total, ngp_rng rng,
+                                           uint32_t max_samples, const uint8_t* bitfield, uint32_t* ray_indices, float* rays,
+                                           uint32_t* numsteps, float* coords, uint32_t* counters,
+                                           const ngp_nerf_error_cdfs* cdfs);
+/* ngp_nerf_compute_loss_error_map (error_map nullable) for rays sampled with cdfs: every channel's loss is divided by
+ * img_pdf * uv_pdf before the mean (testbed_nerf.cu:1846), so loss[] and the error map deposit are; dL/doutput is not
+ * (the reference keeps that line commented out, :1858-1862: importance sampling is meant to reweight the loss). */
+int ngp_nerf_compute_loss_cdf(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
+                              uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples_compacted, const uint32_t* ray_counter,
+                              const void* network_output, const uint32_t* ray_indices, const float* rays, uint32_t* numsteps,
+                              const float* coords_in, float* coords_out, void* dloss_doutput, float* loss,
+                              uint32_t* compacted_counter, const float* mean_density, float loss_scale, float* error_map,
+                              uint32_t em_width, uint32_t em_height, const ngp_nerf_error_cdfs* cdfs);
+/* Engine extension (inspection): the training pixel of rays [ray_offset, ray_offset + n_rays) of a batch of
+ * n_rays_total, as the sampler and the loss pass draw it (one shared function): img [n_rays], uv [n_rays x 2] after
+ * snapping, pdf [n_rays x 2] = {img_pdf, uv_pdf}; device memory. */
+int ngp_nerf_training_pixels(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
+                             uint32_t ray_offset, uint32_t n_rays_total, ngp_rng rng, const ngp_nerf_error_cdfs* cdfs,
+                             uint32_t* img, float* uv, float* pdf);
+/* The same function compiled for the host: the CDFs and the outputs are HOST memory and no GPU call is made. A dataset
+ * lives on the device, so the images (of which width and height are read) come as the array a dataset is made from.
+ * Bit for bit what ngp_nerf_training_pixels writes. */
+int ngp_nerf_training_pixels_host(uint32_t n_images, const ngp_nerf_image* images, const ngp_nerf_config* cfg, uint32_t n_rays,
+                                  uint32_t ray_offset, uint32_t n_rays_total, ngp_rng rng, const ngp_nerf_error_cdfs* cdfs,
+                                  uint32_t* img, float* uv, float* pdf);
 /* tcnn fill_rollover / fill_rollover_and_rescale (testbed_nerf.cu:4061-4069); dtype 0 f32, 1 f16 */
 int ngp_nerf_fill_rollover(void* stream, uint32_t n_elements, uint32_t stride, const uint32_t* n_input, void* data,
                            int dtype, int rescale);
@@ -716,6 +759,15 @@ int ngp_nerf_trainer_reset_camera_extrinsics(ngp_nerf_trainer* t);
  * later sampler writes them: with pipelining on, that may be as soon as the step returns. Outputs nullable. */
 int ngp_nerf_trainer_last_samples(const ngp_nerf_trainer* t, ngp_rng* rng, uint32_t* n_rays, uint32_t* max_samples,
                                   const uint32_t** ray_indices, const float** rays, const uint32_t** counters);
+/* Training::sample_focal_plane_proportional_to_error / sample_image_proportional_to_error (both off by default, as in
+ * the reference). With a switch on, once the first error map window has closed (ngp_nerf_trainer_error_map: cdf_valid),
+ * every step's sampler and loss pass draw the rays' pixels from the CDFs of the last closed window; before that, and
+ * with both off, the step issues exactly the launches and writes exactly the bytes it would without this call. The
+ * step that closes a window prelaunches no sampler: the next step's rays come from the new CDFs. The map is summed
+ * with float atomics, whose last bits feed the CDFs: with a switch on, training is not reproducible from run to run.
+ * Discards a prelaunched sampler. Cannot be combined with optimize_extrinsics (either call fails, state unchanged). */
+int ngp_nerf_trainer_set_error_sampling(ngp_nerf_trainer* t, int focal_plane, int image);
+int ngp_nerf_trainer_get_error_sampling(const ngp_nerf_trainer* t, int* focal_plane, int* image);  /* each nullable */
 /* cam_pos_offset[i] / cam_rot_offset[i] (each nullable) */
 int ngp_nerf_trainer_pose_optimizer_state(const ngp_nerf_trainer* t, uint32_t i, ngp_adam_state* pos, ngp_adam_state* rot);
 

@@ -83,6 +83,12 @@ class NerfCameraTraining(C.Structure):
                 ("extrinsic_l2_reg", C.c_float), ("extrinsic_learning_rate", C.c_float)]
 
 
+class NerfErrorCdfs(C.Structure):
+    """ngp_nerf_error_cdfs: the error map's CDFs a sampler draws training pixels from (null pointer: uniform)."""
+    _fields_ = [("cdf_x_cond_y", C.c_void_p), ("cdf_y", C.c_void_p), ("cdf_img", C.c_void_p), ("width", C.c_uint32),
+                ("height", C.c_uint32)]
+
+
 class SdfRenderConfig(C.Structure):
     """ngp_sdf_render_config: Testbed::Sdf render knobs, sun / up / floor and BRDFParams (testbed.h:798-835, sdf.h:62-72)."""
     _fields_ = [
@@ -259,6 +265,15 @@ SIGNATURES = {
     "ngp_nerf_trainer_last_samples": (i32, [P, C.POINTER(Rng), C.POINTER(u32), C.POINTER(u32), C.POINTER(P), C.POINTER(P),
                                             C.POINTER(P)]),
     "ngp_nerf_trainer_pose_optimizer_state": (i32, [P, u32, C.POINTER(AdamState), C.POINTER(AdamState)]),
+    "ngp_nerf_generate_training_samples_cdf": (i32, [P, C.POINTER(NerfConfig), P, u32, u32, u32, Rng, u32, P, P, P, P, P,
+                                                     P, C.POINTER(NerfErrorCdfs)]),
+    "ngp_nerf_compute_loss_cdf": (i32, [P, C.POINTER(NerfConfig), P, u32, u32, Rng, u32, P, P, P, P, P, P, P, P, P, P, P,
+                                        f32, P, u32, u32, C.POINTER(NerfErrorCdfs)]),
+    "ngp_nerf_training_pixels": (i32, [P, C.POINTER(NerfConfig), P, u32, u32, u32, Rng, C.POINTER(NerfErrorCdfs), P, P, P]),
+    "ngp_nerf_training_pixels_host": (i32, [u32, C.POINTER(NerfImage), C.POINTER(NerfConfig), u32, u32, u32, Rng,
+                                            C.POINTER(NerfErrorCdfs), P, P, P]),
+    "ngp_nerf_trainer_set_error_sampling": (i32, [P, i32, i32]),
+    "ngp_nerf_trainer_get_error_sampling": (i32, [P, C.POINTER(i32), C.POINTER(i32)]),
 }
 
 

@@ -54,6 +54,17 @@ struct Dataset {
 	~Dataset();
 };
 
+// The error map's CDFs a sampler draws training pixels from (ngp_nerf_error_cdfs; nerf_pixel.h): device floats
+// cdf_x_cond_y [n_images][h][w], cdf_y [n_images][h], cdf_img [n_images]. cdf_img null: the image choice stays
+// uniform; cdf_x_cond_y null: the position in the image does. All null: the kernels' uniform instantiations run.
+struct ErrorCdfs {
+	const float* cdf_x_cond_y;
+	const float* cdf_y;
+	const float* cdf_img;
+	uint32_t w, h;
+	bool any() const { return cdf_img != nullptr || cdf_x_cond_y != nullptr; }
+};
+
 struct SampleArgs {
 	uint32_t n_rays, ray_offset, n_rays_total_for_image_idx;  // image_idx uses the global ray id
 	uint32_t max_samples;
@@ -64,6 +75,7 @@ struct SampleArgs {
 	uint32_t* numsteps;        // [n_rays x 2] {numsteps, base}
 	float* coords;             // [max_samples x 7] NerfCoordinate
 	uint32_t* counters;        // [2]: rays kept, numsteps total (incl. dropped)
+	ErrorCdfs cdfs;            // all null: uniform pixels
 };
 
 struct LossArgs {
@@ -100,7 +112,17 @@ struct LossArgs {
 	// as they are final: the host sizes the next step while pass 2, the rollover and the training pass run
 	volatile uint32_t* pub_host;
 	uint32_t pub_seq;
+	// the CDFs the rays' pixels were drawn from (the sampler's): pass 1 repeats the draw and divides the loss by its pdf
+	ErrorCdfs cdfs;
 };
+
+// Every ray's training pixel (nerf_pixel.h): img [n_rays], uv [n_rays x 2] after snapping, pdf [n_rays x 2] =
+// {img_pdf, uv_pdf}. The device form reads the dataset's cameras and device CDFs; the host form makes no GPU call
+// (cams: host cameras of which width and height are read, CDFs and outputs in host memory).
+void training_pixels(const Dataset& ds, const ngp_nerf_config& cfg, uint32_t n_rays, uint32_t ray_offset, uint32_t n_rays_total, Rng rng,
+                     const ErrorCdfs& cdfs, uint32_t* img, float* uv, float* pdf, hipStream_t s);
+void training_pixels_host(const Camera* cams, uint32_t n_images, const ngp_nerf_config& cfg, uint32_t n_rays, uint32_t ray_offset,
+                          uint32_t n_rays_total, Rng rng, const ErrorCdfs& cdfs, uint32_t* img, float* uv, float* pdf);
 
 // The kernels (each cites its reference kernel in nerf.hip).
 // cams (optional): the device cameras to trace instead of the dataset's (a trainer's refined poses)

@@ -15,6 +15,7 @@
 #include "profiler.h"
 #include "render_common.h"
 #include "rng.h"
+#include "nerf_pixel.h"
 
 namespace ngp {
 namespace nerf {
@@ -230,23 +231,7 @@ __device__ __forceinline__ Aabb cfg_aabb(const ngp_nerf_config& c) {
 	return Aabb{v3(c.aabb_min[0], c.aabb_min[1], c.aabb_min[2]), v3(c.aabb_max[0], c.aabb_max[1], c.aabb_max[2])};
 }
 
-// image_idx (testbed_nerf.cu:1317-1338), uniform branch
-__device__ __forceinline__ uint32_t image_idx(uint32_t base_idx, uint32_t n_rays, uint32_t n_images) {
-	return ((base_idx * n_images) / n_rays) % n_images;
-}
-
-// nerf_random_image_pos_training (:1292-1315) without error-map CDFs
-__device__ void random_image_pos(Rng& rng, uint32_t w, uint32_t h, bool snap, float* u, float* v) {
-	*u = pcg_float(rng);
-	*v = pcg_float(rng);
-	if (snap) {
-		int px = (int)(*u * (float)w), py = (int)(*v * (float)h);
-		px = px < 0 ? 0 : (px > (int)w - 1 ? (int)w - 1 : px);
-		py = py < 0 ? 0 : (py > (int)h - 1 ? (int)h - 1 : py);
-		*u = ((float)px + 0.5f) / (float)w;
-		*v = ((float)py + 0.5f) / (float)h;
-	}
-}
+// image_idx and nerf_random_image_pos_training (testbed_nerf.cu:1292-1338): training_pixel (nerf_pixel.h)
 
 __device__ __forceinline__ uint64_t pixel_index(float u, float v, uint32_t w, uint32_t h) {  // image_pos + pixel_idx
 	int px = (int)(u * (float)w), py = (int)(v * (float)h);
@@ -262,15 +247,16 @@ struct RaySetup {
 	float startt, cone;
 };
 
+// CDF: the ray's pixel comes from the error map's CDFs `e` (a separate instantiation: the uniform one carries none of it)
+template <bool CDF>
 __device__ RaySetup setup_ray(const Camera* cams, const uint32_t* pixels, uint32_t n_images, const ngp_nerf_config& cfg,
-                              uint32_t ig, uint32_t n_rays_div, Rng rng, const Cone& cone) {
+                              uint32_t ig, uint32_t n_rays_div, Rng rng, const Cone& cone, const ErrorCdfs& e) {
 	RaySetup r;
 	r.valid = false;
-	const uint32_t img = image_idx(ig, n_rays_div, n_images);
-	const Camera& cam = cams[img];
 	pcg_advance(rng, (uint64_t)ig * N_MAX_RANDOM_SAMPLES_PER_RAY);
-	float u, v;
-	random_image_pos(rng, cam.width, cam.height, cfg.snap_to_pixel_centers != 0, &u, &v);
+	const TrainPixel px = training_pixel<CDF>(cams, n_images, cfg.snap_to_pixel_centers != 0, e, ig, n_rays_div, rng);
+	const Camera& cam = cams[px.img];
+	const float u = px.u, v = px.v;
 	const uint32_t raw = pixels[cam.pixel_offset + pixel_index(u, v, cam.width, cam.height)];
 	if (raw == 0x00FF00FFu) return r;  // masked (read_rgba returns -1)
 	(void)pcg_float(rng);              // motionblur_time
@@ -633,7 +619,7 @@ extern "C" __attribute__((visibility("default"))) int ngp_debug_math_check(int w
 
 // generate_training_samples_nerf pass 1: count the occupied steps of ray i (lane L of its group), keep their t;
 // returns the count (uniform over the group).
-template <bool CONE0>
+template <bool CONE0, bool CDF>
 __device__ __forceinline__ uint32_t count_ray(const Camera* __restrict__ cams, const uint32_t* __restrict__ pixels, uint32_t n_images,
                                               const ngp_nerf_config& cfg, const SampleArgs& a, uint32_t* __restrict__ nsteps,
                                               float* __restrict__ tbuf, RayGeo* __restrict__ geo, const Cone& cone, uint32_t i,
@@ -641,7 +627,7 @@ __device__ __forceinline__ uint32_t count_ray(const Camera* __restrict__ cams, c
 	constexpr uint32_t RGk = sampler_rg<CONE0>();
 	if (!CONE0 && NGP_SAMPLER_PRIO) __builtin_amdgcn_s_setprio(NGP_SAMPLER_PRIO);
 	SAMPLER_STAT(const unsigned long long ck0 = sampler_clock();)
-	const RaySetup r = setup_ray(cams, pixels, n_images, cfg, i + a.ray_offset, a.n_rays_total_for_image_idx, a.rng, cone);
+	const RaySetup r = setup_ray<CDF>(cams, pixels, n_images, cfg, i + a.ray_offset, a.n_rays_total_for_image_idx, a.rng, cone, a.cdfs);
 	SAMPLER_STAT(const unsigned long long ck1 = sampler_clock(); unsigned long long ck2 = ck1, ck_g = 0, ck_o = 0, ck_q = 0;)
 	uint32_t j = 0;
 	if (r.valid) {
@@ -833,7 +819,7 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 // The count pass, and per wave the sum of its rays' counts and the number of its rays with samples (wsum[2 w],
 // wsum[2 w + 1]): the sampler's prefix sums over rays become a scan over waves (k_sample_bscan, ~2 K values at
 // the Lego stand-in's ~32 K rays) plus an in-wave prefix in k_sample_write, instead of a scan over the rays.
-template <bool CONE0>
+template <bool CONE0, bool CDF>
 __global__ void __launch_bounds__(256) k_sample_count(const Camera* __restrict__ cams, const uint32_t* __restrict__ pixels,
                                                       uint32_t n_images, const ngp_nerf_config cfg, SampleArgs a,
                                                       uint32_t* __restrict__ nsteps, float* __restrict__ tbuf,
@@ -843,7 +829,7 @@ __global__ void __launch_bounds__(256) k_sample_count(const Camera* __restrict__
 	const uint32_t i = gid / RGk, L = gid % RGk;
 	const bool live = i < a.n_rays;  // whole rows
 	uint32_t j = 0;
-	if (live) j = count_ray<CONE0>(cams, pixels, n_images, cfg, a, nsteps, tbuf, geo, cone, i, L);
+	if (live) j = count_ray<CONE0, CDF>(cams, pixels, n_images, cfg, a, nsteps, tbuf, geo, cone, i, L);
 	const bool head = live && L == 0;
 	const uint32_t sum = wave_sum(head ? j : 0u);
 	const uint32_t nz = (uint32_t)__popcll(__ballot(head && j > 0));
@@ -1103,12 +1089,10 @@ void sample_rays(const Dataset& ds, const ngp_nerf_config& cfg, const SampleArgs
 	const Cone cone = make_cone(cfg.cone_angle_constant);  // every ray's cone (setup_ray: r.cone)
 	{
 		ProfScope ps("sample_count", s);
-		if (cone0)
-			k_sample_count<true><<<blocks0, NGP_SAMPLER_BLOCK, 0, s>>>(cams, ds.d_pixels, ds.n_images, cfg, a, nsteps, tbuf, geo, cone,
-			                                                          wsum);
-		else
-			k_sample_count<false><<<blocks, NGP_SAMPLER_BLOCK, 0, s>>>(cams, ds.d_pixels, ds.n_images, cfg, a, nsteps, tbuf, geo, cone,
-			                                                           wsum);
+		// pixels from the error map's CDFs: the count pass's other instantiation (the write pass copies what it stored)
+		auto count = cone0 ? (a.cdfs.any() ? k_sample_count<true, true> : k_sample_count<true, false>)
+		                   : (a.cdfs.any() ? k_sample_count<false, true> : k_sample_count<false, false>);
+		count<<<cone0 ? blocks0 : blocks, NGP_SAMPLER_BLOCK, 0, s>>>(cams, ds.d_pixels, ds.n_images, cfg, a, nsteps, tbuf, geo, cone, wsum);
 		NGP_HIP(hipGetLastError());
 	}
 	NGP_CHECK(nw == (cone0 ? blocks0 : blocks) * (NGP_SAMPLER_BLOCK / 64) && 64 % rgk == 0, "sampler: count waves");
@@ -1147,6 +1131,7 @@ __device__ __forceinline__ V3 unwarp_pos(const float* c, const Aabb& b) {
 
 #define NGP_ROW_UNROLL16(M) M(0) M(1) M(2) M(3) M(4) M(5) M(6) M(7) M(8) M(9) M(10) M(11) M(12) M(13) M(14) M(15)
 
+template <bool CDF>
 __global__ void __launch_bounds__(256) k_loss_pass1(const Camera* __restrict__ cams, const uint32_t* __restrict__ pixels,
                                                     uint32_t n_images, const ngp_nerf_config cfg, LossArgs a,
                                                     uint32_t* __restrict__ craw, LossRay* __restrict__ lr) {
@@ -1172,10 +1157,10 @@ __global__ void __launch_bounds__(256) k_loss_pass1(const Camera* __restrict__ c
 	const uint32_t ray_idx = a.ray_indices[i];
 	Rng rng = a.rng;
 	pcg_advance(rng, (uint64_t)ray_idx * N_MAX_RANDOM_SAMPLES_PER_RAY);
-	const uint32_t img = image_idx(ray_idx, a.n_rays_total_for_image_idx, n_images);
+	const TrainPixel px = training_pixel<CDF>(cams, n_images, cfg.snap_to_pixel_centers != 0, a.cdfs, ray_idx, a.n_rays_total_for_image_idx, rng);
+	const uint32_t img = px.img;
 	const Camera& cam = cams[img];
-	float u, v;
-	random_image_pos(rng, cam.width, cam.height, cfg.snap_to_pixel_centers != 0, &u, &v);
+	const float u = px.u, v = px.v;
 	pcg_advance(rng, 1);  // motionblur_time
 	// The per-ray colour work (12 powf in the default configuration) is split over the row: lane ch < 3
 	// finishes colour channel ch with the reference's per-channel operations, and lane 0 gathers the
@@ -1288,6 +1273,11 @@ __global__ void __launch_bounds__(256) k_loss_pass1(const Camera* __restrict__ c
 	if (cn == numsteps) pred += t * bgc;
 	float lc, gc;
 	loss_channel(target, pred, cfg.loss_type, &lc, &gc);
+	// lg.loss /= img_pdf * uv_pdf (testbed_nerf.cu:1846): the reported loss and the error map deposit. The gradient is
+	// NOT divided: the reference leaves that line commented out on purpose (:1858-1862). Dividing it would make the
+	// loss estimate unbiased, the same optimisation with less variance; importance sampling is meant to change the
+	// weighting of the loss instead.
+	if (CDF) lc = lc / (px.img_pdf * px.uv_pdf);
 	const float l1 = row_bcast<1>(lc), l2 = row_bcast<2>(lc), g1 = row_bcast<1>(gc), g2 = row_bcast<2>(gc);
 	const float p1 = row_bcast<1>(pred), p2 = row_bcast<2>(pred);
 	if (L != 0) return;
@@ -1491,7 +1481,8 @@ void compute_loss(const Dataset& ds, const ngp_nerf_config& cfg, const LossArgs&
 		ProfScope ps("loss_pass1", s);
 		static_assert(256 / LG == 16, "k_loss_pass1's XCD-aware order assumes 16 rays per block");
 		const uint32_t b1 = NGP_LOSS_XCD ? 8 * div_round_up(a.n_rays, 128) : blocks;
-		k_loss_pass1<<<b1, 256, 0, s>>>(ds.d_cams, ds.d_pixels, ds.n_images, cfg, a, craw, lr);
+		auto pass1 = a.cdfs.any() ? k_loss_pass1<true> : k_loss_pass1<false>;
+		pass1<<<b1, 256, 0, s>>>(ds.d_cams, ds.d_pixels, ds.n_images, cfg, a, craw, lr);
 		NGP_HIP(hipGetLastError());
 	}
 	{
@@ -1508,6 +1499,39 @@ void compute_loss(const Dataset& ds, const ngp_nerf_config& cfg, const LossArgs&
 		k_loss_pass2<LG><<<blocks, 256, 0, s>>>(ds.d_cams, cfg, a, craw, gpre, lr);
 	}
 	NGP_HIP(hipGetLastError());
+}
+
+// Every ray's training pixel, as the sampler and loss pass 1 draw it (nerf_pixel.h): for inspection and tests
+__global__ void __launch_bounds__(256) k_training_pixels(const Camera* __restrict__ cams, uint32_t n_images, bool snap, ErrorCdfs e,
+                                                         uint32_t n_rays, uint32_t ray_offset, uint32_t n_rays_div, Rng rng,
+                                                         uint32_t* __restrict__ img, float* __restrict__ uv, float* __restrict__ pdf) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n_rays) return;
+	const uint32_t ig = i + ray_offset;
+	pcg_advance(rng, (uint64_t)ig * N_MAX_RANDOM_SAMPLES_PER_RAY);
+	const TrainPixel p = training_pixel<true>(cams, n_images, snap, e, ig, n_rays_div, rng);
+	img[i] = p.img;
+	uv[2 * (size_t)i] = p.u; uv[2 * (size_t)i + 1] = p.v;
+	pdf[2 * (size_t)i] = p.img_pdf; pdf[2 * (size_t)i + 1] = p.uv_pdf;
+}
+void training_pixels(const Dataset& ds, const ngp_nerf_config& cfg, uint32_t n_rays, uint32_t ray_offset, uint32_t n_rays_total, Rng rng,
+                     const ErrorCdfs& cdfs, uint32_t* img, float* uv, float* pdf, hipStream_t s) {
+	if (n_rays == 0) return;
+	k_training_pixels<<<div_round_up(n_rays, 256u), 256, 0, s>>>(ds.d_cams, ds.n_images, cfg.snap_to_pixel_centers != 0, cdfs, n_rays,
+	                                                             ray_offset, n_rays_total, rng, img, uv, pdf);
+	NGP_HIP(hipGetLastError());
+}
+void training_pixels_host(const Camera* cams, uint32_t n_images, const ngp_nerf_config& cfg, uint32_t n_rays, uint32_t ray_offset,
+                          uint32_t n_rays_total, Rng rng, const ErrorCdfs& cdfs, uint32_t* img, float* uv, float* pdf) {
+	for (uint32_t i = 0; i < n_rays; ++i) {
+		const uint32_t ig = i + ray_offset;
+		HostPcg32 r{rng.state, rng.inc};
+		r.advance((uint64_t)ig * N_MAX_RANDOM_SAMPLES_PER_RAY);
+		const TrainPixel p = training_pixel<true>(cams, n_images, cfg.snap_to_pixel_centers != 0, cdfs, ig, n_rays_total, r);
+		img[i] = p.img;
+		uv[2 * (size_t)i] = p.u; uv[2 * (size_t)i + 1] = p.v;
+		pdf[2 * (size_t)i] = p.img_pdf; pdf[2 * (size_t)i + 1] = p.uv_pdf;
+	}
 }
 
 // construct_cdf_2d (testbed_nerf.cu:2356-2382): one thread per (image, row), running sums along x

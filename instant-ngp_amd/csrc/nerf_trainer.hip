@@ -251,6 +251,21 @@ struct ngp_nerf_trainer {
 	uint32_t em_steps_since = 0, em_steps_between = 128;
 	bool em_cdf_valid = false;
 	std::vector<float> em_pmf_img;  // pmf_img_cpu
+	// Error-driven sampling (Training::sample_focal_plane_proportional_to_error / sample_image_proportional_to_error,
+	// testbed.h:733-734): once a window has closed, a step's sampler and its loss pass draw the rays' pixels from the
+	// CDFs of the last closed window (testbed_nerf.cu:3948-3949). Both off: the uniform kernels, nothing else changes.
+	bool sample_focal_plane_by_error = false, sample_image_by_error = false;
+	bool error_sampling() const { return sample_focal_plane_by_error || sample_image_by_error; }
+	ErrorCdfs sampling_cdfs() const {
+		ErrorCdfs e{};
+		if (!em_cdf_valid || !em_cdf_w || !em_cdf_h) return e;
+		if (sample_image_by_error) e.cdf_img = (const float*)em_cdf_img.p;
+		if (sample_focal_plane_by_error) {
+			e.cdf_x_cond_y = (const float*)em_cdf_x.p; e.cdf_y = (const float*)em_cdf_y.p;
+			e.w = em_cdf_w; e.h = em_cdf_h;
+		}
+		return e;
+	}
 };
 
 static hipStream_t S(void* s) { return (hipStream_t)s; }
@@ -385,14 +400,29 @@ int ngp_nerf_dataset_create(uint32_t n_images, const ngp_nerf_image* images, con
 
 void ngp_nerf_dataset_destroy(ngp_nerf_dataset* d) { delete d; }
 
-// ngp_nerf_generate_training_samples, optionally tracing `cams` instead of the dataset's cameras
+// ngp_nerf_error_cdfs -> ErrorCdfs (null: none). The position CDFs come as a pair with a resolution; without
+// cdf_x_cond_y the other two members are not looked at.
+static bool error_cdfs_arg(const ngp_nerf_error_cdfs* c, ErrorCdfs* out) {
+	*out = ErrorCdfs{};
+	if (!c) return true;
+	out->cdf_img = c->cdf_img;
+	if (c->cdf_x_cond_y) {
+		if (!c->cdf_y || c->width == 0 || c->height == 0) return false;
+		out->cdf_x_cond_y = c->cdf_x_cond_y; out->cdf_y = c->cdf_y; out->w = c->width; out->h = c->height;
+	}
+	return true;
+}
+
+// ngp_nerf_generate_training_samples, optionally tracing `cams` instead of the dataset's cameras and drawing the
+// rays' pixels from the error map's CDFs
 static int generate_training_samples(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
                                      uint32_t ray_offset, uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples,
                                      const uint8_t* bitfield, uint32_t* ray_indices, float* rays, uint32_t* numsteps,
-                                     float* coords, uint32_t* counters, const Camera* cams) {
+                                     float* coords, uint32_t* counters, const Camera* cams, const ErrorCdfs& cdfs = ErrorCdfs{}) {
 	if (!ds || !cfg || !bitfield || !ray_indices || !rays || !numsteps || !coords || !counters) return NGP_INVALID;
 	NERF_TRY({
 		SampleArgs a{};
+		a.cdfs = cdfs;
 		a.n_rays = n_rays; a.ray_offset = ray_offset; a.n_rays_total_for_image_idx = n_rays_total ? n_rays_total : n_rays;
 		a.max_samples = max_samples; a.rng = Rng{rng.state, rng.inc}; a.bitfield = bitfield;
 		a.ray_indices = ray_indices; a.rays = rays; a.numsteps = numsteps; a.coords = coords; a.counters = counters;
@@ -408,6 +438,39 @@ int ngp_nerf_generate_training_samples(const ngp_nerf_dataset* ds, const ngp_ner
 	return generate_training_samples(ds, cfg, stream, n_rays, ray_offset, n_rays_total, rng, max_samples, bitfield, ray_indices, rays,
 	                                 numsteps, coords, counters, nullptr);
 }
+int ngp_nerf_generate_training_samples_cdf(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
+                                           uint32_t ray_offset, uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples,
+                                           const uint8_t* bitfield, uint32_t* ray_indices, float* rays, uint32_t* numsteps,
+                                           float* coords, uint32_t* counters, const ngp_nerf_error_cdfs* cdfs) {
+	ErrorCdfs e;
+	if (!error_cdfs_arg(cdfs, &e)) return NGP_INVALID;
+	return generate_training_samples(ds, cfg, stream, n_rays, ray_offset, n_rays_total, rng, max_samples, bitfield, ray_indices, rays,
+	                                 numsteps, coords, counters, nullptr, e);
+}
+
+int ngp_nerf_training_pixels(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays, uint32_t ray_offset,
+                             uint32_t n_rays_total, ngp_rng rng, const ngp_nerf_error_cdfs* cdfs, uint32_t* img, float* uv, float* pdf) {
+	ErrorCdfs e;
+	if (!ds || !cfg || !img || !uv || !pdf || !error_cdfs_arg(cdfs, &e)) return NGP_INVALID;
+	NERF_TRY(training_pixels(ds->ds, *cfg, n_rays, ray_offset, n_rays_total ? n_rays_total : n_rays, Rng{rng.state, rng.inc}, e, img, uv,
+	                         pdf, S(stream)));
+}
+int ngp_nerf_training_pixels_host(uint32_t n_images, const ngp_nerf_image* images, const ngp_nerf_config* cfg, uint32_t n_rays,
+                                  uint32_t ray_offset, uint32_t n_rays_total, ngp_rng rng, const ngp_nerf_error_cdfs* cdfs,
+                                  uint32_t* img, float* uv, float* pdf) {
+	ErrorCdfs e;
+	if (!images || n_images == 0 || !cfg || !img || !uv || !pdf || !error_cdfs_arg(cdfs, &e)) return NGP_INVALID;
+	NERF_TRY({
+		std::vector<Camera> cams(n_images);
+		for (uint32_t i = 0; i < n_images; ++i) {
+			if (images[i].width == 0 || images[i].height == 0) return NGP_INVALID;
+			cams[i] = Camera{};
+			cams[i].width = images[i].width; cams[i].height = images[i].height;
+		}
+		training_pixels_host(cams.data(), n_images, *cfg, n_rays, ray_offset, n_rays_total ? n_rays_total : n_rays,
+		                     Rng{rng.state, rng.inc}, e, img, uv, pdf);
+	});
+}
 
 static int nerf_compute_loss(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
                              uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples_compacted, const uint32_t* ray_counter,
@@ -415,7 +478,8 @@ static int nerf_compute_loss(const ngp_nerf_dataset* ds, const ngp_nerf_config* 
                              uint32_t* numsteps, const float* coords_in, float* coords_out, void* dloss_doutput, float* loss,
                              uint32_t* compacted_counter, const float* mean_density, float loss_scale, bool zero_loss = false,
                              float* error_map = nullptr, uint32_t em_w = 0, uint32_t em_h = 0, float* state = nullptr,
-                             uint64_t state_cap = 0, volatile uint32_t* pub_host = nullptr, uint32_t pub_seq = 0);
+                             uint64_t state_cap = 0, volatile uint32_t* pub_host = nullptr, uint32_t pub_seq = 0,
+                             const ErrorCdfs& cdfs = ErrorCdfs{});
 
 int ngp_nerf_compute_loss(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
                           uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples_compacted, const uint32_t* ray_counter,
@@ -451,13 +515,27 @@ int ngp_nerf_compute_loss_state(const ngp_nerf_dataset* ds, const ngp_nerf_confi
 	                         loss_scale, false, nullptr, 0, 0, sample_state, state_capacity);
 }
 
+int ngp_nerf_compute_loss_cdf(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
+                              uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples_compacted, const uint32_t* ray_counter,
+                              const void* network_output, const uint32_t* ray_indices, const float* rays, uint32_t* numsteps,
+                              const float* coords_in, float* coords_out, void* dloss_doutput, float* loss,
+                              uint32_t* compacted_counter, const float* mean_density, float loss_scale, float* error_map,
+                              uint32_t em_width, uint32_t em_height, const ngp_nerf_error_cdfs* cdfs) {
+	ErrorCdfs e;
+	if (!error_cdfs_arg(cdfs, &e)) return NGP_INVALID;
+	if (error_map && (em_width < 2 || em_height < 2)) return NGP_INVALID;
+	return nerf_compute_loss(ds, cfg, stream, n_rays, n_rays_total, rng, max_samples_compacted, ray_counter, network_output, 16,
+	                         ray_indices, rays, numsteps, coords_in, coords_out, dloss_doutput, loss, compacted_counter, mean_density,
+	                         loss_scale, false, error_map, em_width, em_height, nullptr, 0, nullptr, 0, e);
+}
+
 static int nerf_compute_loss(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
                              uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples_compacted, const uint32_t* ray_counter,
                              const void* network_output, uint32_t out_stride, const uint32_t* ray_indices, const float* rays,
                              uint32_t* numsteps, const float* coords_in, float* coords_out, void* dloss_doutput, float* loss,
                              uint32_t* compacted_counter, const float* mean_density, float loss_scale, bool zero_loss,
                              float* error_map, uint32_t em_w, uint32_t em_h, float* state, uint64_t state_cap,
-                             volatile uint32_t* pub_host, uint32_t pub_seq) {
+                             volatile uint32_t* pub_host, uint32_t pub_seq, const ErrorCdfs& cdfs) {
 	if (!ds || !cfg || !ray_counter || !network_output || !numsteps || !coords_in || !coords_out || !dloss_doutput ||
 	    !compacted_counter || !mean_density)
 		return NGP_INVALID;
@@ -472,6 +550,7 @@ static int nerf_compute_loss(const ngp_nerf_dataset* ds, const ngp_nerf_config* 
 		a.error_map = error_map; a.em_w = em_w; a.em_h = em_h;
 		a.state = state; a.state_cap = state ? state_cap : 0;
 		a.pub_host = pub_host; a.pub_seq = pub_seq;
+		a.cdfs = cdfs;
 		NGP_CHECK(n_rays > 0 || !pub_host, "compute_loss: the counters are published by the scan, which needs rays");
 		if (n_rays == 0) { NGP_HIP(hipMemsetAsync(compacted_counter, 0, 4, S(stream))); return NGP_OK; }
 		static thread_local Buf tmp, tmpf;
@@ -598,6 +677,28 @@ static void cameras_quiesce(ngp_nerf_trainer* t) {
 	NGP_HIP(hipDeviceSynchronize());
 }
 
+// The per-image gradient sums rely on an image's rays being one contiguous run of the batch (k_cam_image_sum), which
+// the image CDF breaks, and the reference divides the ray gradients by uv_pdf: neither is implemented
+static const char* const ERROR_SAMPLING_VS_EXTRINSICS =
+	"optimize_extrinsics cannot be combined with sample_focal_plane_proportional_to_error / "
+	"sample_image_proportional_to_error: turn one of them off first";
+
+int ngp_nerf_trainer_set_error_sampling(ngp_nerf_trainer* t, int focal_plane, int image) {
+	if (!t) return NGP_INVALID;
+	NERF_TRY({
+		NGP_CHECK(!(focal_plane || image) || !t->cam.optimize_extrinsics, ERROR_SAMPLING_VS_EXTRINSICS);
+		t->drain();  // a prelaunched sampler drew its pixels under the old switches
+		t->sample_focal_plane_by_error = focal_plane != 0;
+		t->sample_image_by_error = image != 0;
+	});
+}
+int ngp_nerf_trainer_get_error_sampling(const ngp_nerf_trainer* t, int* focal_plane, int* image) {
+	if (!t) return NGP_INVALID;
+	if (focal_plane) *focal_plane = t->sample_focal_plane_by_error ? 1 : 0;
+	if (image) *image = t->sample_image_by_error ? 1 : 0;
+	return NGP_OK;
+}
+
 int ngp_nerf_trainer_get_camera_training(const ngp_nerf_trainer* t, ngp_nerf_camera_training* out) {
 	if (!t || !out) return NGP_INVALID;
 	*out = t->cam;
@@ -611,6 +712,7 @@ int ngp_nerf_trainer_set_camera_training(ngp_nerf_trainer* t, const ngp_nerf_cam
 		NGP_CHECK(!c->optimize_extrinsics || !t->dp(),
 		          "camera pose refinement is single-GPU: the per-image gradient sums of a data-parallel trainer would need "
 		          "their own all-reduce");
+		NGP_CHECK(!c->optimize_extrinsics || !t->error_sampling(), ERROR_SAMPLING_VS_EXTRINSICS);
 		const bool toggled = (c->optimize_extrinsics != 0) != (t->cam.optimize_extrinsics != 0);
 		if (toggled) {
 			// the training pass is re-captured with (or without) the input gradient; a prelaunched sampler was
@@ -958,7 +1060,7 @@ static void launch_sampler(ngp_nerf_trainer* t, const SamplePlan& p, hipStream_t
 	ProfScope ps("nerf_sample", s);
 	const ngp_rng rng{t->rng.state, t->rng.inc};
 	check_rc(generate_training_samples(t->data, &t->cfg, s, p.Rl, p.r_lo, p.R, rng, p.max_inference, (const uint8_t*)t->bitfield.p,
-	                                   p.ray_indices, p.rays, p.numsteps, p.coords, p.ctr, t->d_cams));
+	                                   p.ray_indices, p.rays, p.numsteps, p.coords, p.ctr, t->d_cams, t->sampling_cdfs()));
 }
 static bool density_grid_update_due(uint32_t step) {
 	const uint32_t skip = std::min(std::max(step / 16u, 1u), 16u);
@@ -985,11 +1087,12 @@ static float* error_map_window(ngp_nerf_trainer* t, hipStream_t s) {
 // After the step (testbed_nerf.cu:3700-3748): when the window is full, the CDFs of the map
 // (construct_cdf_2d/1d on the stream; with data parallelism the ranks' maps are summed first), the
 // host pass over the per-image totals, then a 1.5x longer window.
-static void error_map_step_done(ngp_nerf_trainer* t, hipStream_t s) {
+// Returns whether it rebuilt the CDFs.
+static bool error_map_step_done(ngp_nerf_trainer* t, hipStream_t s) {
 	const Dataset& ds = t->data->ds;
-	if (ds.n_images == 0 || ds.cams.empty()) return;
+	if (ds.n_images == 0 || ds.cams.empty()) return false;
 	t->em_steps_since += 1;
-	if (t->em_steps_since < t->em_steps_between) return;
+	if (t->em_steps_since < t->em_steps_between) return false;
 	t->em_cdf_w = t->em_w;
 	t->em_cdf_h = t->em_h;
 	const uint32_t n_img = ds.n_images, w = t->em_cdf_w, h = t->em_cdf_h;
@@ -1019,6 +1122,7 @@ static void error_map_step_done(ngp_nerf_trainer* t, hipStream_t s) {
 	t->em_steps_since = 0;
 	t->em_cdf_valid = true;
 	t->em_steps_between = (uint32_t)(t->em_steps_between * 1.5f);
+	return true;
 }
 
 int ngp_nerf_trainer_error_map(ngp_nerf_trainer* t, int which, float* out, uint64_t cap, ngp_nerf_error_map_info* info) {
@@ -1112,6 +1216,7 @@ struct Step {
 	bool cam = false;           // camera pose refinement: the training pass also writes dL/dinput
 	float* dinput = nullptr;    // [Bl x 7]
 	bool cam_updated = false;   // this step ended with a pose update (step_camera_update)
+	bool em_closed = false;     // this step closed an error map window: the CDFs were rebuilt (error_map_step_done)
 };
 
 // training_prep_nerf (a prelaunched sampler implies no update was due at this step)
@@ -1191,7 +1296,7 @@ static void step_loss_and_publish(ngp_nerf_trainer* t, hipStream_t s, const Step
 		check_rc(nerf_compute_loss(t->data, &t->cfg, s, Rl, R, c.rng, Bl, ctr, c.mlp_out, 4, sp.ray_indices, sp.rays, sp.numsteps,
 		                           sp.coords, c.coords_c, c.dloss, c.loss, ctr + 2, (const float*)t->mean.p,
 		                           c.dp ? loss_scale_local : 128.0f, true, error_map, t->em_w, t->em_h, lstate, sp.max_samples,
-		                           c.early_pub ? t->host_ctr : nullptr, pub_seq));
+		                           c.early_pub ? t->host_ctr : nullptr, pub_seq, t->sampling_cdfs()));
 	}
 	if (!c.dp) {
 		// single GPU: the rollover launch (fill_rollover_and_rescale + fill_rollover) also publishes the counters
@@ -1330,8 +1435,12 @@ static float step_read_counters(ngp_nerf_trainer* t, hipStream_t s, const Step& 
 
 // next step's sampler, concurrent with this step's training pass (no density-grid update due first)
 static void step_prelaunch_sampler(ngp_nerf_trainer* t, const Step& c) {
-	// (nor a pose update: that step's cameras are uploaded on the step's stream, where the next sampler then runs)
-	if (!c.can_pipeline || t->measured_batch_size == 0 || density_grid_update_due(t->training_step) || c.cam_updated) return;
+	// (nor a pose update: that step's cameras are uploaded on the step's stream, where the next sampler then runs; nor,
+	// with error-driven sampling, a rebuild of the CDFs the sampler reads, possibly into reallocated buffers: the
+	// next step launches its sampler itself, on the stream that rebuilt them)
+	if (!c.can_pipeline || t->measured_batch_size == 0 || density_grid_update_due(t->training_step) || c.cam_updated ||
+	    (c.em_closed && t->error_sampling()))
+		return;
 	const SamplePlan np = sample_plan(t);
 	// early(): the sampler writes the other sample set, which the step before last read (complete: this step's
 	// counters are published), so it waits on nothing
@@ -1373,7 +1482,7 @@ int ngp_nerf_train_step(ngp_nerf_trainer* t, void* stream, int get_loss, ngp_ner
 		++t->training_step;
 		const float loss_scalar = step_read_counters(t, s, c);
 		step_camera_update(t, s, c);
-		error_map_step_done(t, s);
+		c.em_closed = error_map_step_done(t, s);
 		step_prelaunch_sampler(t, c);
 		step_pregenerate_grid_samples(t, c);
 		if (st) {

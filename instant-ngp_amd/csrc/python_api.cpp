@@ -369,8 +369,16 @@ PYBIND11_MODULE(pyngp, m) {
 		              [](NerfTrainingView& v, bool x) {
 			              const uint32_t was = v.t->camera_training().optimize_extrinsics;
 			              v.t->camera_training().optimize_extrinsics = x ? 1u : 0u;
-			              try { v.t->push_camera_training(); } catch (...) { v.t->camera_training().optimize_extrinsics = was; throw; }
+			              try {
+				              v.t->check_error_sampling_vs_extrinsics();
+				              v.t->push_camera_training();
+			              } catch (...) { v.t->camera_training().optimize_extrinsics = was; throw; }
 		              })
+		// error-driven sampling (python_api.cu:624-625); not reproducible from run to run while on
+		.def_property("sample_focal_plane_proportional_to_error", [](NerfTrainingView& v) { return v.t->sample_focal_plane_by_error(); },
+		              [](NerfTrainingView& v, bool x) { v.t->set_error_sampling(x, v.t->sample_image_by_error()); })
+		.def_property("sample_image_proportional_to_error", [](NerfTrainingView& v) { return v.t->sample_image_by_error(); },
+		              [](NerfTrainingView& v, bool x) { v.t->set_error_sampling(v.t->sample_focal_plane_by_error(), x); })
 		.def_property("n_steps_between_cam_updates", [](NerfTrainingView& v) { return v.t->camera_training().n_steps_between_cam_updates; },
 		              [](NerfTrainingView& v, uint32_t x) {
 			              if (x == 0) throw std::runtime_error("n_steps_between_cam_updates: at least 1");

@@ -34,8 +34,8 @@ __device__ void aabb_ray_intersect(const Aabb& b, V3 pos, V3 dir, float* out_min
 	*out_min = tmin; *out_max = tmax;
 }
 
-// random_val.cuh:162-291 (Burley 2019 scrambled Sobol)
-__device__ uint32_t sobol_dim(uint32_t index, uint32_t dim) {
+// random_val.cuh:162-291 (Burley 2019 scrambled Sobol); ld_random_val also runs on the host (nerf_pixel.h)
+__host__ __device__ inline uint32_t sobol_dim(uint32_t index, uint32_t dim) {
 	// direction numbers of dims 0 and 1 (random_val.cuh:163-181)
 	uint32_t X = 0;
 	if (dim == 0) {
@@ -52,9 +52,9 @@ __device__ uint32_t sobol_dim(uint32_t index, uint32_t dim) {
 	}
 	return X;
 }
-__device__ __forceinline__ uint32_t hash_combine(uint32_t seed, uint32_t v) { return seed ^ (v + (seed << 6) + (seed >> 2)); }
-__device__ __forceinline__ uint32_t reverse_bits32(uint32_t x) { return __builtin_bitreverse32(x); }
-__device__ __forceinline__ uint32_t laine_karras(uint32_t x, uint32_t seed) {
+__host__ __device__ __forceinline__ uint32_t hash_combine(uint32_t seed, uint32_t v) { return seed ^ (v + (seed << 6) + (seed >> 2)); }
+__host__ __device__ __forceinline__ uint32_t reverse_bits32(uint32_t x) { return __builtin_bitreverse32(x); }
+__host__ __device__ __forceinline__ uint32_t laine_karras(uint32_t x, uint32_t seed) {
 	x += seed;
 	x ^= x * 0x6c50b47cu;
 	x ^= x * 0xb82f1e52u;
@@ -62,8 +62,8 @@ __device__ __forceinline__ uint32_t laine_karras(uint32_t x, uint32_t seed) {
 	x ^= x * 0x8d22f6e6u;
 	return x;
 }
-__device__ __forceinline__ uint32_t nus_base2(uint32_t x, uint32_t seed) { return reverse_bits32(laine_karras(reverse_bits32(x), seed)); }
-__device__ float ld_random_val(uint32_t index, uint32_t seed, uint32_t dim = 0) {
+__host__ __device__ __forceinline__ uint32_t nus_base2(uint32_t x, uint32_t seed) { return reverse_bits32(laine_karras(reverse_bits32(x), seed)); }
+__host__ __device__ inline float ld_random_val(uint32_t index, uint32_t seed, uint32_t dim = 0) {
 	const float S = (float)(1.0 / 4294967296.0);
 	index = nus_base2(index, seed);
 	return (float)nus_base2(sobol_dim(index, dim), hash_combine(seed, dim)) * S;

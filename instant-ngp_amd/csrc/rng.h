@@ -8,7 +8,7 @@ namespace ngp {
 struct Pcg32Dev { uint64_t state, inc; };
 
 template <typename R>
-__device__ __forceinline__ uint32_t pcg_next(R& r) {
+__host__ __device__ __forceinline__ uint32_t pcg_next(R& r) {
 	const uint64_t old = r.state;
 	r.state = old * 0x5851f42d4c957f2dULL + r.inc;
 	const uint32_t xs = (uint32_t)(((old >> 18u) ^ old) >> 27u), rot = (uint32_t)(old >> 59u);

@@ -382,6 +382,7 @@ public:
 				check(ngp_memcpy(g, kept_grid.data(), kept_grid.size() * 4, 1 /* host to device */), "ngp_memcpy");
 			}
 			push_camera_training();
+			push_error_sampling();
 		}
 	}
 	uint64_t n_params() const { return m_model ? ngp_model_n_params(m_model) : 0; }
@@ -728,6 +729,34 @@ public:
 	void push_camera_training() {
 		if (m_nerf_trainer) check(ngp_nerf_trainer_set_camera_training(m_nerf_trainer, &m_cam_training), "ngp_nerf_trainer_set_camera_training");
 	}
+	// ---- error-driven sampling (sample_focal_plane_proportional_to_error / sample_image_proportional_to_error,
+	// python_api.cu:624-625): kept here until there is a trainer, pushed to a live one
+	bool sample_focal_plane_by_error() const { return m_sample_focal_plane_by_error; }
+	bool sample_image_by_error() const { return m_sample_image_by_error; }
+	void set_error_sampling(bool focal_plane, bool image) {
+		const bool was_f = m_sample_focal_plane_by_error, was_i = m_sample_image_by_error;
+		m_sample_focal_plane_by_error = focal_plane;
+		m_sample_image_by_error = image;
+		try {
+			check_error_sampling_vs_extrinsics();
+			push_error_sampling();
+		} catch (...) {
+			m_sample_focal_plane_by_error = was_f;
+			m_sample_image_by_error = was_i;
+			throw;
+		}
+	}
+	void push_error_sampling() {
+		if (m_nerf_trainer)
+			check(ngp_nerf_trainer_set_error_sampling(m_nerf_trainer, m_sample_focal_plane_by_error, m_sample_image_by_error),
+			      "ngp_nerf_trainer_set_error_sampling");
+	}
+	// the trainer refuses the pair; refused here as well, so that it cannot build up before there is a trainer
+	void check_error_sampling_vs_extrinsics() const {
+		if (m_cam_training.optimize_extrinsics && (m_sample_focal_plane_by_error || m_sample_image_by_error))
+			throw std::runtime_error("optimize_extrinsics cannot be combined with sample_focal_plane_proportional_to_error / "
+			                         "sample_image_proportional_to_error: turn one of them off first");
+	}
 	// Training::transforms[i].start: the trainer's refined transform, or the dataset's before there is a trainer
 	void training_view_xform(uint32_t i, float out[12]) const {
 		if (i >= m_nerf_images.size()) throw std::runtime_error("no such training view");
@@ -895,6 +924,7 @@ private:
 	ngp_nerf_dataset* m_nerf_dataset = nullptr;
 	ngp_nerf_trainer* m_nerf_trainer = nullptr;
 	ngp_nerf_camera_training m_cam_training{0, 16, 1e-4f, 1e-3f};  // testbed.h:716-785 defaults
+	bool m_sample_focal_plane_by_error = false, m_sample_image_by_error = false;  // testbed.h:733-734
 	ngp_nerf_renderer* m_renderer = nullptr;
 	ngp_nerf_config m_nerf_cfg{};
 	std::vector<ngp_nerf_image> m_nerf_images;

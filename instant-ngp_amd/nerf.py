@@ -13,7 +13,8 @@ import os
 import numpy as np
 import torch
 
-from ._capi import AdamState, NerfCameraTraining, NerfConfig, NerfErrorMapInfo, NerfImage, NerfStats, Rng, check, lib
+from ._capi import (AdamState, NerfCameraTraining, NerfConfig, NerfErrorCdfs, NerfErrorMapInfo, NerfImage, NerfStats, Rng, check,
+                    lib)
 from .network import _ptr, _stream, wrap_device
 
 NERF_GRIDSIZE = 128
@@ -116,9 +117,45 @@ class NerfDataset:
 
 
 # ---- kernel-level entry points ------------------------------------------------------------------
+def _error_cdfs(cdfs, device, n_images):
+    """ngp_nerf_error_cdfs from a dict with any of "cdf_x_cond_y" [n_images, h, w], "cdf_y" [n_images, h] and "cdf_img"
+    [n_images] (other keys ignored, so NerfTraining.error_map()'s dict can be passed as it is): float32 numpy arrays
+    or tensors, copied to `device` (None: kept on the host, for training_pixels(host=True)). A missing, None or empty
+    entry is a null pointer; a first dimension other than n_images is refused (the kernels index by image). Returns
+    (struct or None, the arrays it points into)."""
+    if cdfs is None:
+        return None, ()
+    keep, e = [], NerfErrorCdfs()
+
+    def one(name):
+        a = cdfs.get(name)
+        if a is None or (a.numel() if torch.is_tensor(a) else np.asarray(a).size) == 0:
+            return None
+        if device is None:
+            a = np.ascontiguousarray(a.cpu().numpy() if torch.is_tensor(a) else a, dtype=np.float32)
+            keep.append(a)
+            return a, a.ctypes.data
+        a = torch.as_tensor(a, dtype=torch.float32).to(device).contiguous()
+        keep.append(a)
+        return a, a.data_ptr()
+
+    x, img = one("cdf_x_cond_y"), one("cdf_img")
+    if x is not None:
+        y = one("cdf_y")
+        if y is None or x[0].ndim != 3 or tuple(y[0].shape) != tuple(x[0].shape[:2]) or x[0].shape[0] != n_images:
+            raise ValueError("cdfs: cdf_x_cond_y [n_images, h, w] needs cdf_y [n_images, h]")
+        e.cdf_x_cond_y, e.cdf_y, e.width, e.height = x[1], y[1], x[0].shape[2], x[0].shape[1]
+    if img is not None:
+        if tuple(img[0].shape) != (n_images,):
+            raise ValueError("cdfs: cdf_img [n_images]")
+        e.cdf_img = img[1]
+    return e, keep
+
+
 def generate_training_samples(ds, cfg, n_rays, rng, max_samples, bitfield, ray_offset=0, n_rays_total=None,
-                              stream=None):
-    """generate_training_samples_nerf (testbed_nerf.cu:1382-1658)."""
+                              stream=None, cdfs=None):
+    """generate_training_samples_nerf (testbed_nerf.cu:1382-1658). cdfs: draw the rays' pixels from the error map's
+    CDFs (a dict, see _error_cdfs; ngp_nerf_generate_training_samples_cdf)."""
     dev = bitfield.device
     out = {
         "ray_indices": torch.zeros(n_rays, dtype=torch.int32, device=dev),
@@ -127,21 +164,56 @@ def generate_training_samples(ds, cfg, n_rays, rng, max_samples, bitfield, ray_o
         "coords": torch.zeros((max_samples, 7), dtype=torch.float32, device=dev),
         "counters": torch.zeros(2, dtype=torch.int32, device=dev),
     }
-    check(lib().ngp_nerf_generate_training_samples(
-        ds.handle, C.byref(cfg), _stream(stream), n_rays, ray_offset, n_rays_total or n_rays, rng, max_samples,
-        _ptr(bitfield), _ptr(out["ray_indices"]), _ptr(out["rays"]), _ptr(out["numsteps"]), _ptr(out["coords"]),
-        _ptr(out["counters"])))
+    args = (ds.handle, C.byref(cfg), _stream(stream), n_rays, ray_offset, n_rays_total or n_rays, rng, max_samples,
+            _ptr(bitfield), _ptr(out["ray_indices"]), _ptr(out["rays"]), _ptr(out["numsteps"]), _ptr(out["coords"]),
+            _ptr(out["counters"]))
+    if cdfs is None:
+        check(lib().ngp_nerf_generate_training_samples(*args))
+    else:
+        e, keep = _error_cdfs(cdfs, dev, len(ds))
+        check(lib().ngp_nerf_generate_training_samples_cdf(*args, C.byref(e)))
+        torch.cuda.synchronize(dev)  # the kernels read `keep`
+    return out
+
+
+def training_pixels(ds, cfg, n_rays, rng, cdfs=None, ray_offset=0, n_rays_total=None, host=False, stream=None):
+    """The training pixel of rays [ray_offset, ray_offset + n_rays) of a batch of n_rays_total, as the sampler and the
+    loss pass draw it: {"img" [n], "uv" [n, 2] after snapping, "pdf" [n, 2] = (img_pdf, uv_pdf)}. Device tensors from
+    ngp_nerf_training_pixels; host=True: numpy arrays from ngp_nerf_training_pixels_host, the same function compiled
+    for the host (no GPU call; ds may then be a list of NerfImage instead of a NerfDataset)."""
+    if host:
+        images = list(ds.images if isinstance(ds, NerfDataset) else ds)
+        arr = (NerfImage * len(images))(*images)
+        e, keep = _error_cdfs(cdfs, None, len(images))
+        out = {"img": np.zeros(n_rays, np.uint32), "uv": np.zeros((n_rays, 2), np.float32),
+               "pdf": np.zeros((n_rays, 2), np.float32)}
+        check(lib().ngp_nerf_training_pixels_host(len(images), arr, C.byref(cfg), n_rays, ray_offset, n_rays_total or n_rays,
+                                                  rng, C.byref(e) if e is not None else None, out["img"].ctypes.data,
+                                                  out["uv"].ctypes.data, out["pdf"].ctypes.data))
+        del keep
+        return out
+    dev = torch.device("cuda")
+    e, keep = _error_cdfs(cdfs, dev, len(ds))
+    out = {"img": torch.zeros(n_rays, dtype=torch.int32, device=dev),
+           "uv": torch.zeros((n_rays, 2), dtype=torch.float32, device=dev),
+           "pdf": torch.zeros((n_rays, 2), dtype=torch.float32, device=dev)}
+    check(lib().ngp_nerf_training_pixels(ds.handle, C.byref(cfg), _stream(stream), n_rays, ray_offset, n_rays_total or n_rays,
+                                         rng, C.byref(e) if e is not None else None, _ptr(out["img"]), _ptr(out["uv"]),
+                                         _ptr(out["pdf"])))
+    torch.cuda.synchronize(dev)  # the kernel reads `keep`
     return out
 
 
 def compute_loss(ds, cfg, n_rays, rng, max_compacted, samples, network_output, mean_density, loss_scale=128.0,
-                 n_rays_total=None, stream=None, error_map=None, keep_state=False, state_capacity=None):
+                 n_rays_total=None, stream=None, error_map=None, keep_state=False, state_capacity=None, cdfs=None):
     """compute_loss_kernel_train_nerf (testbed_nerf.cu:1660-2012). `samples` is the dict returned by
     generate_training_samples (its numsteps is rewritten to the compacted {n, base}). error_map: a
     float32 device tensor [n_images, h, w] the compacted rays' losses are added into (:1869-1899).
     keep_state: pass 1 keeps each composited sample's state for pass 2 (ngp_nerf_compute_loss_state, the
     training step's form; same outputs bit for bit). state_capacity: samples the kept state holds (default: every
-    sample slot); rays reaching past it are composited again by pass 2, with the same result."""
+    sample slot); rays reaching past it are composited again by pass 2, with the same result. cdfs: the CDFs the
+    samples' pixels were drawn from (generate_training_samples(cdfs=)): loss and the error map deposit are divided by
+    the pixels' pdf, dL/doutput is not (ngp_nerf_compute_loss_cdf; that entry point has no keep_state form)."""
     dev = network_output.device
     # the kernel reads one output row per sample; samples never exceed the sampler's coords buffer
     if network_output.shape[0] < samples["coords"].shape[0]:
@@ -157,7 +229,16 @@ def compute_loss(ds, cfg, n_rays, rng, max_compacted, samples, network_output, m
             _ptr(samples["counters"]), _ptr(network_output), _ptr(samples["ray_indices"]), _ptr(samples["rays"]),
             _ptr(samples["numsteps"]), _ptr(samples["coords"]), _ptr(out["coords_compacted"]), _ptr(out["dloss_doutput"]),
             _ptr(out["loss"]), _ptr(out["compacted_counter"]), _ptr(mean_density), float(loss_scale))
-    if keep_state:
+    if error_map is not None and (error_map.dtype != torch.float32 or error_map.dim() != 3 or not error_map.is_contiguous()):
+        raise ValueError("error_map: a contiguous float32 tensor [n_images, h, w]")
+    if cdfs is not None:
+        if keep_state:
+            raise ValueError("cdfs: without keep_state (the C-ABI form has no sample-state argument)")
+        e, keep = _error_cdfs(cdfs, dev, len(ds))
+        em = (_ptr(error_map), error_map.shape[2], error_map.shape[1]) if error_map is not None else (None, 0, 0)
+        check(lib().ngp_nerf_compute_loss_cdf(*args, *em, C.byref(e)))
+        torch.cuda.synchronize(dev)  # the kernels read `keep`
+    elif keep_state:
         if error_map is not None:
             raise ValueError("keep_state: without error_map (the C-ABI form has no error-map argument)")
         cap = samples["coords"].shape[0] if state_capacity is None else int(state_capacity)
@@ -166,8 +247,6 @@ def compute_loss(ds, cfg, n_rays, rng, max_compacted, samples, network_output, m
     elif error_map is None:
         check(lib().ngp_nerf_compute_loss(*args))
     else:
-        if error_map.dtype != torch.float32 or error_map.dim() != 3 or not error_map.is_contiguous():
-            raise ValueError("error_map: a contiguous float32 tensor [n_images, h, w]")
         check(lib().ngp_nerf_compute_loss_error_map(*args, _ptr(error_map), error_map.shape[2], error_map.shape[1]))
     return out
 
@@ -451,6 +530,22 @@ class NerfTraining:
 
     def reset_camera_extrinsics(self):
         check(lib().ngp_nerf_trainer_reset_camera_extrinsics(self.handle))
+
+    # ---- error-driven sampling (nerf.training.sample_*_proportional_to_error, python_api.cu:624-625) ----
+    def set_error_sampling(self, focal_plane=None, image=None):
+        """Draw the rays' pixels in proportion to the error map once its first window has closed: focal_plane (the
+        position in the image) and image (which image); a switch not named keeps its value. Both default off. With a
+        switch on, training is not reproducible from run to run (the map is summed with float atomics). Cannot be
+        combined with optimize_extrinsics."""
+        cur = self.error_sampling()
+        f = cur["focal_plane"] if focal_plane is None else bool(focal_plane)
+        i = cur["image"] if image is None else bool(image)
+        check(lib().ngp_nerf_trainer_set_error_sampling(self.handle, int(f), int(i)))
+
+    def error_sampling(self):
+        f, i = C.c_int(), C.c_int()
+        check(lib().ngp_nerf_trainer_get_error_sampling(self.handle, C.byref(f), C.byref(i)))
+        return {"focal_plane": bool(f.value), "image": bool(i.value)}
 
     def last_samples(self):
         """The last step's sampler call (ngp_nerf_trainer_last_samples): {"rng", "n_rays", "max_samples"} and views of
