@@ -622,7 +622,11 @@ int ngp_nerf_trainer_error_map(ngp_nerf_trainer* t, int which, float* out, uint6
  * nerf.rgb counters, training_step, loss, aabb. Paths ending in .ingp are gzip streams (zstr; level 0
  * unless compress), others raw msgpack; loading accepts gzip, zlib or raw. Loading restores the params
  * (and the optimizer state if present), the density grid (mean and bitfield recomputed), the
- * rays-per-batch counters and the training step; the network must have the snapshot's n_params. */
+ * rays-per-batch counters and the training step; the network must have the snapshot's n_params.
+ * Engine extension (the reference does not save m_envmap): with an environment map set, a member "envmap" holds
+ * width, height, params_binary and ema_params_binary (fp32) and, with the optimizer state, "optimizer" {current_step,
+ * ema_valid, ema_binary, first_moments_binary, second_moments_binary, param_steps_binary}. Loading sets the trainer's
+ * map from it; a snapshot without the member leaves the trainer's map as it is. */
 int ngp_nerf_save_snapshot(ngp_nerf_trainer* t, void* stream, const char* path, const char* network_config_json,
                            int include_optimizer_state, int compress);
 int ngp_nerf_load_snapshot(ngp_nerf_trainer* t, void* stream, const char* path);
@@ -770,6 +774,82 @@ int ngp_nerf_trainer_set_error_sampling(ngp_nerf_trainer* t, int focal_plane, in
 int ngp_nerf_trainer_get_error_sampling(const ngp_nerf_trainer* t, int* focal_plane, int* image);  /* each nullable */
 /* cam_pos_offset[i] / cam_rot_offset[i] (each nullable) */
 int ngp_nerf_trainer_pose_optimizer_state(const ngp_nerf_trainer* t, uint32_t i, ngp_adam_state* pos, ngp_adam_state* rot);
+
+/* ---- environment map (Testbed::m_envmap, Training::train_envmap) --------------------------------- */
+/* A small trainable equirectangular RGBA image read by ray direction as the background at infinity (envmap.cuh:29-94,
+ * dir_to_spherical_unorm random_val.cuh:62-72). A map is [height][width][4] fp32, texel index x + y * width.
+ * ngp_envmap_lookup: the four texels and bilinear weights of n normalized directions (dirs [n x 3]) as read_envmap and
+ * deposit_envmap_gradient both derive them (envmap.cuh:30-35, 59-64): texels [n x 4] in the order (x, y), (x+1, y),
+ * (x, y+1), (x+1, y+1) with x wrapped and y clamped, weights [n x 4] = (1-wx)(1-wy), wx(1-wy), (1-wx)wy, wx wy.
+ * Device memory. _host: the same function compiled for the host, host memory, no GPU call; acosf / atan2f differ
+ * between the two, so they agree to rounding, not to the bit. Width and height in 1..8192. */
+int ngp_envmap_lookup(void* stream, uint32_t width, uint32_t height, uint32_t n, const float* dirs, uint32_t* texels,
+                      float* weights);
+int ngp_envmap_lookup_host(uint32_t width, uint32_t height, uint32_t n, const float* dirs, uint32_t* texels, float* weights);
+/* Engine extension (inspection): deposit_envmap_gradient (envmap.cuh:57-94, T = half) of n fp16 rgb values
+ * (values_f16 [n x 3]; alpha's gradient is zero in the reference, testbed_nerf.cu:2007-2008) along n directions, as
+ * the loss pass does it: each corner receives fp16(value) * fp16(weight) rounded to fp16, and gradient
+ * [height][width][4] fp32 is WRITTEN with the exact sum of a channel's contributions rounded once to fp32 (64-bit
+ * integer atomics in units of 2^-24: no dependence on the order of arrival). A non-finite contribution makes its
+ * channel NaN. */
+int ngp_envmap_deposit(void* stream, uint32_t width, uint32_t height, uint32_t n, const float* dirs, const void* values_f16,
+                       float* gradient);
+/* tcnn Trainer<float, float, float>::optimizer_step over a TrainableBuffer (testbed.cu:4133-4147, testbed_nerf.cu:
+ * 3683-3685): one step of the Ema / ExponentialDecay / Adam chain of optimizer_json over n fp32 parameters with an
+ * fp32 gradient, no matrix weights (a parameter whose gradient is exactly zero is skipped: no l2 term, its entry of
+ * param_steps stays). `step`: the chain's steps taken before this one (schedule, EMA debias). ema / ema_params (both
+ * required under an Ema wrapper): the running EMA and its debiased value. Device memory, caller-owned state. */
+int ngp_envmap_optimizer_step(void* stream, const char* optimizer_json, uint32_t step, float loss_scale, uint32_t n, float* params,
+                              const float* gradient, float* first_moments, float* second_moments, uint32_t* param_steps,
+                              float* ema, float* ema_params);
+/* ngp_nerf_compute_loss with an environment map bound (testbed_nerf.cu:1781-1792): every ray's background becomes
+ * envmap.rgb + srgb_to_linear(background) * (1 - envmap.a) in the ray's normalized direction, before the target and
+ * the prediction use it. envmap_gradient (nullable; [env_height][env_width][4], WRITTEN): the loss's gradient with
+ * respect to the map (:1988-2011): rays that kept all of their samples (and at least one) deposit
+ * fp16(loss_scale / n_rays * T * dL/drgb [/ srgb_to_linear_derivative(background)]) as ngp_envmap_deposit does, with
+ * the gradient of envmap_loss_type (ELossType) where that differs from cfg's loss; alpha's gradient stays zero. */
+int ngp_nerf_compute_loss_envmap(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
+                                 uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples_compacted,
+                                 const uint32_t* ray_counter, const void* network_output, const uint32_t* ray_indices,
+                                 const float* rays, uint32_t* numsteps, const float* coords_in, float* coords_out,
+                                 void* dloss_doutput, float* loss, uint32_t* compacted_counter, const float* mean_density,
+                                 float loss_scale, const float* envmap, uint32_t env_width, uint32_t env_height,
+                                 uint32_t envmap_loss_type, float* envmap_gradient);
+/* The trainer's map (m_envmap; reset_network / load_nerf_post, testbed.cu:4133-4147, nerf_loader.cu:516-528): rgba
+ * (nullable: zeros) are the [height][width][4] initial values in HOST memory. Setting a map resets its optimizer.
+ * With a map set every training ray is composited over it (the raw parameters, m_envmap.view()); without one the step
+ * issues exactly the launches it would have. */
+int ngp_nerf_trainer_set_envmap(ngp_nerf_trainer* t, uint32_t width, uint32_t height, const float* rgba);
+int ngp_nerf_trainer_clear_envmap(ngp_nerf_trainer* t);
+enum {
+	NGP_ENVMAP_PARAMS = 0,            /* the raw parameters (training reads these) */
+	NGP_ENVMAP_INFERENCE_PARAMS = 1,  /* inference_view(): the debiased EMA once a step ran under an Ema wrapper */
+	NGP_ENVMAP_GRADIENT = 2,          /* the last step's gradient (still scaled by LOSS_SCALE = 128) */
+	NGP_ENVMAP_FIRST_MOMENTS = 3,
+	NGP_ENVMAP_SECOND_MOMENTS = 4,
+	NGP_ENVMAP_PARAM_STEPS = 5        /* per-parameter Adam step counters: uint32 in the float slots */
+};
+/* Copies array `which` ([height][width][4]) to HOST memory (out nullable: only the resolution; 0 x 0: no map). */
+int ngp_nerf_trainer_envmap(const ngp_nerf_trainer* t, int which, float* out, uint64_t capacity, uint32_t* width,
+                            uint32_t* height);
+/* The device array (NGP_ENVMAP_PARAMS or NGP_ENVMAP_INFERENCE_PARAMS; NULL without a map), e.g. for
+ * ngp_nerf_renderer_set_envmap. Valid until the map is set or cleared; which array holds the inference parameters
+ * changes with the first training step, so ask again after training. */
+int ngp_nerf_trainer_envmap_device(const ngp_nerf_trainer* t, int which, const float** data, uint32_t* width, uint32_t* height);
+/* Training::train_envmap (testbed.h:716-785, python_api.cu:618-653; default off): every step sums the map's gradient
+ * (bitwise reproducible, see ngp_envmap_deposit) and takes one step of the map's optimizer with LOSS_SCALE after the
+ * loss pass (testbed_nerf.cu:3668-3685). Without a map it does nothing, as in the reference. Single GPU: refused with
+ * a data-parallel exchange hook set, and so is setting a hook while it is on. */
+int ngp_nerf_trainer_set_train_envmap(ngp_nerf_trainer* t, int train);
+int ngp_nerf_trainer_get_train_envmap(const ngp_nerf_trainer* t, int* train);
+/* The network config's "envmap" section (testbed.cu:4135-4136): the map's loss (ELossType; -1: the training loss)
+ * and its optimizer chain (JSON as ngp_trainer_create takes it; NULL: the main trainer's). base.json trains the map
+ * with RelativeL2 and its own Ema / ExponentialDecay / Adam. */
+int ngp_nerf_trainer_set_envmap_training(ngp_nerf_trainer* t, int loss_type, const char* optimizer_json);
+/* render_nerf with an environment map (testbed_nerf.cu:2315-2319): the frame is pre-filled per pixel with the map's
+ * value in the pixel's normalized ray direction instead of background_rgba. envmap: DEVICE [height][width][4] fp32,
+ * owned by the caller and read by every later ngp_nerf_render; NULL unbinds. */
+int ngp_nerf_renderer_set_envmap(ngp_nerf_renderer* r, const float* envmap, uint32_t width, uint32_t height);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

@@ -274,6 +274,20 @@ SIGNATURES = {
                                             C.POINTER(NerfErrorCdfs), P, P, P]),
     "ngp_nerf_trainer_set_error_sampling": (i32, [P, i32, i32]),
     "ngp_nerf_trainer_get_error_sampling": (i32, [P, C.POINTER(i32), C.POINTER(i32)]),
+    "ngp_envmap_lookup": (i32, [P, u32, u32, u32, P, P, P]),
+    "ngp_envmap_lookup_host": (i32, [u32, u32, u32, P, P, P]),
+    "ngp_envmap_deposit": (i32, [P, u32, u32, u32, P, P, P]),
+    "ngp_envmap_optimizer_step": (i32, [P, C.c_char_p, u32, f32, u32, P, P, P, P, P, P, P]),
+    "ngp_nerf_compute_loss_envmap": (i32, [P, C.POINTER(NerfConfig), P, u32, u32, Rng, u32, P, P, P, P, P, P, P, P, P, P,
+                                           P, f32, P, u32, u32, u32, P]),
+    "ngp_nerf_trainer_set_envmap": (i32, [P, u32, u32, P]),
+    "ngp_nerf_trainer_clear_envmap": (i32, [P]),
+    "ngp_nerf_trainer_envmap": (i32, [P, i32, P, u64, C.POINTER(u32), C.POINTER(u32)]),
+    "ngp_nerf_trainer_envmap_device": (i32, [P, i32, C.POINTER(P), C.POINTER(u32), C.POINTER(u32)]),
+    "ngp_nerf_trainer_set_train_envmap": (i32, [P, i32]),
+    "ngp_nerf_trainer_get_train_envmap": (i32, [P, C.POINTER(i32)]),
+    "ngp_nerf_trainer_set_envmap_training": (i32, [P, i32, C.c_char_p]),
+    "ngp_nerf_renderer_set_envmap": (i32, [P, P, u32, u32]),
 }
 
 

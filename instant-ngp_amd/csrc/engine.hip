@@ -1276,6 +1276,11 @@ static void parse_optimizer(const Json& j, AdamConfig& c) {
 	}
 }
 
+}  // extern "C"
+void ngp::parse_optimizer_json(const char* json, AdamConfig& c) { parse_optimizer(Json::parse(json), c); }
+const AdamConfig& ngp::trainer_adam_config(const ngp_trainer* t) { return t->cfg; }
+extern "C" {
+
 int ngp_trainer_create(ngp_model* m, const char* optimizer_json, uint64_t seed, ngp_trainer** out) {
 	NGP_ARG(m && out);
 	NGP_TRY({

@@ -29,6 +29,11 @@ int forward_backward_with(ngp_model* m, void* stream, uint32_t n, const float* i
 int capture_training_step_with(ngp_trainer* t, void* stream, uint32_t n, const float* input, uint32_t input_stride,
                                const void* dL_doutput, uint32_t dL_stride, float loss_scale, uint32_t n_steps, int with_optimizer,
                                const Exchange& ex, ngp_graph** out, float* dL_dinput = nullptr, uint32_t dL_dinput_stride = 0);
+// The optimizer chain's JSON (Ema / ExponentialDecay / Adam, as ngp_trainer_create takes it) into c; and a trainer's
+// own configuration (the NeRF environment map's optimizer falls back to it, testbed.cu:4135-4136)
+struct AdamConfig;
+void parse_optimizer_json(const char* json, AdamConfig& c);
+const AdamConfig& trainer_adam_config(const ngp_trainer* t);
 // The values ngp_graph_launch writes into the trainer's device control block before a launch of its graph (set_device_ctl:
 // step at ctl[0], the AdamConfig at ctl + CTL_CFG), for a caller that writes them in a kernel of its own, and
 // the launch without that write (the rest of ngp_graph_launch: workspace check, step and staleness bookkeeping).

@@ -114,7 +114,24 @@ struct LossArgs {
 	uint32_t pub_seq;
 	// the CDFs the rays' pixels were drawn from (the sampler's): pass 1 repeats the draw and divides the loss by its pdf
 	ErrorCdfs cdfs;
+	// environment map (testbed_nerf.cu:1781-1792, 1988-2011; envmap.h): [env_h][env_w] RGBA floats read by the ray's
+	// direction as the background behind cfg's; null: off, and the kernels' instantiations without it run.
+	// env_acc (optional): the gradient accumulator (envmap_acc_words64 words, zeroed by the caller) pass 2 deposits
+	// into for every ray that kept all of its samples; the gradient's loss is env_loss_type.
+	const float* envmap;
+	uint32_t env_w, env_h, env_loss_type;
+	unsigned long long* env_acc;
 };
+
+// The environment map's stand-alone forms (envmap.hip): dirs [n x 3] normalized; texels, weights [n x 4] as
+// envmap_lookup returns them; values [n x 3] fp16 rgb gradients added into acc (envmap_acc_words64 words, zeroed by
+// the caller); envmap_gradient_f32 converts an accumulator to the fp32 gradient [h x w x 4].
+size_t envmap_acc_words64(uint32_t width, uint32_t height);
+void envmap_lookup_device(uint32_t w, uint32_t h, uint32_t n, const float* dirs, uint32_t* texels, float* weights, hipStream_t s);
+void envmap_lookup_host(uint32_t w, uint32_t h, uint32_t n, const float* dirs, uint32_t* texels, float* weights);
+void envmap_deposit_values(uint32_t w, uint32_t h, uint32_t n, const float* dirs, const f16* values, unsigned long long* acc,
+                           hipStream_t s);
+void envmap_gradient_f32(uint32_t w, uint32_t h, const unsigned long long* acc, float* grad, hipStream_t s);
 
 // Every ray's training pixel (nerf_pixel.h): img [n_rays], uv [n_rays x 2] after snapping, pdf [n_rays x 2] =
 // {img_pdf, uv_pdf}. The device form reads the dataset's cameras and device CDFs; the host form makes no GPU call
@@ -194,6 +211,10 @@ struct RenderArgs {
 	uint32_t render_mode;          // ERenderMode (common.h:110-121): 0 AO, 1 Shade, 2 Normals, 3 Positions, 4 Depth, 9 EncodingVis
 	float depth_scale;             // ERenderMode::Depth: 1 / dataset scale (testbed_nerf.cu:2822)
 	int32_t show_accel;            // Testbed::Nerf::show_accel (-1 off): the march's minimum mip, alpha 1, Positions by cell
+	// environment map (testbed_nerf.cu:2315-2319): the frame is pre-filled per pixel with the map's value in the
+	// pixel's ray direction instead of `background`; device [env_h][env_w] RGBA floats, null: off
+	const float* envmap;
+	uint32_t env_w, env_h;
 };
 enum : uint32_t { RENDER_AO = 0, RENDER_SHADE = 1, RENDER_NORMALS = 2, RENDER_POSITIONS = 3, RENDER_DEPTH = 4, RENDER_ENCODING_VIS = 9 };
 struct RenderWorkspace {

@@ -16,6 +16,7 @@
 #include "render_common.h"
 #include "rng.h"
 #include "nerf_pixel.h"
+#include "envmap.h"
 
 namespace ngp {
 namespace nerf {
@@ -167,6 +168,9 @@ __device__ __forceinline__ float unwarp_dt(float dt) {  // :418-421
 
 // common_device.cuh:75-121
 __device__ __forceinline__ float srgb_to_linear(float s) { return s <= 0.04045f ? s / 12.92f : powf((s + 0.055f) / 1.055f, 2.4f); }
+__device__ __forceinline__ float srgb_to_linear_derivative(float s) {
+	return s <= 0.04045f ? 1.0f / 12.92f : 2.4f / 1.055f * powf((s + 0.055f) / 1.055f, 1.4f);
+}
 __device__ __forceinline__ float linear_to_srgb(float l) { return l < 0.0031308f ? 12.92f * l : 1.055f * powf(l, 0.41666f) - 0.055f; }
 
 __device__ __forceinline__ float logistic(float x) { return 1.0f / (1.0f + ngp_expf_fast(-x)); }  // tcnn::logistic
@@ -1110,8 +1114,9 @@ void sample_rays(const Dataset& ds, const ngp_nerf_config& cfg, const SampleArgs
 // ------------------------------------------------------------------------------------------------
 // compute_loss_kernel_train_nerf (testbed_nerf.cu:1660-2012), split at its atomicAdd into two passes
 // around a prefix scan. The error map deposit (:1869-1899, always on in the reference's training) is
-// done in pass 2 after the compaction early-out, as there; sharpness / envmap / exposure / depth
-// supervision are off in the reference's default training and not implemented.
+// done in pass 2 after the compaction early-out, as there, and so is the environment map's gradient
+// deposit (:1988-2011; envmap.h); sharpness / exposure / depth supervision are off in the
+// reference's default training and not implemented.
 // A ray owns one DPP row: lanes load and activate 16 samples at once (network output, dt, exp), and
 // the compositing recurrence (T *= 1 - alpha, rgb += alpha T c) runs over the row in sample order
 // with row_newbcast broadcasts, i.e. with the reference's float ops in the reference's order.
@@ -1122,7 +1127,9 @@ struct LossRay {  // pass-1 results kept for pass 2
 	float mean_loss;
 	float u, v;    // the ray's image position and image (the error map deposit)
 	uint32_t img;
-	float pad[2];
+	// with an environment map's gradient bound: the ray's fp16 dL/d(envmap rgb) (bits of halves 0|1, 2|-), valid when
+	// the ray kept all of its samples; zero otherwise
+	uint32_t env[2];
 };
 
 __device__ __forceinline__ V3 unwarp_pos(const float* c, const Aabb& b) {
@@ -1131,7 +1138,8 @@ __device__ __forceinline__ V3 unwarp_pos(const float* c, const Aabb& b) {
 
 #define NGP_ROW_UNROLL16(M) M(0) M(1) M(2) M(3) M(4) M(5) M(6) M(7) M(8) M(9) M(10) M(11) M(12) M(13) M(14) M(15)
 
-template <bool CDF>
+// ENV: an environment map is bound (LossArgs::envmap): a separate instantiation, as CDF is
+template <bool CDF, bool ENV>
 __global__ void __launch_bounds__(256) k_loss_pass1(const Camera* __restrict__ cams, const uint32_t* __restrict__ pixels,
                                                     uint32_t n_images, const ngp_nerf_config cfg, LossArgs a,
                                                     uint32_t* __restrict__ craw, LossRay* __restrict__ lr) {
@@ -1171,6 +1179,17 @@ __global__ void __launch_bounds__(256) k_loss_pass1(const Camera* __restrict__ c
 	float bgc = srgb_to_linear(ch == 0 ? bg[0] : ch == 1 ? bg[1] : bg[2]);
 	// read_rgba, Byte images (common_device.cuh:885-904)
 	const uint32_t raw = pixels[cam.pixel_offset + pixel_index(u, v, cam.width, cam.height)];
+	// the environment map's four texels in the ray's direction, loaded here for the same reason
+	EnvmapTap tap;
+	f32x4 e0, e1, e2, e3;
+	if (ENV) {
+		const float* rd = a.rays + (size_t)i * 6 + 3;
+		const float dx = rd[0], dy = rd[1], dz = rd[2];
+		const float inv = 1.0f / sqrtf(dx * dx + dy * dy + dz * dz);
+		tap = envmap_lookup(a.env_w, a.env_h, dx * inv, dy * inv, dz * inv);
+		const f32x4* em = (const f32x4*)a.envmap;
+		e0 = em[tap.idx[0]]; e1 = em[tap.idx[1]]; e2 = em[tap.idx[2]]; e3 = em[tap.idx[3]];
+	}
 	float t = 1.f;
 	const float eps = 1e-4f;
 	float rr = 0.f, rg = 0.f, rb = 0.f;
@@ -1260,6 +1279,10 @@ __global__ void __launch_bounds__(256) k_loss_pass1(const Camera* __restrict__ c
 		texc = srgb_to_linear((float)((raw >> (8 * ch)) & 0xff) * (1.0f / 255.0f)) * alpha;
 		tex3 = alpha;
 	}
+	if (ENV) {  // the background behind the map's (testbed_nerf.cu:1787-1792), before the target and the prediction use it
+		const float ec = envmap_mix(tap, e0[ch], e1[ch], e2[ch], e3[ch]), ea = envmap_mix(tap, e0[3], e1[3], e2[3], e3[3]);
+		bgc = ec + bgc * (1.0f - ea);
+	}
 	const float exposure_scale = expf(0.6931471805599453f * 0.0f);
 	float target;
 	if (cfg.linear_colors || cfg.color_space_linear) {
@@ -1280,6 +1303,21 @@ __global__ void __launch_bounds__(256) k_loss_pass1(const Camera* __restrict__ c
 	if (CDF) lc = lc / (px.img_pdf * px.uv_pdf);
 	const float l1 = row_bcast<1>(lc), l2 = row_bcast<2>(lc), g1 = row_bcast<1>(gc), g2 = row_bcast<2>(gc);
 	const float p1 = row_bcast<1>(pred), p2 = row_bcast<2>(pred);
+	// dL/d(envmap) of channel ch (testbed_nerf.cu:1988-2002): the map's own loss where it differs, times the
+	// transmittance left, through the sRGB curve when not training in linear colours, rounded to fp16
+	uint32_t eh0 = 0, eh1 = 0, eh2 = 0;
+	if (ENV) {
+		if (a.env_acc && cn == numsteps) {
+			float ge = gc;
+			if (a.env_loss_type != cfg.loss_type) { float le; loss_channel(target, pred, a.env_loss_type, &le, &ge); }
+			float dbg = t * ge;
+			if (!cfg.linear_colors) dbg = dbg / srgb_to_linear_derivative(bgc);
+			const f16 hv = (f16)((a.loss_scale / (float)a.n_rays) * dbg);
+			eh0 = (uint32_t)__builtin_bit_cast(uint16_t, hv);
+		}
+		eh1 = __float_as_uint(row_bcast<1>(__uint_as_float(eh0)));
+		eh2 = __float_as_uint(row_bcast<2>(__uint_as_float(eh0)));
+	}
 	if (L != 0) return;
 	craw[i] = cn;
 	LossRay q;
@@ -1287,7 +1325,7 @@ __global__ void __launch_bounds__(256) k_loss_pass1(const Camera* __restrict__ c
 	q.grad[0] = gc; q.grad[1] = g1; q.grad[2] = g2;
 	q.rgb_ray[0] = pred; q.rgb_ray[1] = p1; q.rgb_ray[2] = p2;
 	q.u = u; q.v = v; q.img = img;
-	q.pad[0] = q.pad[1] = 0.f;
+	q.env[0] = eh0 | (eh1 << 16); q.env[1] = eh2;
 	lr[i] = q;
 }
 
@@ -1313,7 +1351,8 @@ __device__ __forceinline__ void deposit_error(const LossArgs& a, const Camera* _
 // LANES per ray: LG (one DPP row) when pass 2 composites again; a whole wave when it reads pass 1's kept state,
 // where the samples are independent: a ray's samples then take ceil(cn / 64) rounds of loads instead of
 // ceil(cn / 16), and the long rays, each round a memory latency, set the kernel's time (fox: up to ~26 rounds)
-template <uint32_t LANES>
+// ENV: an environment map's gradient accumulator is bound (LossArgs::env_acc): lane 0 deposits the ray's gradient
+template <uint32_t LANES, bool ENV>
 __global__ void __launch_bounds__(256) k_loss_pass2(const Camera* __restrict__ cams, const ngp_nerf_config cfg, LossArgs a,
                                                     const uint32_t* __restrict__ craw, const uint32_t* __restrict__ gpre,
                                                     const LossRay* __restrict__ lr) {
@@ -1321,6 +1360,8 @@ __global__ void __launch_bounds__(256) k_loss_pass2(const Camera* __restrict__ c
 	const uint32_t i = gid / LANES, L = gid % LANES;
 	if (i >= a.n_rays || i >= *a.ray_counter) return;
 	const uint32_t base = a.numsteps[2 * i + 1];
+	uint32_t numsteps = 0;  // the sampler's count, read by every lane before lane 0 overwrites it below
+	if (ENV) numsteps = a.numsteps[2 * i];
 	// the exclusive prefix of the compacted counts: the ray's group of 4 (k_scan4) plus the rays of the group before it
 	uint32_t compacted_base = gpre[i / 4];
 	for (uint32_t r = i & ~3u; r < i; ++r) compacted_base += craw[r];
@@ -1334,6 +1375,16 @@ __global__ void __launch_bounds__(256) k_loss_pass2(const Camera* __restrict__ c
 	const LossRay q = lr[i];
 	if (L == 0 && a.loss) a.loss[i] = q.mean_loss / (float)a.n_rays;  // written after the compaction early-out (:1836-1866)
 	if (L == 0 && a.error_map) deposit_error(a, cams, q);
+	// the map's gradient, after the compaction early-out and only from rays that kept every sample (:1836, :1988):
+	// a ray cut short by the compacted budget deposits nothing, as there
+	if (ENV && L == 0 && cn == numsteps) {
+		const float* rd = a.rays + (size_t)i * 6 + 3;
+		const float dx = rd[0], dy = rd[1], dz = rd[2];
+		const float inv = 1.0f / sqrtf(dx * dx + dy * dy + dz * dz);
+		const EnvmapTap tap = envmap_lookup(a.env_w, a.env_h, dx * inv, dy * inv, dz * inv);
+		envmap_deposit(a.env_acc, (size_t)a.env_w * a.env_h * 4, tap, __builtin_bit_cast(f16, (uint16_t)(q.env[0] & 0xffffu)),
+		               __builtin_bit_cast(f16, (uint16_t)(q.env[0] >> 16)), __builtin_bit_cast(f16, (uint16_t)(q.env[1] & 0xffffu)));
+	}
 	const float loss_scale = a.loss_scale / (float)a.n_rays;
 	const float output_l2_reg = cfg.rgb_activation == ACT_EXP ? 1e-4f : 0.0f;
 	const float output_l1_reg_density = *a.mean_density < MIN_OPTICAL_THICKNESS ? 1e-4f : 0.0f;
@@ -1481,7 +1532,10 @@ void compute_loss(const Dataset& ds, const ngp_nerf_config& cfg, const LossArgs&
 		ProfScope ps("loss_pass1", s);
 		static_assert(256 / LG == 16, "k_loss_pass1's XCD-aware order assumes 16 rays per block");
 		const uint32_t b1 = NGP_LOSS_XCD ? 8 * div_round_up(a.n_rays, 128) : blocks;
-		auto pass1 = a.cdfs.any() ? k_loss_pass1<true> : k_loss_pass1<false>;
+		NGP_CHECK(!a.envmap || (a.env_w > 0 && a.env_h > 0 && a.rays), "compute_loss: environment map without a resolution or rays");
+		NGP_CHECK(!a.env_acc || a.envmap, "compute_loss: an environment map gradient needs the map");
+		auto pass1 = a.envmap ? (a.cdfs.any() ? k_loss_pass1<true, true> : k_loss_pass1<false, true>)
+		                      : (a.cdfs.any() ? k_loss_pass1<true, false> : k_loss_pass1<false, false>);
 		pass1<<<b1, 256, 0, s>>>(ds.d_cams, ds.d_pixels, ds.n_images, cfg, a, craw, lr);
 		NGP_HIP(hipGetLastError());
 	}
@@ -1494,9 +1548,11 @@ void compute_loss(const Dataset& ds, const ngp_nerf_config& cfg, const LossArgs&
 	static_assert(NGP_LOSS_SELECT, "pass 1 keeps the compositing state pass 2 reads only in its select form");
 	if (a.state) {
 		constexpr uint32_t W = NGP_LOSS2_LANES;  // a wave per ray: see k_loss_pass2
-		k_loss_pass2<W><<<div_round_up((size_t)a.n_rays * W, 256), 256, 0, s>>>(ds.d_cams, cfg, a, craw, gpre, lr);
+		auto pass2 = a.env_acc ? k_loss_pass2<W, true> : k_loss_pass2<W, false>;
+		pass2<<<div_round_up((size_t)a.n_rays * W, 256), 256, 0, s>>>(ds.d_cams, cfg, a, craw, gpre, lr);
 	} else {
-		k_loss_pass2<LG><<<blocks, 256, 0, s>>>(ds.d_cams, cfg, a, craw, gpre, lr);
+		auto pass2 = a.env_acc ? k_loss_pass2<LG, true> : k_loss_pass2<LG, false>;
+		pass2<<<blocks, 256, 0, s>>>(ds.d_cams, cfg, a, craw, gpre, lr);
 	}
 	NGP_HIP(hipGetLastError());
 }
@@ -2364,6 +2420,29 @@ __global__ void k_render_fill(uint32_t n, f32x4 bg, float* __restrict__ frame) {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i < n) *(f32x4*)(frame + 4 * (size_t)i) = bg;
 }
+// The frame pre-filled with the environment map in each pixel's ray direction (testbed_nerf.cu:2315-2319); the
+// direction is the one k_render_init gives the pixel's payload (same operations)
+__global__ void k_render_fill_envmap(RenderArgs a, float* __restrict__ frame) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	const uint32_t W = a.width, H = a.height;
+	if (i >= W * H) return;
+	const uint32_t x = i % W, y = i / W;
+	float ox, oy;
+	ld_random_pixel_offset(a.snap_to_pixel_centers ? 0u : a.sample_index, &ox, &oy);
+	const float u = ((float)x + ox) / (float)W, v = ((float)y + oy) / (float)H;
+	float dx = (u - a.screen_center[0]) * (float)W / a.focal[0];
+	float dy = (v - a.screen_center[1]) * (float)H / a.focal[1];
+	lens_undistort(a.lens_mode, a.lens, &dx, &dy);
+	const float* m = a.cam;
+	const V3 d = v3(m[0] * dx + m[3] * dy + m[6], m[1] * dx + m[4] * dy + m[7], m[2] * dx + m[5] * dy + m[8]);
+	const float inv = 1.0f / sqrtf(d.x * d.x + d.y * d.y + d.z * d.z);
+	const EnvmapTap t = envmap_lookup(a.env_w, a.env_h, d.x * inv, d.y * inv, d.z * inv);
+	const f32x4* em = (const f32x4*)a.envmap;
+	const f32x4 e0 = em[t.idx[0]], e1 = em[t.idx[1]], e2 = em[t.idx[2]], e3 = em[t.idx[3]];
+	f32x4 c;
+	for (int k = 0; k < 4; ++k) c[k] = envmap_mix(t, e0[k], e1[k], e2[k], e3[k]);
+	*(f32x4*)(frame + 4 * (size_t)i) = c;
+}
 __global__ void k_render_accumulate(uint32_t n4, float w, const float* __restrict__ frame, float* __restrict__ acc, bool first) {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i < n4) acc[i] = (first ? 0.f : acc[i]) + frame[i] * w;
@@ -2382,8 +2461,9 @@ void render_frame(const RenderArgs& a, uint32_t spp, RenderWorkspace& ws, const 
 	for (uint32_t sidx = 0; sidx < spp; ++sidx) {
 		RenderArgs r = a;
 		r.sample_index = a.sample_index + sidx;
-		k_render_fill<<<div_round_up(n_px, 256), 256, 0, s>>>(n_px, f32x4{a.background[0], a.background[1], a.background[2],
-		                                                                    a.background[3]}, ws.frame);
+		if (a.envmap) k_render_fill_envmap<<<div_round_up(n_px, 256), 256, 0, s>>>(r, ws.frame);
+		else k_render_fill<<<div_round_up(n_px, 256), 256, 0, s>>>(n_px, f32x4{a.background[0], a.background[1], a.background[2],
+		                                                                         a.background[3]}, ws.frame);
 		k_render_init<<<div_round_up(n_px, 128), 128, 0, s>>>(r, pay[0], rgba[0]);
 		NGP_HIP(hipGetLastError());
 		NGP_HIP(hipMemsetAsync(ws.counters, 0, 8, s));  // counters[1]: hits (whole trace)

@@ -23,6 +23,7 @@
 #include "msgpack.h"
 #include "nerf.h"
 #include "nerf_camera.h"
+#include "optimizer.h"
 #include "profiler.h"
 
 using namespace ngp;
@@ -117,6 +118,8 @@ extern "C" const char* ngp_last_error(void);
 
 struct ngp_nerf_renderer {
 	Buf pay0, pay1, payh, rgba0, rgba1, rgbah, coords, out, frame, counters;
+	const float* envmap = nullptr;        // ngp_nerf_renderer_set_envmap (the caller's device memory)
+	uint32_t env_w = 0, env_h = 0;
 	uint32_t* host_counters = nullptr;
 	uint32_t render_mode = RENDER_SHADE;  // ngp_nerf_renderer_set_mode
 	int32_t show_accel = -1;             // ngp_nerf_renderer_set_show_accel
@@ -256,6 +259,28 @@ struct ngp_nerf_trainer {
 	// CDFs of the last closed window (testbed_nerf.cu:3948-3949). Both off: the uniform kernels, nothing else changes.
 	bool sample_focal_plane_by_error = false, sample_image_by_error = false;
 	bool error_sampling() const { return sample_focal_plane_by_error || sample_image_by_error; }
+	// Environment map (Testbed::m_envmap and Training::train_envmap; testbed.cu:4133-4147, testbed_nerf.cu:3668-3685):
+	// fp32 RGBA parameters [h][w][4] behind every training ray, their EMA for rendering, and with `train` on a
+	// gradient summed exactly per step (envmap.h) and an optimizer step of their own after every loss pass. Not set:
+	// the step issues exactly the launches it would without any of this.
+	struct Envmap {
+		uint32_t w = 0, h = 0;
+		Buf params, ema, ema_out, m1, m2, steps, grad, acc;
+		uint32_t step = 0;         // optimizer steps taken
+		bool ema_valid = false;    // ema_out holds the debiased EMA of a step under an Ema wrapper (or a snapshot's)
+		AdamConfig opt;            // the "envmap" section's optimizer; opt_set false: the main trainer's
+		bool opt_set = false;
+		int32_t loss_type = -1;    // the "envmap" section's loss; -1: cfg.loss_type
+		bool train = false;
+		size_t n() const { return (size_t)w * h * 4; }
+		bool bound() const { return w != 0; }
+	} env;
+	const AdamConfig& envmap_optimizer() const { return env.opt_set ? env.opt : trainer_adam_config(trainer); }
+	uint32_t envmap_loss_type() const { return env.loss_type < 0 ? cfg.loss_type : (uint32_t)env.loss_type; }
+	// what rendering reads (inference_view): the debiased EMA once a step has been taken under an Ema wrapper
+	const float* envmap_inference() const {
+		return (const float*)(env.ema_valid ? env.ema_out.p : env.params.p);
+	}
 	ErrorCdfs sampling_cdfs() const {
 		ErrorCdfs e{};
 		if (!em_cdf_valid || !em_cdf_w || !em_cdf_h) return e;
@@ -479,7 +504,8 @@ static int nerf_compute_loss(const ngp_nerf_dataset* ds, const ngp_nerf_config* 
                              uint32_t* compacted_counter, const float* mean_density, float loss_scale, bool zero_loss = false,
                              float* error_map = nullptr, uint32_t em_w = 0, uint32_t em_h = 0, float* state = nullptr,
                              uint64_t state_cap = 0, volatile uint32_t* pub_host = nullptr, uint32_t pub_seq = 0,
-                             const ErrorCdfs& cdfs = ErrorCdfs{});
+                             const ErrorCdfs& cdfs = ErrorCdfs{}, const float* envmap = nullptr, uint32_t env_w = 0,
+                             uint32_t env_h = 0, uint32_t env_loss_type = 0, unsigned long long* env_acc = nullptr);
 
 int ngp_nerf_compute_loss(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
                           uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples_compacted, const uint32_t* ray_counter,
@@ -529,13 +555,79 @@ int ngp_nerf_compute_loss_cdf(const ngp_nerf_dataset* ds, const ngp_nerf_config*
 	                         loss_scale, false, error_map, em_width, em_height, nullptr, 0, nullptr, 0, e);
 }
 
+static bool envmap_dims_ok(uint32_t w, uint32_t h) { return w >= 1 && h >= 1 && w <= 8192 && h <= 8192; }
+
+int ngp_nerf_compute_loss_envmap(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
+                                 uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples_compacted, const uint32_t* ray_counter,
+                                 const void* network_output, const uint32_t* ray_indices, const float* rays, uint32_t* numsteps,
+                                 const float* coords_in, float* coords_out, void* dloss_doutput, float* loss,
+                                 uint32_t* compacted_counter, const float* mean_density, float loss_scale, const float* envmap,
+                                 uint32_t env_width, uint32_t env_height, uint32_t envmap_loss_type, float* envmap_gradient) {
+	if (!envmap || !rays || !envmap_dims_ok(env_width, env_height) || envmap_loss_type > LOSS_RELL2) return NGP_INVALID;
+	NERF_TRY({
+		static thread_local Buf acc;
+		unsigned long long* a = nullptr;
+		if (envmap_gradient) {
+			const size_t words = envmap_acc_words64(env_width, env_height);
+			a = acc.get<unsigned long long>(words);
+			NGP_HIP(hipMemsetAsync(a, 0, words * 8, S(stream)));
+		}
+		const int rc = nerf_compute_loss(ds, cfg, stream, n_rays, n_rays_total, rng, max_samples_compacted, ray_counter,
+		                                 network_output, 16, ray_indices, rays, numsteps, coords_in, coords_out, dloss_doutput, loss,
+		                                 compacted_counter, mean_density, loss_scale, false, nullptr, 0, 0, nullptr, 0, nullptr, 0,
+		                                 ErrorCdfs{}, envmap, env_width, env_height, envmap_loss_type, a);
+		if (rc != NGP_OK) return rc;  // the error string is set
+		if (envmap_gradient) envmap_gradient_f32(env_width, env_height, a, envmap_gradient, S(stream));
+	});
+}
+
+int ngp_envmap_lookup(void* stream, uint32_t width, uint32_t height, uint32_t n, const float* dirs, uint32_t* texels, float* weights) {
+	if (!envmap_dims_ok(width, height) || (n && (!dirs || !texels || !weights))) return NGP_INVALID;
+	NERF_TRY({ envmap_lookup_device(width, height, n, dirs, texels, weights, S(stream)); });
+}
+
+int ngp_envmap_lookup_host(uint32_t width, uint32_t height, uint32_t n, const float* dirs, uint32_t* texels, float* weights) {
+	if (!envmap_dims_ok(width, height) || (n && (!dirs || !texels || !weights))) return NGP_INVALID;
+	envmap_lookup_host(width, height, n, dirs, texels, weights);
+	return NGP_OK;
+}
+
+int ngp_envmap_deposit(void* stream, uint32_t width, uint32_t height, uint32_t n, const float* dirs, const void* values_f16,
+                       float* gradient) {
+	if (!envmap_dims_ok(width, height) || !gradient || (n && (!dirs || !values_f16))) return NGP_INVALID;
+	NERF_TRY({
+		static thread_local Buf acc;
+		const size_t words = envmap_acc_words64(width, height);
+		unsigned long long* a = acc.get<unsigned long long>(words);
+		NGP_HIP(hipMemsetAsync(a, 0, words * 8, S(stream)));
+		envmap_deposit_values(width, height, n, dirs, (const f16*)values_f16, a, S(stream));
+		envmap_gradient_f32(width, height, a, gradient, S(stream));
+	});
+}
+
+int ngp_envmap_optimizer_step(void* stream, const char* optimizer_json, uint32_t step, float loss_scale, uint32_t n, float* params,
+                              const float* gradient, float* first_moments, float* second_moments, uint32_t* param_steps, float* ema,
+                              float* ema_params) {
+	if (!optimizer_json || !params || !gradient || !first_moments || !second_moments || !param_steps || !(loss_scale > 0.f))
+		return NGP_INVALID;
+	NERF_TRY({
+		AdamConfig c;
+		parse_optimizer_json(optimizer_json, c);
+		AdamState st{};
+		st.w32 = params; st.g32 = gradient; st.m1 = first_moments; st.m2 = second_moments; st.steps = param_steps;
+		st.ema32 = ema; st.ema_f32 = ema_params; st.step_add = step;
+		adam_ema_update_f32(c, n, loss_scale, st, S(stream));
+	});
+}
+
 static int nerf_compute_loss(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
                              uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples_compacted, const uint32_t* ray_counter,
                              const void* network_output, uint32_t out_stride, const uint32_t* ray_indices, const float* rays,
                              uint32_t* numsteps, const float* coords_in, float* coords_out, void* dloss_doutput, float* loss,
                              uint32_t* compacted_counter, const float* mean_density, float loss_scale, bool zero_loss,
                              float* error_map, uint32_t em_w, uint32_t em_h, float* state, uint64_t state_cap,
-                             volatile uint32_t* pub_host, uint32_t pub_seq, const ErrorCdfs& cdfs) {
+                             volatile uint32_t* pub_host, uint32_t pub_seq, const ErrorCdfs& cdfs, const float* envmap,
+                             uint32_t env_w, uint32_t env_h, uint32_t env_loss_type, unsigned long long* env_acc) {
 	if (!ds || !cfg || !ray_counter || !network_output || !numsteps || !coords_in || !coords_out || !dloss_doutput ||
 	    !compacted_counter || !mean_density)
 		return NGP_INVALID;
@@ -551,6 +643,7 @@ static int nerf_compute_loss(const ngp_nerf_dataset* ds, const ngp_nerf_config* 
 		a.state = state; a.state_cap = state ? state_cap : 0;
 		a.pub_host = pub_host; a.pub_seq = pub_seq;
 		a.cdfs = cdfs;
+		a.envmap = envmap; a.env_w = env_w; a.env_h = env_h; a.env_loss_type = env_loss_type; a.env_acc = envmap ? env_acc : nullptr;
 		NGP_CHECK(n_rays > 0 || !pub_host, "compute_loss: the counters are published by the scan, which needs rays");
 		if (n_rays == 0) { NGP_HIP(hipMemsetAsync(compacted_counter, 0, 4, S(stream))); return NGP_OK; }
 		static thread_local Buf tmp, tmpf;
@@ -699,6 +792,95 @@ int ngp_nerf_trainer_get_error_sampling(const ngp_nerf_trainer* t, int* focal_pl
 	return NGP_OK;
 }
 
+// ---- environment map ---------------------------------------------------------------------------------------------
+// The map's gradient is summed on one GPU and stepped there; all-reducing it is not implemented
+static const char* const TRAIN_ENVMAP_VS_DATA_PARALLEL =
+	"train_envmap is single-GPU (the environment map's gradient is not all-reduced): it cannot be combined with a "
+	"data-parallel exchange hook; turn one of them off first";
+
+int ngp_nerf_trainer_set_envmap(ngp_nerf_trainer* t, uint32_t width, uint32_t height, const float* rgba) {
+	if (!t || !envmap_dims_ok(width, height)) return NGP_INVALID;
+	NERF_TRY({
+		NGP_HIP(hipDeviceSynchronize());  // the last step may still read the old map (the prelaunched sampler reads none)
+		ngp_nerf_trainer::Envmap& e = t->env;
+		e.w = width; e.h = height; e.step = 0; e.ema_valid = false;
+		const size_t n = e.n(), b = n * sizeof(float);
+		float* p = e.params.get<float>(n);
+		if (rgba) NGP_HIP(hipMemcpy(p, rgba, b, hipMemcpyHostToDevice));
+		else NGP_HIP(hipMemset(p, 0, b));
+		for (Buf* q : {&e.ema, &e.ema_out, &e.m1, &e.m2, &e.steps, &e.grad}) NGP_HIP(hipMemset(q->get<float>(n), 0, b));
+		(void)e.acc.get<unsigned long long>(envmap_acc_words64(width, height));
+	});
+}
+
+int ngp_nerf_trainer_clear_envmap(ngp_nerf_trainer* t) {
+	if (!t) return NGP_INVALID;
+	NERF_TRY({
+		NGP_HIP(hipDeviceSynchronize());
+		t->env.w = t->env.h = 0;
+		t->env.step = 0;
+		t->env.ema_valid = false;
+	});
+}
+
+static const float* envmap_array(const ngp_nerf_trainer* t, int which) {
+	const ngp_nerf_trainer::Envmap& e = t->env;
+	switch (which) {
+		case NGP_ENVMAP_PARAMS: return (const float*)e.params.p;
+		case NGP_ENVMAP_INFERENCE_PARAMS: return t->envmap_inference();
+		case NGP_ENVMAP_GRADIENT: return (const float*)e.grad.p;
+		case NGP_ENVMAP_FIRST_MOMENTS: return (const float*)e.m1.p;
+		case NGP_ENVMAP_SECOND_MOMENTS: return (const float*)e.m2.p;
+		case NGP_ENVMAP_PARAM_STEPS: return (const float*)e.steps.p;
+	}
+	return nullptr;
+}
+
+int ngp_nerf_trainer_envmap(const ngp_nerf_trainer* t, int which, float* out, uint64_t cap, uint32_t* width, uint32_t* height) {
+	if (!t || which < NGP_ENVMAP_PARAMS || which > NGP_ENVMAP_PARAM_STEPS) return NGP_INVALID;
+	if (width) *width = t->env.w;
+	if (height) *height = t->env.h;
+	if (!out || !t->env.bound()) return NGP_OK;
+	if (cap < t->env.n()) return NGP_INVALID;
+	NERF_TRY({
+		NGP_HIP(hipDeviceSynchronize());
+		NGP_HIP(hipMemcpy(out, envmap_array(t, which), t->env.n() * sizeof(float), hipMemcpyDeviceToHost));
+	});
+}
+
+int ngp_nerf_trainer_envmap_device(const ngp_nerf_trainer* t, int which, const float** data, uint32_t* width, uint32_t* height) {
+	if (!t || !data || (which != NGP_ENVMAP_PARAMS && which != NGP_ENVMAP_INFERENCE_PARAMS)) return NGP_INVALID;
+	*data = t->env.bound() ? envmap_array(t, which) : nullptr;
+	if (width) *width = t->env.w;
+	if (height) *height = t->env.h;
+	return NGP_OK;
+}
+
+int ngp_nerf_trainer_set_train_envmap(ngp_nerf_trainer* t, int train) {
+	if (!t) return NGP_INVALID;
+	NERF_TRY({
+		NGP_CHECK(!train || !t->dp(), TRAIN_ENVMAP_VS_DATA_PARALLEL);
+		t->env.train = train != 0;
+	});
+}
+
+int ngp_nerf_trainer_get_train_envmap(const ngp_nerf_trainer* t, int* train) {
+	if (!t || !train) return NGP_INVALID;
+	*train = t->env.train ? 1 : 0;
+	return NGP_OK;
+}
+
+int ngp_nerf_trainer_set_envmap_training(ngp_nerf_trainer* t, int loss_type, const char* optimizer_json) {
+	if (!t || loss_type < -1 || loss_type > (int)LOSS_RELL2) return NGP_INVALID;
+	NERF_TRY({
+		AdamConfig c;
+		if (optimizer_json) parse_optimizer_json(optimizer_json, c);
+		t->env.loss_type = loss_type;
+		t->env.opt_set = optimizer_json != nullptr;
+		if (optimizer_json) t->env.opt = c;
+	});
+}
+
 int ngp_nerf_trainer_get_camera_training(const ngp_nerf_trainer* t, ngp_nerf_camera_training* out) {
 	if (!t || !out) return NGP_INVALID;
 	*out = t->cam;
@@ -788,6 +970,13 @@ int ngp_nerf_renderer_set_depth_scale(ngp_nerf_renderer* r, float depth_scale) {
 	r->depth_scale = depth_scale;
 	return NGP_OK;
 }
+int ngp_nerf_renderer_set_envmap(ngp_nerf_renderer* r, const float* envmap, uint32_t width, uint32_t height) {
+	if (!r || (envmap && !envmap_dims_ok(width, height))) return NGP_INVALID;
+	r->envmap = envmap;
+	r->env_w = envmap ? width : 0;
+	r->env_h = envmap ? height : 0;
+	return NGP_OK;
+}
 
 int ngp_nerf_render(ngp_nerf_renderer* r, ngp_model* model, const ngp_nerf_config* cfg, void* stream, const ngp_nerf_image* camera,
                     const uint8_t* bitfield, uint32_t spp, uint32_t sample_index, float min_transmittance, const float* background_rgba,
@@ -836,7 +1025,8 @@ int ngp_nerf_render(ngp_nerf_renderer* r, ngp_model* model, const ngp_nerf_confi
 		a.render_mode = r->render_mode;
 		a.depth_scale = r->depth_scale;
 		a.show_accel = r->show_accel;
-		auto infer = [&](uint32_t n, const float* coords, f16* out) {
+		a.envmap = r->envmap; a.env_w = r->env_w; a.env_h = r->env_h;
+		auto infer =[&](uint32_t n, const float* coords, f16* out) {
 			check_rc(ngp_inference(model, s, n, coords, 7, out, n, NGP_LAYOUT_SOA, use_inference_params));
 		};
 		// Normals: tcnn input_gradient's default backprop_scale (128); it reads the inference parameters
@@ -851,6 +1041,10 @@ int ngp_nerf_trainer_set_data_parallel(ngp_nerf_trainer* t, uint32_t rank, uint3
 	if (!t || world == 0 || rank >= world || (world > 1 && !allreduce)) return NGP_INVALID;
 	if (allreduce && t->cam.optimize_extrinsics) {
 		nerf_set_error("camera pose refinement is single-GPU: turn optimize_extrinsics off before setting an exchange hook");
+		return NGP_ERROR;
+	}
+	if (allreduce && t->env.train) {
+		nerf_set_error(TRAIN_ENVMAP_VS_DATA_PARALLEL);
 		return NGP_ERROR;
 	}
 	t->drain();
@@ -1289,6 +1483,11 @@ static void step_loss_and_publish(ngp_nerf_trainer* t, hipStream_t s, const Step
 		memset(p, 0, 64);
 	}
 	const uint32_t pub_seq = c.dp ? 0u : ++t->publish_seq;
+	// environment map: the raw parameters behind every ray (m_envmap.view()), and with train_envmap the gradient
+	// accumulator, cleared for this step's deposit
+	const ngp_nerf_trainer::Envmap& env = t->env;
+	unsigned long long* env_acc = env.bound() && env.train ? (unsigned long long*)env.acc.p : nullptr;
+	if (env_acc) NGP_HIP(hipMemsetAsync(env_acc, 0, envmap_acc_words64(env.w, env.h) * 8, s));
 	{
 		ProfScope ps("nerf_loss", s);
 		// pass 1 keeps each composited sample's state for pass 2 (indexed like the sampler's samples, at most max_samples)
@@ -1296,7 +1495,8 @@ static void step_loss_and_publish(ngp_nerf_trainer* t, hipStream_t s, const Step
 		check_rc(nerf_compute_loss(t->data, &t->cfg, s, Rl, R, c.rng, Bl, ctr, c.mlp_out, 4, sp.ray_indices, sp.rays, sp.numsteps,
 		                           sp.coords, c.coords_c, c.dloss, c.loss, ctr + 2, (const float*)t->mean.p,
 		                           c.dp ? loss_scale_local : 128.0f, true, error_map, t->em_w, t->em_h, lstate, sp.max_samples,
-		                           c.early_pub ? t->host_ctr : nullptr, pub_seq, t->sampling_cdfs()));
+		                           c.early_pub ? t->host_ctr : nullptr, pub_seq, t->sampling_cdfs(),
+		                           env.bound() ? (const float*)env.params.p : nullptr, env.w, env.h, t->envmap_loss_type(), env_acc));
 	}
 	if (!c.dp) {
 		// single GPU: the rollover launch (fill_rollover_and_rescale + fill_rollover) also publishes the counters
@@ -1359,6 +1559,25 @@ static void step_train_pass(ngp_nerf_trainer* t, hipStream_t s, const Step& c) {
 		check_rc(train_step_with(t->trainer, s, Bl, c.coords_c, 7, c.dloss, 16, 128.0f, t->exchange()));
 	}
 	t->rng.advance();  // m_rng.advance() (testbed_nerf.cu:4127)
+}
+
+// train_envmap (testbed_nerf.cu:3683-3685): the loss pass's exact gradient sum to fp32, then the map's own optimizer
+// step with LOSS_SCALE, eager on the step's stream after the training graph. The next step's loss pass reads the
+// parameters on the same stream; the prelaunched sampler never does.
+static void step_envmap_update(ngp_nerf_trainer* t, hipStream_t s, const Step& c) {
+	ngp_nerf_trainer::Envmap& e = t->env;
+	if (!e.bound() || !e.train || c.sp.Rl == 0) return;
+	ProfScope ps("nerf_envmap_update", s);
+	envmap_gradient_f32(e.w, e.h, (const unsigned long long*)e.acc.p, (float*)e.grad.p, s);
+	AdamState st{};
+	st.w32 = (float*)e.params.p; st.g32 = (const float*)e.grad.p;
+	st.m1 = (float*)e.m1.p; st.m2 = (float*)e.m2.p; st.steps = (uint32_t*)e.steps.p;
+	st.ema32 = (float*)e.ema.p; st.ema_f32 = (float*)e.ema_out.p;
+	st.step_add = e.step;
+	const AdamConfig& oc = t->envmap_optimizer();
+	adam_ema_update_f32(oc, (uint32_t)e.n(), 128.0f, st, s);
+	++e.step;
+	e.ema_valid = oc.ema_decay > 0.f;
 }
 
 // Camera pose refinement, device part (testbed_nerf.cu:3641-3644, 4071-4125): the compacted batch's input gradient summed per
@@ -1478,6 +1697,7 @@ int ngp_nerf_train_step(ngp_nerf_trainer* t, void* stream, int get_loss, ngp_ner
 		step_loss_and_publish(t, s, c);
 		step_release_samples(t, s, c);
 		step_train_pass(t, s, c);
+		step_envmap_update(t, s, c);
 		step_camera_gradients(t, s, c);
 		++t->training_step;
 		const float loss_scalar = step_read_counters(t, s, c);
@@ -1732,6 +1952,32 @@ int ngp_nerf_save_snapshot(ngp_nerf_trainer* t, void* stream, const char* path, 
 		snap["aabb"]["min"] = vec3(t->cfg.aabb_min);
 		snap["aabb"]["max"] = vec3(t->cfg.aabb_max);
 		snap["density_grid_ema_step"] = Value::uint(t->ema_step);
+		// engine extension (the reference does not save m_envmap): the environment map and its optimizer
+		if (t->env.bound()) {
+			NGP_HIP(hipDeviceSynchronize());
+			const ngp_nerf_trainer::Envmap& e = t->env;
+			const size_t n = e.n();
+			auto put = [&](Value& to, const char* name, const void* d) {
+				auto h = device_to_host<float>(d, n);
+				to[name] = Value::bin(h.data(), n * 4);
+			};
+			Value em = Value::object();
+			em["width"] = Value::uint(e.w);
+			em["height"] = Value::uint(e.h);
+			put(em, "params_binary", e.params.p);
+			put(em, "ema_params_binary", t->envmap_inference());
+			if (include_optimizer_state) {
+				Value opt = Value::object();
+				opt["current_step"] = Value::uint(e.step);
+				opt["ema_valid"] = Value::uint(e.ema_valid ? 1 : 0);
+				put(opt, "ema_binary", e.ema.p);
+				put(opt, "first_moments_binary", e.m1.p);
+				put(opt, "second_moments_binary", e.m2.p);
+				put(opt, "param_steps_binary", e.steps.p);
+				em["optimizer"] = opt;
+			}
+			snap["envmap"] = em;
+		}
 		write_snapshot(path, root, snap, compress);
 	});
 }
@@ -1792,6 +2038,37 @@ int ngp_nerf_load_snapshot(ngp_nerf_trainer* t, void* stream, const char* path) 
 			t->n_steps_since_cam_update = 0;
 			NGP_HIP(hipDeviceSynchronize());
 			t->rebuild_cameras(s);
+		}
+		// the environment map, where the snapshot has one (a snapshot without it leaves this trainer's as it is)
+		if (const Value* em = snap.find("envmap")) {
+			const uint32_t w = (uint32_t)em->at("width").number(), h = (uint32_t)em->at("height").number();
+			NGP_CHECK(envmap_dims_ok(w, h), "snapshot: envmap resolution");
+			const size_t n = (size_t)w * h * 4;
+			auto bin = [&](const Value& v, const char* name) -> const float* {
+				const Value* b = v.find(name);
+				if (!b) return nullptr;
+				NGP_CHECK(b->s.size() == n * 4, std::string("snapshot: envmap ") + name + " size");
+				return (const float*)b->s.data();
+			};
+			const float* params = bin(*em, "params_binary");
+			NGP_CHECK(params, "snapshot: envmap without params_binary");
+			check_ok(ngp_nerf_trainer_set_envmap(t, w, h, params));
+			ngp_nerf_trainer::Envmap& e = t->env;
+			auto up = [&](Buf& dst, const float* src) {
+				if (src) NGP_HIP(hipMemcpy(dst.p, src, n * 4, hipMemcpyHostToDevice));
+			};
+			if (const float* ema = bin(*em, "ema_params_binary")) {
+				up(e.ema_out, ema);
+				e.ema_valid = true;
+			}
+			if (const Value* opt = em->find("optimizer")) {
+				e.step = (uint32_t)opt->number_or("current_step", 0.0);
+				e.ema_valid = opt->number_or("ema_valid", 1.0) != 0.0;
+				up(e.ema, bin(*opt, "ema_binary"));
+				up(e.m1, bin(*opt, "first_moments_binary"));
+				up(e.m2, bin(*opt, "second_moments_binary"));
+				up(e.steps, bin(*opt, "param_steps_binary"));
+			}
 		}
 		NGP_HIP(hipStreamSynchronize(s));
 	});

@@ -50,6 +50,7 @@ struct AdamState {
 	// lazy layout, sharded data parallelism: the gradient is the ranks' fp32 sum of their fp16 gradients
 	// (reduce-scatter); it is rounded to fp16 once here, as the all-reduce path narrows it (dp_comm.hip)
 	const float* g32 = nullptr;
+	float* ema_f32 = nullptr;  // adam_ema_update_f32: the debiased EMA parameters in fp32 (where ema16 goes otherwise)
 };
 // ---- device helpers shared by optimizer.hip and the fused update in the grid backward ----------
 // Adam's bias correction depends on the parameter's own step s only: the factors sqrtf(1 - beta2^s) and
@@ -257,6 +258,11 @@ __device__ __forceinline__ void fused_adam_pair(const FusedAdam& fa, uint32_t r,
 // set_learning_rate / set_option like eager ones.
 constexpr uint32_t CTL_CFG = 16;
 void adam_ema_update(const AdamConfig& c, uint32_t n, uint32_t n_matrix, float loss_scale, const AdamState& st, hipStream_t s);
+// The eager chain over fp32 parameters with an fp32 gradient (st.g32) and no matrix weights: tcnn's
+// Trainer<float, float, float> over a TrainableBuffer (the NeRF environment map, testbed.cu:4133-4147). Every
+// parameter is a non-matrix one: an exactly zero gradient skips it (no l2 term, its step counter stays); the EMA runs
+// over all of them and st.ema_f32 receives it debiased. Same kernel text as adam_ema_update's tail (k_adam_ema).
+void adam_ema_update_f32(const AdamConfig& c, uint32_t n, float loss_scale, const AdamState& st, hipStream_t s);
 // Lazy layout: the update of parameters [lo, hi) only (multiples of 4): one rank's slice under the sharded
 // optimizer (st.g32 = the reduce-scattered fp32 gradient sums, indexed like the parameters)
 void adam_lazy_range(const AdamConfig& c, uint32_t lo, uint32_t hi, uint32_t n_matrix, float loss_scale, const AdamState& st,

@@ -27,6 +27,8 @@ void adam_bias_table(float* tab, float beta1, float beta2, hipStream_t s) {
 	NGP_HIP(hipGetLastError());
 }
 
+// F32 (adam_ema_update_f32): fp32 gradient (st.g32) and fp32 inference parameters (st.ema_f32), no fp16 copies
+template <bool F32>
 __global__ void k_adam_ema(const uint32_t i0, const uint32_t n, const uint32_t n_matrix, const float loss_scale, const AdamConfig c_arg,
                            const AdamState st) {
 	const AdamConfig c = st.cfg_dev ? *st.cfg_dev : c_arg;
@@ -34,7 +36,7 @@ __global__ void k_adam_ema(const uint32_t i0, const uint32_t n, const uint32_t n
 	const uint32_t step = (st.step_base ? *st.step_base : 0u) + st.step_add;
 	if (i < n) {
 		const float lr = lr_schedule(c, step);
-		float g = (float)st.g16[i] / loss_scale;
+		float g = (F32 ? st.g32[i] : (float)st.g16[i]) / loss_scale;
 		float w = st.w32[i];
 		if (!(i >= n_matrix && g == 0.f)) {
 			if (i < n_matrix) g += c.l2 * w;
@@ -47,19 +49,22 @@ __global__ void k_adam_ema(const uint32_t i0, const uint32_t n, const uint32_t n
 			const float lr_s = adam_step_size(c, lr, s, st.bias_tab);
 			w = w - lr_s / (sqrtf(vv) + c.eps) * mm;
 			st.w32[i] = w;
-			const f16 h = (f16)w;
-			st.w16[i] = h;
-			if (st.frags && i < n_matrix) {
-				const uint32_t q0 = st.fragmap[2 * i], q1 = st.fragmap[2 * i + 1];
-				if (q0 != ~0u) st.frags[q0] = h;
-				if (q1 != ~0u) st.frags[q1] = h;
+			if (!F32) {
+				const f16 h = (f16)w;
+				st.w16[i] = h;
+				if (st.frags && i < n_matrix) {
+					const uint32_t q0 = st.fragmap[2 * i], q1 = st.fragmap[2 * i + 1];
+					if (q0 != ~0u) st.frags[q0] = h;
+					if (q1 != ~0u) st.frags[q1] = h;
+				}
 			}
 		}
 		if (st.ema32) {
 			const float debias = 1.f - powf(c.ema_decay, (float)(step + 1));
 			const float v = ema_step(st.ema32[i], c.ema_decay, (1.f - c.ema_decay) * w);
 			st.ema32[i] = v;
-			st.ema16[i] = (f16)(v / debias);
+			if (F32) st.ema_f32[i] = v / debias;
+			else st.ema16[i] = (f16)(v / debias);
 		}
 	}
 }
@@ -268,7 +273,17 @@ void adam_ema_update(const AdamConfig& c, uint32_t n, uint32_t n_matrix, float l
 	                      (uintptr_t)a.w16 | (uintptr_t)a.g16 | (uintptr_t)a.ema16) % 16 == 0;
 	const uint32_t n4 = aligned ? n / 4 : 0;
 	if (n4) k_adam_ema4<<<div_round_up(n4, 256), 256, 0, s>>>(n4, n_matrix, loss_scale, c, a);
-	if (4 * n4 < n) k_adam_ema<<<div_round_up(n - 4 * n4, 256), 256, 0, s>>>(4 * n4, n, n_matrix, loss_scale, c, a);
+	if (4 * n4 < n) k_adam_ema<false><<<div_round_up(n - 4 * n4, 256), 256, 0, s>>>(4 * n4, n, n_matrix, loss_scale, c, a);
+	NGP_HIP(hipGetLastError());
+}
+
+void adam_ema_update_f32(const AdamConfig& c, uint32_t n, float loss_scale, const AdamState& st, hipStream_t s) {
+	NGP_CHECK(st.w32 && st.g32 && st.m1 && st.m2 && st.steps && !st.rec && (c.ema_decay <= 0.f || (st.ema32 && st.ema_f32)),
+	          "fp32 optimizer step: parameters, gradient, moments, step counters (and the EMA pair) required");
+	if (n == 0) return;
+	AdamState a = st;
+	if (c.ema_decay <= 0.f) a.ema32 = nullptr;
+	k_adam_ema<true><<<div_round_up(n, 256), 256, 0, s>>>(0, n, 0, loss_scale, c, a);
 	NGP_HIP(hipGetLastError());
 }
 

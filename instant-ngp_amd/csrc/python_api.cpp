@@ -73,8 +73,16 @@ void load_training_data(Testbed& tb, const std::string& path) {
 			const std::vector<float> o = d.attr("offset").cast<std::vector<float>>();
 			if (o.size() == 3) std::copy(o.begin(), o.end(), offset);
 		}
+		// the transforms file's "envmap" image: the initial environment map and its resolution (nerf_loader.cu:516-528)
+		py::array_t<float, py::array::c_style | py::array::forcecast> envmap;
+		const bool has_envmap = py::hasattr(d, "envmap") && !d.attr("envmap").is_none();
+		if (has_envmap) {
+			envmap = py::array_t<float, py::array::c_style | py::array::forcecast>(d.attr("envmap"));
+			if (envmap.ndim() != 3 || envmap.shape(2) != 4) throw std::runtime_error("load_training_data: the envmap is an [H, W, 4] RGBA image");
+		}
 		py::gil_scoped_release nogil;
 		tb.load_nerf(meta, ptrs, aabb_scale, scale, offset);
+		if (has_envmap) tb.set_dataset_envmap((uint32_t)envmap.shape(1), (uint32_t)envmap.shape(0), envmap.data());
 		break;
 	}
 	case ETestbedMode::Image: {
@@ -374,6 +382,21 @@ PYBIND11_MODULE(pyngp, m) {
 				              v.t->push_camera_training();
 			              } catch (...) { v.t->camera_training().optimize_extrinsics = was; throw; }
 		              })
+		// the environment map (python_api.cu:618-653): trains the dataset's "envmap" image, or the zero map of create_envmap
+		.def_property("train_envmap", [](NerfTrainingView& v) { return v.t->train_envmap(); },
+		              [](NerfTrainingView& v, bool x) { v.t->set_train_envmap(x); })
+		.def("create_envmap", [](NerfTrainingView& v, uint32_t width, uint32_t height) { v.t->create_envmap(width, height); },
+		     py::arg("width"), py::arg("height"),
+		     "Engine extension: a zero environment map of this resolution (for a dataset without an \"envmap\" image).")
+		.def("envmap", [](NerfTrainingView& v, bool ema) -> py::object {
+			     uint32_t w = 0, h = 0;
+			     const std::vector<float> a = v.t->envmap(ema, &w, &h);
+			     if (a.empty()) return py::none();
+			     py::array_t<float> out({(py::ssize_t)h, (py::ssize_t)w, (py::ssize_t)4});
+			     std::memcpy(out.mutable_data(), a.data(), a.size() * sizeof(float));
+			     return std::move(out);
+		     }, py::arg("ema") = false,
+		     "Engine extension: the environment map [H, W, 4] (the raw parameters, or the EMA parameters rendering reads); None without one.")
 		// error-driven sampling (python_api.cu:624-625); not reproducible from run to run while on
 		.def_property("sample_focal_plane_proportional_to_error", [](NerfTrainingView& v) { return v.t->sample_focal_plane_by_error(); },
 		              [](NerfTrainingView& v, bool x) { v.t->set_error_sampling(x, v.t->sample_image_by_error()); })

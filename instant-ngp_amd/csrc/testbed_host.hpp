@@ -19,6 +19,7 @@
 #pragma once
 
 #include <algorithm>
+#include <cctype>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -383,6 +384,7 @@ public:
 			}
 			push_camera_training();
 			push_error_sampling();
+			push_envmap();
 		}
 	}
 	uint64_t n_params() const { return m_model ? ngp_model_n_params(m_model) : 0; }
@@ -544,6 +546,12 @@ public:
 			const uint8_t* bf = nullptr;
 			const float* mean = nullptr;
 			check(ngp_nerf_trainer_buffers_read(m_nerf_trainer, &g, &bf, &mean), "ngp_nerf_trainer_buffers_read");
+			{  // the environment map's EMA parameters behind the frame (inference_view, testbed_nerf.cu:2315-2319); none: unbound
+				const float* env = nullptr;
+				uint32_t ew = 0, eh = 0;
+				check(ngp_nerf_trainer_envmap_device(m_nerf_trainer, NGP_ENVMAP_INFERENCE_PARAMS, &env, &ew, &eh), "ngp_nerf_trainer_envmap_device");
+				check(ngp_nerf_renderer_set_envmap(m_renderer, env, ew, eh), "ngp_nerf_renderer_set_envmap");
+			}
 			float* dev = m_render_buf.get<float>(out.size());
 			ngp_nerf_config cfg = m_nerf_cfg;
 			check(ngp_nerf_render(m_renderer, m_model, &cfg, nullptr, &cam, bf, spp, m_render_sample_index, m_render_min_transmittance,
@@ -751,6 +759,70 @@ public:
 			check(ngp_nerf_trainer_set_error_sampling(m_nerf_trainer, m_sample_focal_plane_by_error, m_sample_image_by_error),
 			      "ngp_nerf_trainer_set_error_sampling");
 	}
+	// ---- environment map (Testbed::m_envmap, Training::train_envmap; testbed.cu:4133-4147, python_api.cu:618-653) ----
+	// The dataset's "envmap" image (nerf_loader.cu:516-528), or zeros of a resolution asked for with create_envmap
+	// when the dataset brings none: the trainer's map after every reset_network. Without either, train_envmap does
+	// nothing, as in the reference.
+	void set_dataset_envmap(uint32_t width, uint32_t height, const float* rgba) {
+		if (width == 0 || height == 0) throw std::runtime_error("envmap: empty resolution");
+		m_envmap_res[0] = width;
+		m_envmap_res[1] = height;
+		if (rgba) m_envmap_init.assign(rgba, rgba + (size_t)width * height * 4);
+		else m_envmap_init.clear();
+		push_envmap();
+	}
+	void create_envmap(uint32_t width, uint32_t height) { set_dataset_envmap(width, height, nullptr); }
+	bool train_envmap() const { return m_train_envmap; }
+	void set_train_envmap(bool on) {
+		const bool was = m_train_envmap;
+		m_train_envmap = on;
+		try {
+			if (m_nerf_trainer) check(ngp_nerf_trainer_set_train_envmap(m_nerf_trainer, on ? 1 : 0), "ngp_nerf_trainer_set_train_envmap");
+		} catch (...) {
+			m_train_envmap = was;
+			throw;
+		}
+	}
+	// the map, its "envmap" config section (loss and optimizer, each falling back to the main one, testbed.cu:4135-4136)
+	// and the switch, to a live trainer
+	void push_envmap() {
+		if (!m_nerf_trainer) return;
+		if (m_envmap_res[0] == 0) {
+			check(ngp_nerf_trainer_clear_envmap(m_nerf_trainer), "ngp_nerf_trainer_clear_envmap");
+		} else {
+			check(ngp_nerf_trainer_set_envmap(m_nerf_trainer, m_envmap_res[0], m_envmap_res[1], m_envmap_init.empty() ? nullptr : m_envmap_init.data()),
+			      "ngp_nerf_trainer_set_envmap");
+			int loss = -1;
+			std::string opt;
+			if (m_network_config.contains("envmap")) {
+				const Json& e = m_network_config["envmap"];
+				if (e.contains("loss")) loss = loss_type_from_name(e["loss"].string_or("otype", "L2"));
+				if (e.contains("optimizer")) opt = e["optimizer"].dump();
+			}
+			check(ngp_nerf_trainer_set_envmap_training(m_nerf_trainer, loss, opt.empty() ? nullptr : opt.c_str()),
+			      "ngp_nerf_trainer_set_envmap_training");
+		}
+		check(ngp_nerf_trainer_set_train_envmap(m_nerf_trainer, m_train_envmap ? 1 : 0), "ngp_nerf_trainer_set_train_envmap");
+	}
+	static int loss_type_from_name(const std::string& name) {  // string_to_loss_type (common.cu), ELossType's order
+		static const char* const names[] = {"L2", "L1", "Mape", "Smape", "Huber", "LogL1", "RelativeL2"};
+		for (int k = 0; k < 7; ++k) {
+			const std::string n = names[k];
+			if (n.size() == name.size() && std::equal(n.begin(), n.end(), name.begin(), [](char a, char b) { return std::tolower(a) == std::tolower(b); }))
+				return k;
+		}
+		throw std::runtime_error("envmap: unknown loss type '" + name + "'");
+	}
+	// the trainer's map on the host: [height x width x 4], the raw or the EMA (rendering) parameters; empty without a map
+	std::vector<float> envmap(bool ema, uint32_t* width, uint32_t* height) {
+		*width = *height = 0;
+		if (!m_nerf_trainer) return {};
+		const int which = ema ? NGP_ENVMAP_INFERENCE_PARAMS : NGP_ENVMAP_PARAMS;
+		check(ngp_nerf_trainer_envmap(m_nerf_trainer, which, nullptr, 0, width, height), "ngp_nerf_trainer_envmap");
+		std::vector<float> out((size_t)*width * *height * 4);
+		if (!out.empty()) check(ngp_nerf_trainer_envmap(m_nerf_trainer, which, out.data(), out.size(), width, height), "ngp_nerf_trainer_envmap");
+		return out;
+	}
 	// the trainer refuses the pair; refused here as well, so that it cannot build up before there is a trainer
 	void check_error_sampling_vs_extrinsics() const {
 		if (m_cam_training.optimize_extrinsics && (m_sample_focal_plane_by_error || m_sample_image_by_error))
@@ -908,6 +980,8 @@ private:
 		m_image = nullptr;
 		m_sdf_mesh = nullptr;
 		m_nerf_images.clear();
+		m_envmap_init.clear();
+		m_envmap_res[0] = m_envmap_res[1] = 0;
 		m_training_data_available = false;
 	}
 
@@ -925,6 +999,9 @@ private:
 	ngp_nerf_trainer* m_nerf_trainer = nullptr;
 	ngp_nerf_camera_training m_cam_training{0, 16, 1e-4f, 1e-3f};  // testbed.h:716-785 defaults
 	bool m_sample_focal_plane_by_error = false, m_sample_image_by_error = false;  // testbed.h:733-734
+	bool m_train_envmap = false;            // Training::train_envmap
+	uint32_t m_envmap_res[2] = {0, 0};      // NerfDataset::envmap_resolution, or create_envmap's; 0: no map
+	std::vector<float> m_envmap_init;       // NerfDataset::envmap_data; empty: zeros
 	ngp_nerf_renderer* m_renderer = nullptr;
 	ngp_nerf_config m_nerf_cfg{};
 	std::vector<ngp_nerf_image> m_nerf_images;

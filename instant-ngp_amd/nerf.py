@@ -205,7 +205,8 @@ def training_pixels(ds, cfg, n_rays, rng, cdfs=None, ray_offset=0, n_rays_total=
 
 
 def compute_loss(ds, cfg, n_rays, rng, max_compacted, samples, network_output, mean_density, loss_scale=128.0,
-                 n_rays_total=None, stream=None, error_map=None, keep_state=False, state_capacity=None, cdfs=None):
+                 n_rays_total=None, stream=None, error_map=None, keep_state=False, state_capacity=None, cdfs=None,
+                 envmap=None, envmap_gradient=None, envmap_loss=None):
     """compute_loss_kernel_train_nerf (testbed_nerf.cu:1660-2012). `samples` is the dict returned by
     generate_training_samples (its numsteps is rewritten to the compacted {n, base}). error_map: a
     float32 device tensor [n_images, h, w] the compacted rays' losses are added into (:1869-1899).
@@ -213,7 +214,11 @@ def compute_loss(ds, cfg, n_rays, rng, max_compacted, samples, network_output, m
     training step's form; same outputs bit for bit). state_capacity: samples the kept state holds (default: every
     sample slot); rays reaching past it are composited again by pass 2, with the same result. cdfs: the CDFs the
     samples' pixels were drawn from (generate_training_samples(cdfs=)): loss and the error map deposit are divided by
-    the pixels' pdf, dL/doutput is not (ngp_nerf_compute_loss_cdf; that entry point has no keep_state form)."""
+    the pixels' pdf, dL/doutput is not (ngp_nerf_compute_loss_cdf; that entry point has no keep_state form).
+    envmap: a contiguous float32 device tensor [h, w, 4], the environment map behind every ray (testbed_nerf.cu:1781-1792;
+    ngp_nerf_compute_loss_envmap, on its own: no error_map, keep_state or cdfs). envmap_gradient: a tensor of the same
+    shape that is overwritten with the map's gradient (:1988-2011, an exact sum: the same bits in every run);
+    envmap_loss: the gradient's loss name or number (default: cfg.loss_type)."""
     dev = network_output.device
     # the kernel reads one output row per sample; samples never exceed the sampler's coords buffer
     if network_output.shape[0] < samples["coords"].shape[0]:
@@ -231,7 +236,19 @@ def compute_loss(ds, cfg, n_rays, rng, max_compacted, samples, network_output, m
             _ptr(out["loss"]), _ptr(out["compacted_counter"]), _ptr(mean_density), float(loss_scale))
     if error_map is not None and (error_map.dtype != torch.float32 or error_map.dim() != 3 or not error_map.is_contiguous()):
         raise ValueError("error_map: a contiguous float32 tensor [n_images, h, w]")
-    if cdfs is not None:
+    if envmap is None and envmap_gradient is not None:
+        raise ValueError("envmap_gradient: needs envmap")
+    if envmap is not None:
+        if error_map is not None or keep_state or cdfs is not None:
+            raise ValueError("envmap: without error_map, keep_state and cdfs (the C-ABI form takes none of them)")
+        for t in (envmap, envmap_gradient):
+            if t is not None and (t.dtype != torch.float32 or t.dim() != 3 or t.shape[2] != 4 or not t.is_contiguous()
+                                  or t.shape != envmap.shape or t.device != dev):
+                raise ValueError("envmap / envmap_gradient: contiguous float32 device tensors [h, w, 4] of one shape")
+        lt = cfg.loss_type if envmap_loss is None else (LOSS[envmap_loss] if isinstance(envmap_loss, str) else int(envmap_loss))
+        check(lib().ngp_nerf_compute_loss_envmap(*args, _ptr(envmap), envmap.shape[1], envmap.shape[0], lt,
+                                                 _ptr(envmap_gradient)))
+    elif cdfs is not None:
         if keep_state:
             raise ValueError("cdfs: without keep_state (the C-ABI form has no sample-state argument)")
         e, keep = _error_cdfs(cdfs, dev, len(ds))
@@ -249,6 +266,57 @@ def compute_loss(ds, cfg, n_rays, rng, max_compacted, samples, network_output, m
     else:
         check(lib().ngp_nerf_compute_loss_error_map(*args, _ptr(error_map), error_map.shape[2], error_map.shape[1]))
     return out
+
+
+# ---- environment map ----------------------------------------------------------------------------
+def envmap_lookup(width, height, dirs, host=False, stream=None):
+    """The four texels and bilinear weights of normalized directions in a width x height environment map, as the read
+    and the gradient deposit derive them (envmap.cuh:29-35, 59-64): (texels [n, 4] int64 indices x + y * width in the
+    order (x, y), (x+1, y), (x, y+1), (x+1, y+1), weights [n, 4] float32). dirs: [n, 3] float32; a device tensor
+    (ngp_envmap_lookup) or, host=True, a numpy array (ngp_envmap_lookup_host: the same function compiled for the host,
+    no GPU call). The two agree to the rounding of acos / atan2, not to the bit."""
+    if host:
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        tex, wt = np.zeros((d.shape[0], 4), np.uint32), np.zeros((d.shape[0], 4), np.float32)
+        check(lib().ngp_envmap_lookup_host(int(width), int(height), d.shape[0], d.ctypes.data, tex.ctypes.data, wt.ctypes.data))
+        return tex.astype(np.int64), wt
+    d = dirs.to(torch.float32).contiguous().view(-1, 3)
+    tex = torch.zeros((d.shape[0], 4), dtype=torch.int32, device=d.device)
+    wt = torch.zeros((d.shape[0], 4), dtype=torch.float32, device=d.device)
+    check(lib().ngp_envmap_lookup(_stream(stream), int(width), int(height), d.shape[0], _ptr(d), _ptr(tex), _ptr(wt)))
+    return tex.to(torch.int64), wt
+
+
+def envmap_deposit(width, height, dirs, values, stream=None):
+    """deposit_envmap_gradient (envmap.cuh:57-94) of fp16 rgb values [n, 3] along directions [n, 3], as the loss pass
+    does it (ngp_envmap_deposit): the gradient image [height, width, 4] float32, each channel the exact sum of its
+    fp16 contributions rounded once; alpha stays zero. Device tensors."""
+    d = dirs.to(torch.float32).contiguous().view(-1, 3)
+    v = values.to(torch.float16).contiguous().view(-1, 3)
+    if v.shape[0] != d.shape[0] or v.device != d.device:
+        raise ValueError("envmap_deposit: one fp16 rgb value per direction, on the directions' device")
+    g = torch.empty((int(height), int(width), 4), dtype=torch.float32, device=d.device)
+    check(lib().ngp_envmap_deposit(_stream(stream), int(width), int(height), d.shape[0], _ptr(d), _ptr(v), _ptr(g)))
+    return g
+
+
+def envmap_optimizer_step(optimizer, step, state, gradient, loss_scale=128.0, stream=None):
+    """One step of the map's optimizer chain (ngp_envmap_optimizer_step; tcnn Trainer<float, float, float>): optimizer
+    is the chain's config dict, step the steps taken before, state a dict of float32 device tensors of one size
+    ("params", "first_moments", "second_moments", "ema", "ema_params") and "param_steps" (int32), updated in place."""
+    n = state["params"].numel()
+    for k in ("params", "first_moments", "second_moments", "ema", "ema_params", "param_steps"):
+        t = state[k]
+        want = torch.int32 if k == "param_steps" else torch.float32
+        if t.dtype != want or t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"envmap_optimizer_step: state[{k!r}] is a contiguous {want} tensor of {n} elements")
+    g = gradient.to(torch.float32).contiguous()
+    if g.numel() != n:
+        raise ValueError("envmap_optimizer_step: one gradient per parameter")
+    check(lib().ngp_envmap_optimizer_step(_stream(stream), json.dumps(optimizer).encode(), int(step), float(loss_scale), n,
+                                          _ptr(state["params"]), _ptr(g), _ptr(state["first_moments"]),
+                                          _ptr(state["second_moments"]), _ptr(state["param_steps"]), _ptr(state["ema"]),
+                                          _ptr(state["ema_params"])))
 
 
 def fill_rollover(data, n_input, rescale=False, stream=None):
@@ -547,6 +615,60 @@ class NerfTraining:
         check(lib().ngp_nerf_trainer_get_error_sampling(self.handle, C.byref(f), C.byref(i)))
         return {"focal_plane": bool(f.value), "image": bool(i.value)}
 
+    # ---- environment map (nerf.training.train_envmap, python_api.cu:618-653; testbed.cu:4133-4147) ----
+    ENVMAP_ARRAYS = {"params": 0, "ema": 1, "gradient": 2, "first_moments": 3, "second_moments": 4, "param_steps": 5}
+
+    def set_envmap(self, rgba=None, resolution=None, loss=None, optimizer=None):
+        """Give the trainer an environment map: rgba, linear RGBA float32 [h, w, 4] (e.g. LoadedNerf.envmap), or zeros of
+        resolution = (width, height). rgba=None and resolution=None: remove the map. Every training ray is then
+        composited over the map; it trains only with train_envmap on. loss / optimizer: the network config's "envmap"
+        section ({"loss": {"otype": ...}, "optimizer": {...}}); not given: the training loss and the main optimizer."""
+        if rgba is None and resolution is None:
+            check(lib().ngp_nerf_trainer_clear_envmap(self.handle))
+            return
+        if rgba is not None:
+            a = np.ascontiguousarray(rgba.detach().cpu().numpy() if torch.is_tensor(rgba) else rgba, dtype=np.float32)
+            if a.ndim != 3 or a.shape[2] != 4 or (resolution is not None and tuple(resolution) != (a.shape[1], a.shape[0])):
+                raise ValueError("set_envmap: rgba is [h, w, 4] (and resolution, if given, its (width, height))")
+            check(lib().ngp_nerf_trainer_set_envmap(self.handle, a.shape[1], a.shape[0], a.ctypes.data))
+        else:
+            check(lib().ngp_nerf_trainer_set_envmap(self.handle, int(resolution[0]), int(resolution[1]), None))
+        if loss is not None or optimizer is not None:
+            lt = -1 if loss is None else (LOSS[loss] if isinstance(loss, str) else int(loss))
+            check(lib().ngp_nerf_trainer_set_envmap_training(self.handle, lt,
+                                                             json.dumps(optimizer).encode() if optimizer is not None else None))
+
+    def envmap(self, which="params"):
+        """The map as a numpy array [h, w, 4] (None without one): "params" (what training reads), "ema" (what rendering
+        reads: the debiased EMA parameters once a step ran under an Ema wrapper), "gradient" (the last step's, scaled
+        by LOSS_SCALE = 128), "first_moments", "second_moments" or "param_steps" (int32)."""
+        w, h = C.c_uint32(), C.c_uint32()
+        k = self.ENVMAP_ARRAYS[which]
+        check(lib().ngp_nerf_trainer_envmap(self.handle, k, None, 0, C.byref(w), C.byref(h)))
+        if w.value == 0:
+            return None
+        a = np.zeros((h.value, w.value, 4), np.float32)
+        check(lib().ngp_nerf_trainer_envmap(self.handle, k, a.ctypes.data, a.size, C.byref(w), C.byref(h)))
+        return a.view(np.int32) if which == "param_steps" else a
+
+    def envmap_device(self, ema=True):
+        """(device pointer, width, height) of the raw or EMA parameters for NerfRenderer.set_envmap; (None, 0, 0) without
+        a map. Ask again after training: the array holding the EMA parameters changes with the first step."""
+        p, w, h = C.c_void_p(), C.c_uint32(), C.c_uint32()
+        check(lib().ngp_nerf_trainer_envmap_device(self.handle, 1 if ema else 0, C.byref(p), C.byref(w), C.byref(h)))
+        return p.value, w.value, h.value
+
+    @property
+    def train_envmap(self):
+        """Training::train_envmap: every step also trains the environment map (default off; nothing without a map)."""
+        v = C.c_int()
+        check(lib().ngp_nerf_trainer_get_train_envmap(self.handle, C.byref(v)))
+        return bool(v.value)
+
+    @train_envmap.setter
+    def train_envmap(self, on):
+        check(lib().ngp_nerf_trainer_set_train_envmap(self.handle, int(bool(on))))
+
     def last_samples(self):
         """The last step's sampler call (ngp_nerf_trainer_last_samples): {"rng", "n_rays", "max_samples"} and views of
         the "ray_indices", "rays" and "counters" it wrote (valid until a later sampler runs: turn pipelining off)."""
@@ -616,6 +738,24 @@ class NerfRenderer:
                                     _ptr(bitfield), spp, sample_index, float(min_transmittance), bg,
                                     int(use_inference_params), _ptr(out)))
         return out
+
+    def set_envmap(self, envmap=None):
+        """Render over an environment map instead of `background` (testbed_nerf.cu:2315-2319): a contiguous float32
+        device tensor [h, w, 4] (kept alive by the renderer), a NerfTraining (its EMA parameters, inference_view();
+        bind again after further training or after the trainer's map changes), or None to unbind."""
+        if envmap is None:
+            self._envmap = None
+            check(lib().ngp_nerf_renderer_set_envmap(self.handle, None, 0, 0))
+        elif isinstance(envmap, NerfTraining):
+            p, w, h = envmap.envmap_device(ema=True)
+            self._envmap = envmap
+            check(lib().ngp_nerf_renderer_set_envmap(self.handle, p, w, h))
+        else:
+            if envmap.dtype != torch.float32 or envmap.dim() != 3 or envmap.shape[2] != 4 or not envmap.is_contiguous() \
+                    or not envmap.is_cuda:
+                raise ValueError("set_envmap: a contiguous float32 device tensor [h, w, 4]")
+            self._envmap = envmap
+            check(lib().ngp_nerf_renderer_set_envmap(self.handle, _ptr(envmap), envmap.shape[1], envmap.shape[0]))
 
     def __del__(self):
         h = getattr(self, "handle", None)

@@ -5,7 +5,7 @@ formats the training path consumes: the original NeRF/instant-ngp `transforms.js
 files), 8-bit images (PNG/JPEG/BMP... decoded to RGBA8 sRGB, EImageDataType::Byte), perspective and
 OpenCV / OpenCV-fisheye lenses, per-frame intrinsics overrides, `scale` / `offset` / `aabb` /
 `aabb_scale`, the sharpness filter, `n_frames`, `white_transparent` / `black_transparent`,
-`<file>.alpha.<ext>` alpha images and `dynamic_mask_<name>.png` masks. Not handled (the loader
+`<file>.alpha.<ext>` alpha images, `dynamic_mask_<name>.png` masks and the `envmap` image. Not handled (the loader
 raises): EXR/HDR images, depth supervision, per-pixel ray files, rolling shutter, FTheta / LatLong /
 equirectangular lenses, Mitsuba scenes — none of the in-scope datasets use them.
 Image decoding is PIL's (the reference uses stb_image); the pixels then travel to the device
@@ -127,6 +127,21 @@ def _srgb_to_linear(x):
     return np.where(x <= 0.04045, x / 12.92, ((x + 0.055) / 1.055) ** 2.4)
 
 
+def _load_envmap(path):
+    """The transforms file's "envmap" image (nerf_loader.cu:516-528) as linear RGBA float32 [h, w, 4]: load_exr_gpu for
+    .exr (the package's EXR reader), else load_stbi_gpu's from_rgba32 (common_device.cuh:771-798): sRGB decoded and
+    premultiplied by alpha."""
+    if not os.path.exists(path):
+        raise FileNotFoundError(f"Environment map {path} does not exist.")
+    if path.lower().endswith(".exr"):
+        from .exr import read_exr
+        return np.ascontiguousarray(read_exr(path), dtype=np.float32)
+    px = _decode(path).astype(np.float32) * np.float32(1.0 / 255.0)
+    alpha = px[..., 3:4]
+    rgb = _srgb_to_linear(px[..., :3]).astype(np.float32) * alpha
+    return np.ascontiguousarray(np.concatenate([rgb, alpha], axis=-1), dtype=np.float32)
+
+
 class LoadedNerf:
     """Result of load_nerf: cameras + RGBA8 pixels (host) and the dataset-level settings."""
 
@@ -134,6 +149,12 @@ class LoadedNerf:
         self.images, self.rgba8, self.paths = [], [], []
         self.scale, self.offset, self.aabb_scale = NERF_SCALE, [0.5, 0.5, 0.5], 1.0
         self.up = [0.0, 1.0, 0.0]
+        self.envmap = None  # the "envmap" image: linear RGBA float32 [h, w, 4] (NerfTraining.set_envmap takes it)
+
+    @property
+    def envmap_resolution(self):
+        """(width, height) of the dataset's environment map, (0, 0) without one (NerfDataset::envmap_resolution)."""
+        return (0, 0) if self.envmap is None else (self.envmap.shape[1], self.envmap.shape[0])
 
     def __len__(self):
         return len(self.images)
@@ -201,6 +222,8 @@ def load_nerf(jsonpaths, max_images=None):
             res.offset = [(float(a[1][k]) + float(a[0][k])) * 0.5 * -res.scale + 0.5 for k in range(3)]
         if "up" in j:
             res.up = [float(j["up"][1]), float(j["up"][2]), float(j["up"][0])]
+        if "envmap" in j:  # the initial environment map; its resolution is the map's (nerf_loader.cu:516-528)
+            res.envmap = _load_envmap(_resolve(base, j["envmap"]))
         if "integer_depth_scale" in j or any("depth_path" in fr for fr in frames):
             pass  # depth supervision is not part of the training path here: ignored like a missing depth file
         lens0 = {"mode": LENS_PERSPECTIVE, "params": [0.0] * 4, "principal": [0.5, 0.5]}
