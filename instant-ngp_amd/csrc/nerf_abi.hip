@@ -1,0 +1,414 @@
+// nerf_abi.hip — the C-ABI that needs no trainer: the NeRF dataset, the default config, stateless wrappers around the
+// kernels of nerf.hip and envmap.hip (sampler, training pixels, loss, environment map, rollover, density grid), and
+// the renderer. run_sampler and run_compute_loss are the wrappers' common part, which the training step
+// (nerf_trainer.hip) calls too.
+#include "nerf_host.h"
+
+namespace ngp {
+namespace nerf {
+
+// sample_rays, optionally tracing `cams` instead of the dataset's cameras
+int run_sampler(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, SampleArgs a, const Camera* cams) {
+	if (!ds || !cfg || !a.bitfield || !a.ray_indices || !a.rays || !a.numsteps || !a.coords || !a.counters) return NGP_INVALID;
+	NERF_TRY({
+		if (!a.n_rays_total_for_image_idx) a.n_rays_total_for_image_idx = a.n_rays;
+		static thread_local Buf tmp, tmpf;
+		if (a.n_rays == 0) { NGP_HIP(hipMemsetAsync(a.counters, 0, 8, S(stream))); return NGP_OK; }
+		sample_rays(ds->ds, *cfg, a, tmp.get<uint32_t>(sample_tmp_u32(a.n_rays)), tmpf.get<float>(sample_tmp_f32(a.n_rays)), S(stream), cams);
+	});
+}
+
+int run_compute_loss(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, LossArgs a) {
+	if (!ds || !cfg || !a.ray_counter || !a.network_output || !a.numsteps || !a.coords_in || !a.coords_out || !a.dloss_doutput ||
+	    !a.compacted_counter || !a.mean_density)
+		return NGP_INVALID;
+	NERF_TRY({
+		if (!a.n_rays_total_for_image_idx) a.n_rays_total_for_image_idx = a.n_rays;
+		if (!a.state) a.state_cap = 0;
+		if (!a.envmap) a.env_acc = nullptr;
+		NGP_CHECK(a.n_rays > 0 || !a.pub_host, "compute_loss: the counters are published by the scan, which needs rays");
+		if (a.n_rays == 0) { NGP_HIP(hipMemsetAsync(a.compacted_counter, 0, 4, S(stream))); return NGP_OK; }
+		static thread_local Buf tmp, tmpf;
+		compute_loss(ds->ds, *cfg, a, tmp.get<uint32_t>(2 * (size_t)a.n_rays), tmpf.get<float>(loss_tmp_f32(a.n_rays)), S(stream));
+	});
+}
+
+}  // namespace nerf
+}  // namespace ngp
+
+// The parameters every ngp_nerf_compute_loss* entry shares, in the order of their signature
+static LossArgs public_loss_args(uint32_t n_rays, uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples_compacted,
+                                 const uint32_t* ray_counter, const void* network_output, const uint32_t* ray_indices,
+                                 const float* rays, uint32_t* numsteps, const float* coords_in, float* coords_out,
+                                 void* dloss_doutput, float* loss, uint32_t* compacted_counter, const float* mean_density,
+                                 float loss_scale) {
+	LossArgs a{};
+	a.n_rays = n_rays; a.n_rays_total_for_image_idx = n_rays_total; a.rng = Rng{rng.state, rng.inc};
+	a.max_samples_compacted = max_samples_compacted; a.ray_counter = ray_counter;
+	a.network_output = (const f16*)network_output; a.out_stride = 16;
+	a.ray_indices = ray_indices; a.rays = rays; a.numsteps = numsteps; a.coords_in = coords_in; a.coords_out = coords_out;
+	a.dloss_doutput = (f16*)dloss_doutput; a.loss = loss; a.compacted_counter = compacted_counter;
+	a.mean_density = mean_density; a.loss_scale = loss_scale;
+	return a;
+}
+
+struct ngp_nerf_renderer {
+	Buf pay0, pay1, payh, rgba0, rgba1, rgbah, coords, out, frame, counters;
+	const float* envmap = nullptr;        // ngp_nerf_renderer_set_envmap (the caller's device memory)
+	uint32_t env_w = 0, env_h = 0;
+	uint32_t* host_counters = nullptr;
+	uint32_t render_mode = RENDER_SHADE;  // ngp_nerf_renderer_set_mode
+	int32_t show_accel = -1;             // ngp_nerf_renderer_set_show_accel
+	float depth_scale = 1.0f;             // ngp_nerf_renderer_set_depth_scale
+	~ngp_nerf_renderer() { if (host_counters) (void)hipHostFree(host_counters); }
+};
+
+extern "C" {
+
+int ngp_nerf_default_config(float aabb_scale, ngp_nerf_config* o) {
+	if (!o || !(aabb_scale >= 1.0f)) return NGP_INVALID;
+	memset(o, 0, sizeof(*o));
+	const float inflate = 0.5f * std::min((float)(1 << (CASCADES - 1)), aabb_scale);  // testbed_nerf.cu:3093-3094
+	for (int k = 0; k < 3; ++k) { o->aabb_min[k] = 0.5f - inflate; o->aabb_max[k] = 0.5f + inflate; }
+	uint32_t mc = 0;
+	while ((float)(1u << mc) < aabb_scale) ++mc;  // :3102-3105
+	o->max_cascade = mc;
+	o->cone_angle_constant = aabb_scale <= 1.0f ? 0.0f : 1.0f / 256.0f;  // :3109
+	o->snap_to_pixel_centers = 1;
+	o->random_bg_color = 1;
+	o->linear_colors = 0;
+	o->color_space_linear = 1;
+	o->rgb_activation = ACT_EXP;
+	o->density_activation = ACT_EXP;
+	o->loss_type = LOSS_HUBER;  // configs/nerf/base.json "loss": Huber
+	o->near_distance = 0.1f;
+	o->target_batch_size = 1u << 18;
+	return NGP_OK;
+}
+
+int ngp_nerf_dataset_create(uint32_t n_images, const ngp_nerf_image* images, const void* const* rgba8, ngp_nerf_dataset** out) {
+	if (!out || !images || !rgba8 || n_images == 0) return NGP_INVALID;
+	NERF_TRY({
+		auto d = std::make_unique<ngp_nerf_dataset>();
+		d->ds.n_images = n_images;
+		uint64_t total = 0;
+		std::vector<Camera> cams(n_images);
+		for (uint32_t i = 0; i < n_images; ++i) {
+			const ngp_nerf_image& im = images[i];
+			Camera& c = cams[i];
+			c.width = im.width; c.height = im.height;
+			c.focal[0] = im.focal_length[0]; c.focal[1] = im.focal_length[1];
+			c.principal[0] = im.principal_point[0]; c.principal[1] = im.principal_point[1];
+			NGP_CHECK(im.lens_mode <= LENS_OPENCV_FISHEYE, "nerf dataset: unsupported lens mode");
+			c.lens_mode = im.lens_mode;
+			for (int k = 0; k < 4; ++k) c.lens[k] = im.lens_params[k];
+			effective_camera_matrix(im.xform, c.m);
+			c.pixel_offset = total;
+			total += (uint64_t)im.width * im.height;
+		}
+		NGP_HIP(hipMalloc(&d->ds.d_pixels, total * 4 + 12 * 4 * n_images));
+		for (uint32_t i = 0; i < n_images; ++i)
+			NGP_HIP(hipMemcpy(d->ds.d_pixels + cams[i].pixel_offset, rgba8[i], (size_t)images[i].width * images[i].height * 4,
+			                  hipMemcpyHostToDevice));
+		// raw (start) transforms after the pixels, for mark_untrained_density_grid
+		std::vector<float> raw(12 * n_images);
+		for (uint32_t i = 0; i < n_images; ++i) memcpy(&raw[12 * i], images[i].xform, 48);
+		NGP_HIP(hipMemcpy(d->ds.d_pixels + total, raw.data(), raw.size() * 4, hipMemcpyHostToDevice));
+		d->ds.xforms = raw;
+		NGP_HIP(hipMalloc(&d->ds.d_cams, n_images * sizeof(Camera)));
+		NGP_HIP(hipMemcpy(d->ds.d_cams, cams.data(), n_images * sizeof(Camera), hipMemcpyHostToDevice));
+		d->ds.cams = cams;
+		*out = d.release();
+	});
+}
+
+void ngp_nerf_dataset_destroy(ngp_nerf_dataset* d) { delete d; }
+
+int ngp_nerf_generate_training_samples(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
+                                       uint32_t ray_offset, uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples,
+                                       const uint8_t* bitfield, uint32_t* ray_indices, float* rays, uint32_t* numsteps,
+                                       float* coords, uint32_t* counters) {
+	SampleArgs a{};
+	a.n_rays = n_rays; a.ray_offset = ray_offset; a.n_rays_total_for_image_idx = n_rays_total;
+	a.max_samples = max_samples; a.rng = Rng{rng.state, rng.inc}; a.bitfield = bitfield;
+	a.ray_indices = ray_indices; a.rays = rays; a.numsteps = numsteps; a.coords = coords; a.counters = counters;
+	return run_sampler(ds, cfg, stream, a, nullptr);
+}
+int ngp_nerf_generate_training_samples_cdf(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
+                                           uint32_t ray_offset, uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples,
+                                           const uint8_t* bitfield, uint32_t* ray_indices, float* rays, uint32_t* numsteps,
+                                           float* coords, uint32_t* counters, const ngp_nerf_error_cdfs* cdfs) {
+	SampleArgs a{};
+	if (!error_cdfs_arg(cdfs, &a.cdfs)) return NGP_INVALID;
+	a.n_rays = n_rays; a.ray_offset = ray_offset; a.n_rays_total_for_image_idx = n_rays_total;
+	a.max_samples = max_samples; a.rng = Rng{rng.state, rng.inc}; a.bitfield = bitfield;
+	a.ray_indices = ray_indices; a.rays = rays; a.numsteps = numsteps; a.coords = coords; a.counters = counters;
+	return run_sampler(ds, cfg, stream, a, nullptr);
+}
+
+int ngp_nerf_training_pixels(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays, uint32_t ray_offset,
+                             uint32_t n_rays_total, ngp_rng rng, const ngp_nerf_error_cdfs* cdfs, uint32_t* img, float* uv, float* pdf) {
+	ErrorCdfs e;
+	if (!ds || !cfg || !img || !uv || !pdf || !error_cdfs_arg(cdfs, &e)) return NGP_INVALID;
+	NERF_TRY(training_pixels(ds->ds, *cfg, n_rays, ray_offset, n_rays_total ? n_rays_total : n_rays, Rng{rng.state, rng.inc}, e, img, uv,
+	                         pdf, S(stream)));
+}
+int ngp_nerf_training_pixels_host(uint32_t n_images, const ngp_nerf_image* images, const ngp_nerf_config* cfg, uint32_t n_rays,
+                                  uint32_t ray_offset, uint32_t n_rays_total, ngp_rng rng, const ngp_nerf_error_cdfs* cdfs,
+                                  uint32_t* img, float* uv, float* pdf) {
+	ErrorCdfs e;
+	if (!images || n_images == 0 || !cfg || !img || !uv || !pdf || !error_cdfs_arg(cdfs, &e)) return NGP_INVALID;
+	NERF_TRY({
+		std::vector<Camera> cams(n_images);
+		for (uint32_t i = 0; i < n_images; ++i) {
+			if (images[i].width == 0 || images[i].height == 0) return NGP_INVALID;
+			cams[i] = Camera{};
+			cams[i].width = images[i].width; cams[i].height = images[i].height;
+		}
+		training_pixels_host(cams.data(), n_images, *cfg, n_rays, ray_offset, n_rays_total ? n_rays_total : n_rays,
+		                     Rng{rng.state, rng.inc}, e, img, uv, pdf);
+	});
+}
+
+int ngp_nerf_compute_loss(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
+                          uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples_compacted, const uint32_t* ray_counter,
+                          const void* network_output, const uint32_t* ray_indices, const float* rays, uint32_t* numsteps,
+                          const float* coords_in, float* coords_out, void* dloss_doutput, float* loss,
+                          uint32_t* compacted_counter, const float* mean_density, float loss_scale) {
+	const LossArgs a = public_loss_args(n_rays, n_rays_total, rng, max_samples_compacted, ray_counter, network_output, ray_indices, rays,
+	                                    numsteps, coords_in, coords_out, dloss_doutput, loss, compacted_counter, mean_density, loss_scale);
+	return run_compute_loss(ds, cfg, stream, a);
+}
+
+int ngp_nerf_compute_loss_error_map(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
+                                    uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples_compacted,
+                                    const uint32_t* ray_counter, const void* network_output, const uint32_t* ray_indices,
+                                    const float* rays, uint32_t* numsteps, const float* coords_in, float* coords_out,
+                                    void* dloss_doutput, float* loss, uint32_t* compacted_counter, const float* mean_density,
+                                    float loss_scale, float* error_map, uint32_t em_width, uint32_t em_height) {
+	if (error_map && (em_width < 2 || em_height < 2)) return NGP_INVALID;  // the bilinear deposit needs a 2x2 texel block
+	LossArgs a = public_loss_args(n_rays, n_rays_total, rng, max_samples_compacted, ray_counter, network_output, ray_indices, rays,
+	                              numsteps, coords_in, coords_out, dloss_doutput, loss, compacted_counter, mean_density, loss_scale);
+	a.error_map = error_map; a.em_w = em_width; a.em_h = em_height;
+	return run_compute_loss(ds, cfg, stream, a);
+}
+
+int ngp_nerf_compute_loss_state(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
+                                uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples_compacted, const uint32_t* ray_counter,
+                                const void* network_output, const uint32_t* ray_indices, const float* rays, uint32_t* numsteps,
+                                const float* coords_in, float* coords_out, void* dloss_doutput, float* loss,
+                                uint32_t* compacted_counter, const float* mean_density, float loss_scale, float* sample_state,
+                                uint64_t state_capacity) {
+	if (!sample_state || state_capacity == 0) return NGP_INVALID;
+	LossArgs a = public_loss_args(n_rays, n_rays_total, rng, max_samples_compacted, ray_counter, network_output, ray_indices, rays,
+	                              numsteps, coords_in, coords_out, dloss_doutput, loss, compacted_counter, mean_density, loss_scale);
+	a.state = sample_state; a.state_cap = state_capacity;
+	return run_compute_loss(ds, cfg, stream, a);
+}
+
+int ngp_nerf_compute_loss_cdf(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
+                              uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples_compacted, const uint32_t* ray_counter,
+                              const void* network_output, const uint32_t* ray_indices, const float* rays, uint32_t* numsteps,
+                              const float* coords_in, float* coords_out, void* dloss_doutput, float* loss,
+                              uint32_t* compacted_counter, const float* mean_density, float loss_scale, float* error_map,
+                              uint32_t em_width, uint32_t em_height, const ngp_nerf_error_cdfs* cdfs) {
+	LossArgs a = public_loss_args(n_rays, n_rays_total, rng, max_samples_compacted, ray_counter, network_output, ray_indices, rays,
+	                              numsteps, coords_in, coords_out, dloss_doutput, loss, compacted_counter, mean_density, loss_scale);
+	if (!error_cdfs_arg(cdfs, &a.cdfs)) return NGP_INVALID;
+	if (error_map && (em_width < 2 || em_height < 2)) return NGP_INVALID;
+	a.error_map = error_map; a.em_w = em_width; a.em_h = em_height;
+	return run_compute_loss(ds, cfg, stream, a);
+}
+
+int ngp_nerf_compute_loss_envmap(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
+                                 uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples_compacted, const uint32_t* ray_counter,
+                                 const void* network_output, const uint32_t* ray_indices, const float* rays, uint32_t* numsteps,
+                                 const float* coords_in, float* coords_out, void* dloss_doutput, float* loss,
+                                 uint32_t* compacted_counter, const float* mean_density, float loss_scale, const float* envmap,
+                                 uint32_t env_width, uint32_t env_height, uint32_t envmap_loss_type, float* envmap_gradient) {
+	if (!envmap || !rays || !envmap_dims_ok(env_width, env_height) || envmap_loss_type > LOSS_RELL2) return NGP_INVALID;
+	NERF_TRY({
+		static thread_local Buf acc;
+		LossArgs a = public_loss_args(n_rays, n_rays_total, rng, max_samples_compacted, ray_counter, network_output, ray_indices, rays,
+		                              numsteps, coords_in, coords_out, dloss_doutput, loss, compacted_counter, mean_density, loss_scale);
+		a.envmap = envmap; a.env_w = env_width; a.env_h = env_height; a.env_loss_type = envmap_loss_type;
+		if (envmap_gradient) {
+			const size_t words = envmap_acc_words64(env_width, env_height);
+			a.env_acc = acc.get<unsigned long long>(words);
+			NGP_HIP(hipMemsetAsync(a.env_acc, 0, words * 8, S(stream)));
+		}
+		const int rc = run_compute_loss(ds, cfg, stream, a);
+		if (rc != NGP_OK) return rc;  // the error string is set
+		if (envmap_gradient) envmap_gradient_f32(env_width, env_height, a.env_acc, envmap_gradient, S(stream));
+	});
+}
+
+int ngp_envmap_lookup(void* stream, uint32_t width, uint32_t height, uint32_t n, const float* dirs, uint32_t* texels, float* weights) {
+	if (!envmap_dims_ok(width, height) || (n && (!dirs || !texels || !weights))) return NGP_INVALID;
+	NERF_TRY({ envmap_lookup_device(width, height, n, dirs, texels, weights, S(stream)); });
+}
+
+int ngp_envmap_lookup_host(uint32_t width, uint32_t height, uint32_t n, const float* dirs, uint32_t* texels, float* weights) {
+	if (!envmap_dims_ok(width, height) || (n && (!dirs || !texels || !weights))) return NGP_INVALID;
+	envmap_lookup_host(width, height, n, dirs, texels, weights);
+	return NGP_OK;
+}
+
+int ngp_envmap_deposit(void* stream, uint32_t width, uint32_t height, uint32_t n, const float* dirs, const void* values_f16,
+                       float* gradient) {
+	if (!envmap_dims_ok(width, height) || !gradient || (n && (!dirs || !values_f16))) return NGP_INVALID;
+	NERF_TRY({
+		static thread_local Buf acc;
+		const size_t words = envmap_acc_words64(width, height);
+		unsigned long long* a = acc.get<unsigned long long>(words);
+		NGP_HIP(hipMemsetAsync(a, 0, words * 8, S(stream)));
+		envmap_deposit_values(width, height, n, dirs, (const f16*)values_f16, a, S(stream));
+		envmap_gradient_f32(width, height, a, gradient, S(stream));
+	});
+}
+
+int ngp_envmap_optimizer_step(void* stream, const char* optimizer_json, uint32_t step, float loss_scale, uint32_t n, float* params,
+                              const float* gradient, float* first_moments, float* second_moments, uint32_t* param_steps, float* ema,
+                              float* ema_params) {
+	if (!optimizer_json || !params || !gradient || !first_moments || !second_moments || !param_steps || !(loss_scale > 0.f))
+		return NGP_INVALID;
+	NERF_TRY({
+		AdamConfig c;
+		parse_optimizer_json(optimizer_json, c);
+		AdamState st{};
+		st.w32 = params; st.g32 = gradient; st.m1 = first_moments; st.m2 = second_moments; st.steps = param_steps;
+		st.ema32 = ema; st.ema_f32 = ema_params; st.step_add = step;
+		adam_ema_update_f32(c, n, loss_scale, st, S(stream));
+	});
+}
+
+int ngp_nerf_fill_rollover(void* stream, uint32_t n_elements, uint32_t stride, const uint32_t* n_input, void* data, int dtype,
+                           int rescale) {
+	if (!n_input || !data) return NGP_INVALID;
+	NERF_TRY({
+		if (dtype == 1) fill_rollover_f16(n_elements, stride, n_input, (f16*)data, rescale != 0, S(stream));
+		else fill_rollover_f32(n_elements, stride, n_input, (float*)data, S(stream));
+	});
+}
+
+int ngp_nerf_grid_generate_samples(void* stream, const ngp_nerf_config* cfg, uint32_t n, ngp_rng rng, uint32_t step,
+                                   const float* grid, uint32_t n_cascades, float thresh, float* positions, uint32_t* indices) {
+	if (!cfg || !grid || !positions || !indices) return NGP_INVALID;
+	NERF_TRY({
+		static thread_local Buf mask;
+		grid_generate_samples(n, Rng{rng.state, rng.inc}, step, *cfg, grid, n_cascades, thresh, positions, indices,
+		                      mask.get<uint32_t>(grid_mask_words(n_cascades)), S(stream));
+	});
+}
+int ngp_nerf_grid_splat_max(void* stream, uint32_t n, const uint32_t* indices, const void* density_rm, uint32_t act, float* tmp) {
+	if (!indices || !density_rm || !tmp) return NGP_INVALID;
+	NERF_TRY(grid_splat_max(n, indices, (const f16*)density_rm, act, tmp, S(stream)));
+}
+int ngp_nerf_grid_splat_max_cells(void* stream, uint32_t n, const uint32_t* indices, const void* density_rm, uint32_t act,
+                                  float* tmp, uint32_t n_cells) {
+	if ((n && (!indices || !density_rm)) || !tmp || n_cells == 0 || n_cells % 8192 || n_cells > 8 * GRID_N_CELLS) return NGP_INVALID;
+	NERF_TRY({
+		static thread_local Buf scratch;
+		grid_splat_max_binned(n, indices, (const f16*)density_rm, act, tmp, n_cells,
+		                      scratch.get<uint32_t>(grid_splat_scratch_u32(n, n_cells)), S(stream));
+	});
+}
+int ngp_nerf_grid_ema(void* stream, uint32_t n, float decay, float* grid, const float* tmp) {
+	if (!grid || !tmp) return NGP_INVALID;
+	NERF_TRY(grid_ema(n, decay, grid, tmp, S(stream)));
+}
+int ngp_nerf_grid_mean_and_bitfield(void* stream, const float* grid, uint32_t max_cascade, float* mean, uint8_t* bitfield) {
+	if (!grid || !mean || !bitfield || max_cascade >= CASCADES) return NGP_INVALID;
+	NERF_TRY(grid_mean_bitfield(grid, max_cascade, mean, bitfield, S(stream)));
+}
+
+// ---- rendering ---------------------------------------------------------------------------------
+int ngp_nerf_renderer_create(ngp_nerf_renderer** out) {
+	if (!out) return NGP_INVALID;
+	NERF_TRY({ *out = new ngp_nerf_renderer(); });
+}
+void ngp_nerf_renderer_destroy(ngp_nerf_renderer* r) { delete r; }
+int ngp_nerf_renderer_set_mode(ngp_nerf_renderer* r, int render_mode) {
+	if (!r || render_mode < (int)RENDER_AO || (render_mode > (int)RENDER_DEPTH && render_mode != (int)RENDER_ENCODING_VIS))
+		return NGP_INVALID;
+	r->render_mode = (uint32_t)render_mode;
+	return NGP_OK;
+}
+int ngp_nerf_renderer_set_show_accel(ngp_nerf_renderer* r, int show_accel) {
+	if (!r || show_accel < -1 || show_accel >= (int)CASCADES) return NGP_INVALID;
+	r->show_accel = show_accel;
+	return NGP_OK;
+}
+int ngp_nerf_renderer_set_depth_scale(ngp_nerf_renderer* r, float depth_scale) {
+	if (!r) return NGP_INVALID;
+	r->depth_scale = depth_scale;
+	return NGP_OK;
+}
+int ngp_nerf_renderer_set_envmap(ngp_nerf_renderer* r, const float* envmap, uint32_t width, uint32_t height) {
+	if (!r || (envmap && !envmap_dims_ok(width, height))) return NGP_INVALID;
+	r->envmap = envmap;
+	r->env_w = envmap ? width : 0;
+	r->env_h = envmap ? height : 0;
+	return NGP_OK;
+}
+
+int ngp_nerf_render(ngp_nerf_renderer* r, ngp_model* model, const ngp_nerf_config* cfg, void* stream, const ngp_nerf_image* camera,
+                    const uint8_t* bitfield, uint32_t spp, uint32_t sample_index, float min_transmittance, const float* background_rgba,
+                    int use_inference_params, float* out_rgba) {
+	if (!r || !model || !cfg || !camera || !out_rgba || spp == 0) return NGP_INVALID;
+	NERF_TRY({
+		hipStream_t s = S(stream);
+		RenderArgs a{};
+		a.width = camera->width; a.height = camera->height;
+		a.focal[0] = camera->focal_length[0]; a.focal[1] = camera->focal_length[1];
+		// m_screen_center = 1 - principal point (set_camera_to_training_view, testbed.cu:852), then
+		// render_screen_center (testbed.cu:4376-4379, zoom 1): (0.5 - m_screen_center) + 0.5 = principal point
+		for (int k = 0; k < 2; ++k) a.screen_center[k] = (0.5f - (1.0f - camera->principal_point[k])) * 1.0f + 0.5f;
+		effective_camera_matrix(camera->xform, a.cam);
+		NGP_CHECK(camera->lens_mode <= LENS_OPENCV_FISHEYE, "render: unsupported lens mode");
+		a.lens_mode = camera->lens_mode;
+		for (int k = 0; k < 4; ++k) a.lens[k] = camera->lens_params[k];
+		a.near_distance = 0.0f;  // m_render_near_distance (testbed.h:914)
+		for (int k = 0; k < 3; ++k) { a.aabb_min[k] = cfg->aabb_min[k]; a.aabb_max[k] = cfg->aabb_max[k]; }
+		a.cone_angle_constant = cfg->cone_angle_constant;
+		a.max_mip = cfg->max_cascade;
+		a.bitfield = bitfield;
+		a.sample_index = sample_index;
+		a.snap_to_pixel_centers = cfg->snap_to_pixel_centers;
+		a.linear_colors = cfg->linear_colors;
+		a.rgb_activation = cfg->rgb_activation;
+		a.density_activation = cfg->density_activation;
+		a.min_transmittance = min_transmittance;
+		for (int k = 0; k < 4; ++k) a.background[k] = background_rgba ? background_rgba[k] : 0.f;
+		const uint32_t n_px = a.width * a.height;
+		const size_t max_q = (size_t)std::max(n_px, 2u * 1024 * 1024) + 256;
+		RenderWorkspace ws{};
+		const size_t pb = render_payload_bytes();
+		ws.payload[0] = r->pay0.get<char>(pb * n_px);
+		ws.payload[1] = r->pay1.get<char>(pb * n_px);
+		ws.payload_hit = r->payh.get<char>(pb * n_px);
+		ws.rgba[0] = r->rgba0.get<float>(4 * (size_t)n_px);
+		ws.rgba[1] = r->rgba1.get<float>(4 * (size_t)n_px);
+		ws.rgba_hit = r->rgbah.get<float>(4 * (size_t)n_px);
+		ws.coords = r->coords.get<float>(7 * max_q);
+		ws.out = r->out.get<f16>(16 * max_q);
+		ws.frame = r->frame.get<float>(4 * (size_t)n_px);
+		ws.counters = r->counters.get<uint32_t>(2);
+		if (!r->host_counters) NGP_HIP(hipHostMalloc(&r->host_counters, 16));
+		ws.host_counters = r->host_counters;
+		a.render_mode = r->render_mode;
+		a.depth_scale = r->depth_scale;
+		a.show_accel = r->show_accel;
+		a.envmap = r->envmap; a.env_w = r->env_w; a.env_h = r->env_h;
+		auto infer =[&](uint32_t n, const float* coords, f16* out) {
+			check_rc(ngp_inference(model, s, n, coords, 7, out, n, NGP_LAYOUT_SOA, use_inference_params));
+		};
+		// Normals: tcnn input_gradient's default backprop_scale (128); it reads the inference parameters
+		auto grad = [&](uint32_t n, float* coords) {
+			check_rc(ngp_input_gradient(model, s, 3, n, coords, 7, coords, 7, 128.0f));
+		};
+		render_frame(a, spp, ws, infer, out_rgba, s, grad);
+	});
+}
+
+}  // extern "C"

@@ -1,312 +1,16 @@
-// nerf_trainer.hip — C-ABI for the NeRF kernels and the Testbed-level NeRF training step.
+// nerf_trainer.hip — the Testbed-level NeRF trainer: create / destroy, its setters and getters, the density-grid
+// update and the training step in its stages. The trainer object itself is in nerf_host.h; the sampler and loss
+// wrappers the step calls (run_sampler, run_compute_loss) are in nerf_abi.hip, snapshots in nerf_snapshot.hip.
 //
 // ngp_nerf_train_step mirrors Testbed::train for NeRF (src/testbed.cu:4285-4370): training_prep_nerf
 // (occupancy-grid update every clamp(step/16, 1, 16) steps, testbed_nerf.cu:4137-4152) then
 // train_nerf (testbed_nerf.cu:3611-3862): sample -> inference over every sample -> loss/compaction
 // -> rollover -> forward/backward on the compacted batch -> optimizer step -> counters (host sync) ->
 // rays_per_batch adaptation.
-#include <cmath>
-#include <cstring>
-#include <memory>
-#include <string>
-#include <vector>
-
-#include <zlib.h>
-
 #include <chrono>
-#include <fstream>
-#include <sstream>
 
-#include "engine_internal.h"
-#include "json.h"
-#include "knobs.h"
-#include "msgpack.h"
-#include "nerf.h"
-#include "nerf_camera.h"
-#include "optimizer.h"
+#include "nerf_host.h"
 #include "profiler.h"
-
-using namespace ngp;
-using namespace ngp::nerf;
-
-struct ngp_nerf_dataset {
-	Dataset ds;
-};
-
-namespace {
-
-struct HostPcg {  // tcnn::pcg32 (host) for the Testbed's m_rng / density_grid_rng
-	uint64_t state, inc;
-	explicit HostPcg(uint64_t initstate, uint64_t initseq = 1u) {
-		state = 0u; inc = (initseq << 1u) | 1u; next_uint(); state += initstate; next_uint();
-	}
-	uint32_t next_uint() {
-		const uint64_t old = state;
-		state = old * 0x5851f42d4c957f2dULL + inc;
-		const uint32_t xs = (uint32_t)(((old >> 18u) ^ old) >> 27u), rot = (uint32_t)(old >> 59u);
-		return (xs >> rot) | (xs << ((~rot + 1u) & 31));
-	}
-	void advance(uint64_t delta = (1ull << 32)) {
-		uint64_t cm = 0x5851f42d4c957f2dULL, cp = inc, am = 1u, ap = 0u;
-		while (delta > 0) {
-			if (delta & 1) { am *= cm; ap = ap * cm + cp; }
-			cp = (cm + 1) * cp; cm *= cm; delta /= 2;
-		}
-		state = am * state + ap;
-	}
-	Rng dev() const { return Rng{state, inc}; }
-};
-
-struct Buf {
-	void* p = nullptr;
-	size_t n = 0;
-	template <typename T> T* get(size_t count) {
-		const size_t need = count * sizeof(T);
-		if (need > n) {
-			if (p) NGP_HIP(hipFree(p));
-			NGP_HIP(hipMalloc(&p, need));
-			n = need;
-		}
-		return (T*)p;
-	}
-	~Buf() { if (p) (void)hipFree(p); }
-};
-
-// One cross-queue handoff: the producer's stream signals, the consumer's stream waits for the latest signal. By
-// event, or by value (hipStreamWriteValue32 / hipStreamWaitValue32 on signal memory): a queue idling on a pending
-// event wait starts its next kernel ~10 us after the event's work ends, on a pending value wait ~6 us; a wait that
-// finds its signal complete costs ~1.3 us by event against ~3.6 by value (tools/microbench/queue_handoff.hip,
-// profiles/r06s_queue_handoff.jsonl; sampler -> inference by value: Lego step 0.433 -> 0.428 ms, fox 0.542 -> 0.535).
-struct Handoff {
-	bool by_value = false;
-	hipEvent_t ev = nullptr;
-	uint32_t* sig = nullptr;  // signal memory: only a by-value handoff allocates it
-	uint32_t seq = 0;
-	void signal(hipStream_t producer) {
-		if (by_value) {
-			if (!sig) {
-				NGP_HIP(hipExtMallocWithFlags((void**)&sig, 8, hipMallocSignalMemory));
-				NGP_HIP(hipMemset(sig, 0, 8));
-			}
-			NGP_HIP(hipStreamWriteValue32(producer, sig, ++seq, 0));
-		} else {
-			if (!ev) NGP_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-			NGP_HIP(hipEventRecord(ev, producer));
-		}
-	}
-	void wait(hipStream_t consumer) const {
-		if (!sig && !ev) return;  // never signalled: nothing to wait for
-		if (by_value) NGP_HIP(hipStreamWaitValue32(consumer, sig, seq, hipStreamWaitValueGte, 0xFFFFFFFFu));
-		else NGP_HIP(hipStreamWaitEvent(consumer, ev, 0));
-	}
-	~Handoff() {
-		if (ev) (void)hipEventDestroy(ev);
-		if (sig) (void)hipFree(sig);
-	}
-};
-
-}  // namespace
-
-// external engine entry points used by the orchestrator
-extern "C" int ngp_inference(ngp_model*, void*, uint32_t, const float*, uint32_t, void*, uint32_t, uint32_t, int);
-extern "C" int ngp_density(ngp_model*, void*, uint32_t, const float*, uint32_t, void*, uint32_t, uint32_t, int);
-extern "C" int ngp_forward_backward(ngp_model*, void*, uint32_t, const float*, uint32_t, void*, uint32_t, const void*, uint32_t, int);
-extern "C" int ngp_trainer_optimizer_step(ngp_trainer*, void*, float);
-extern "C" void* ngp_trainer_gradients(ngp_trainer*);
-extern "C" uint64_t ngp_model_n_params(const ngp_model*);
-extern "C" const char* ngp_last_error(void);
-
-struct ngp_nerf_renderer {
-	Buf pay0, pay1, payh, rgba0, rgba1, rgbah, coords, out, frame, counters;
-	const float* envmap = nullptr;        // ngp_nerf_renderer_set_envmap (the caller's device memory)
-	uint32_t env_w = 0, env_h = 0;
-	uint32_t* host_counters = nullptr;
-	uint32_t render_mode = RENDER_SHADE;  // ngp_nerf_renderer_set_mode
-	int32_t show_accel = -1;             // ngp_nerf_renderer_set_show_accel
-	float depth_scale = 1.0f;             // ngp_nerf_renderer_set_depth_scale
-	~ngp_nerf_renderer() { if (host_counters) (void)hipHostFree(host_counters); }
-};
-
-struct ngp_nerf_trainer {
-	const NerfKnobs knobs = NerfKnobs::read();  // at creation (knobs.h)
-	ngp_model* model;
-	ngp_trainer* trainer;
-	const ngp_nerf_dataset* data;
-	ngp_nerf_config cfg;
-	HostPcg rng{1337}, grid_rng{1};
-	uint32_t training_step = 0, ema_step = 0;
-	uint32_t rays_per_batch = 1u << 12;  // testbed.h:440
-	uint32_t n_rays_total = 0;
-	uint32_t measured_batch_size = 0, measured_before_compaction = 0;
-	uint32_t measured_before_compaction_local = 0;  // this rank's pre-compaction count (inference sizing)
-	float loss_scalar = 0.f;  // m_loss_scalar (last step that computed the loss)
-	// the training pass (forward_backward + optimizer over the fixed compacted batch) replayed as one
-	// HIP graph per step; re-captured if its buffers move
-	ngp_graph* train_graph = nullptr;
-	const void* graph_in = nullptr;
-	const void* graph_dl = nullptr;
-	uint32_t graph_n = 0;
-	uint64_t graph_epoch = 0;  // model workspace epoch at capture (ngp_model_workspace_epoch)
-	hipStream_t own_stream = nullptr;  // used when the caller passes the null stream (graphs need a stream)
-	// per-step counters published by the step's last kernel into host-coherent pinned memory, read by
-	// spinning on a sequence number (no copy-engine transfer, no blocking stream synchronize)
-	volatile uint32_t* host_ctr = nullptr;
-	uint32_t publish_seq = 0;
-	// Sampler pipelining: the next step's ray sampling depends on the occupancy bitfield, the rng and the
-	// rays-per-batch count, not on the network, so (when no density-grid update is due before it) it is
-	// launched on `sample_stream` as soon as this step's loss pass has released the sample buffers and
-	// runs concurrently with this step's training pass. Same kernels, same inputs: same samples.
-	bool pipeline = true;                // ngp_nerf_trainer_set_pipeline
-	bool prelaunched = false;
-	uint32_t pre_R = 0, pre_max_inference = 0;
-	hipStream_t sample_stream = nullptr;
-	// prelaunched sampler -> this step's inference (the consumer is usually already waiting: by value), and the step's
-	// release of the sample buffers -> the next sampler (long done when the host launches that sampler: by event; the
-	// release by value too: Lego 0.427, fox 0.538 ms; not used under early())
-	Handoff sampled{knobs.waitval != 0}, released{knobs.waitval == 2};
-	// Density-grid update pipelining: when the next step is due an update, its sample generation and bin sort read
-	// only the grid (unchanged until that update) and the grid rng, so they run on `sample_stream` under this step's
-	// training pass, after the update before it (grid_updated: that one wrote the grid they read and read the buffers
-	// they write); the update then starts at the density evaluation (pregenerated). Discarding them restores the rng.
-	bool grid_pregen = false;
-	uint32_t pregen_nu = 0, pregen_nn = 0;
-	Handoff pregenerated, grid_updated;
-	HostPcg pregen_rng{1};  // grid_rng before the pregenerated samples
-	void drain() {  // the prelaunched sampler finished and discarded (state is about to change)
-		if (sample_stream) (void)hipStreamSynchronize(sample_stream);
-		prelaunched = false;
-		if (grid_pregen) grid_rng = pregen_rng;
-		grid_pregen = false;
-	}
-	~ngp_nerf_trainer() {
-		drain();
-		if (train_graph) ngp_graph_destroy(train_graph);
-		if (own_stream) (void)hipStreamDestroy(own_stream);
-		if (sample_stream) (void)hipStreamDestroy(sample_stream);
-		if (host_ctr) (void)hipHostFree((void*)host_ctr);
-		if (d_cams) (void)hipFree(d_cams);
-		if (d_raw) (void)hipFree(d_raw);
-		ngp_pose_optimizer_destroy(pose);
-	}
-	// data parallelism: rank r traces global rays [R r / N, R (r+1) / N), compacts to B / N,
-	// evaluates 1/N of the density-grid samples; the exchange steps go through `allreduce`
-	uint32_t rank = 0, world = 1;
-	ngp_allreduce_fn allreduce = nullptr;
-	void* allreduce_user = nullptr;
-	bool dp_capturable = false;  // the hook is the engine's RCCL communicator: the DP training pass is a graph
-	Buf dp_scalars;
-	bool dp() const { return allreduce != nullptr; }
-	// the training pass's exchange: the shards' dL/doutput is already scaled by 128 / R_global, so the summed
-	// gradient is the 1-GPU gradient (world factor 1)
-	ngp::Exchange exchange() const {
-		ngp::Exchange e;
-		e.fn = allreduce; e.user = allreduce_user; e.rank = rank; e.world = world; e.world_factor = 1.f;
-		e.rank_known = allreduce != nullptr;
-		return e;
-	}
-	// occupancy grid
-	Buf grid, grid_tmp, bitfield, mean, gpos, gidx, gdens, grid_mask, splat_scratch, gpos_sorted;
-	// training workspaces
-	Buf mlp_out, dloss, coords_c, loss, scan_tmp, tmp_u32, tmp_f32;
-	struct SampleSet { Buf ray_indices, rays, numsteps, coords, counters; } sets[2];  // the second one: early()
-	// Early publish (one GPU): the counters are published by the loss's scan, so the host launches the next step's
-	// sampler while this step's loss pass 2, rollover and training pass still run; the sampler's outputs then
-	// alternate between two sets by step parity (the set it writes was last read two steps before), so it waits on
-	// nothing. Default under cone stepping only (aabb_scale > 1: the count pass, ~1.5x the training pass, is the
-	// step's critical path; fox 0.517 -> 0.499 ms); at cone 0 the two are balanced and a count pass already resident
-	// when the training pass starts keeps its one-wave-per-SIMD MLP kernel off the SIMDs (Lego 0.421 -> 0.440 ms,
-	// gpurun_out/r06bd). NGP_NERF_EARLY=1: always, 0: never (publish in the rollover, one set, the sampler waits
-	// for this step's release).
-	bool early() const {
-		const bool on = knobs.early < 0 ? cfg.cone_angle_constant > 1e-5f : knobs.early != 0;
-		return on && !dp();
-	}
-	// The sampler's outputs alternate between the two sets: under early publish, and with camera pose refinement, whose
-	// gradient kernels read the ray buffers after the training pass: the next sampler, prelaunched under that pass,
-	// then writes the other set (last read by the step before this one, complete once this step's counters are
-	// published) instead of waiting for this step's release
-	bool two_sets() const { return early() || (cam.optimize_extrinsics != 0 && !dp()); }
-	Buf loss_state;  // compute_loss: pass 1's per-sample compositing state for pass 2 (LossArgs::state)
-	// Camera pose refinement (Testbed::Nerf::Training::optimize_extrinsics and its neighbours, testbed.h:716-785). The
-	// trainer traces its own device copy of the cameras: the dataset's array to begin with (bit for bit), rebuilt from
-	// `xforms` and the per-camera offsets (ngp_pose_apply, then effective_camera_matrix) whenever those change; d_raw
-	// is the raw-transform array mark_untrained_density_grid reads, refreshed the same way.
-	ngp_nerf_camera_training cam{0, 16, 1e-4f, 1e-3f};
-	ngp_pose_optimizer* pose = nullptr;
-	std::vector<float> xforms;   // [n_images x 12] the transforms the offsets apply to (set_camera_extrinsics writes them)
-	std::vector<Camera> cams;    // host mirror of d_cams
-	Camera* d_cams = nullptr;
-	float* d_raw = nullptr;
-	uint32_t n_steps_since_cam_update = 0;
-	Buf cam_grad, cam_ray_grad, dinput;  // [2][n_images x 3] accumulators {pos, rot}; per-ray workspace; dL/dinput [B x 7]
-	const float* graph_dinput = nullptr;  // the gradient pointer the training graph was captured with
-	// the last step's sampler call, for ngp_nerf_trainer_last_samples
-	ngp_rng last_rng{0, 0};
-	uint32_t last_n_rays = 0, last_max_samples = 0;
-	const uint32_t* last_ray_indices = nullptr;
-	const float* last_rays = nullptr;
-	const uint32_t* last_counters = nullptr;
-	void refined_xform(uint32_t i, float out[12]) const;
-	void rebuild_cameras(hipStream_t s);
-	// training error map (Testbed::Nerf::Training::ErrorMap and its update window, testbed.h:668-677, 736-738)
-	Buf em_data, em_cdf_x, em_cdf_y, em_cdf_img;
-	uint32_t em_w = 0, em_h = 0, em_cdf_w = 0, em_cdf_h = 0;
-	uint32_t em_steps_since = 0, em_steps_between = 128;
-	bool em_cdf_valid = false;
-	std::vector<float> em_pmf_img;  // pmf_img_cpu
-	// Error-driven sampling (Training::sample_focal_plane_proportional_to_error / sample_image_proportional_to_error,
-	// testbed.h:733-734): once a window has closed, a step's sampler and its loss pass draw the rays' pixels from the
-	// CDFs of the last closed window (testbed_nerf.cu:3948-3949). Both off: the uniform kernels, nothing else changes.
-	bool sample_focal_plane_by_error = false, sample_image_by_error = false;
-	bool error_sampling() const { return sample_focal_plane_by_error || sample_image_by_error; }
-	// Environment map (Testbed::m_envmap and Training::train_envmap; testbed.cu:4133-4147, testbed_nerf.cu:3668-3685):
-	// fp32 RGBA parameters [h][w][4] behind every training ray, their EMA for rendering, and with `train` on a
-	// gradient summed exactly per step (envmap.h) and an optimizer step of their own after every loss pass. Not set:
-	// the step issues exactly the launches it would without any of this.
-	struct Envmap {
-		uint32_t w = 0, h = 0;
-		Buf params, ema, ema_out, m1, m2, steps, grad, acc;
-		uint32_t step = 0;         // optimizer steps taken
-		bool ema_valid = false;    // ema_out holds the debiased EMA of a step under an Ema wrapper (or a snapshot's)
-		AdamConfig opt;            // the "envmap" section's optimizer; opt_set false: the main trainer's
-		bool opt_set = false;
-		int32_t loss_type = -1;    // the "envmap" section's loss; -1: cfg.loss_type
-		bool train = false;
-		size_t n() const { return (size_t)w * h * 4; }
-		bool bound() const { return w != 0; }
-	} env;
-	const AdamConfig& envmap_optimizer() const { return env.opt_set ? env.opt : trainer_adam_config(trainer); }
-	uint32_t envmap_loss_type() const { return env.loss_type < 0 ? cfg.loss_type : (uint32_t)env.loss_type; }
-	// what rendering reads (inference_view): the debiased EMA once a step has been taken under an Ema wrapper
-	const float* envmap_inference() const {
-		return (const float*)(env.ema_valid ? env.ema_out.p : env.params.p);
-	}
-	ErrorCdfs sampling_cdfs() const {
-		ErrorCdfs e{};
-		if (!em_cdf_valid || !em_cdf_w || !em_cdf_h) return e;
-		if (sample_image_by_error) e.cdf_img = (const float*)em_cdf_img.p;
-		if (sample_focal_plane_by_error) {
-			e.cdf_x_cond_y = (const float*)em_cdf_x.p; e.cdf_y = (const float*)em_cdf_y.p;
-			e.w = em_cdf_w; e.h = em_cdf_h;
-		}
-		return e;
-	}
-};
-
-static hipStream_t S(void* s) { return (hipStream_t)s; }
-
-#define NERF_TRY(...)                                  \
-	try {                                              \
-		__VA_ARGS__;                                   \
-		return NGP_OK;                                 \
-	} catch (const std::exception& e) {                \
-		nerf_set_error(e.what());                      \
-		return NGP_ERROR;                              \
-	}
-
-// share the engine's thread-local error string through a tiny hook in engine.hip
-namespace ngp { void set_last_error(const char* msg); }
-static void nerf_set_error(const char* m) { ngp::set_last_error(m); }
 
 // mark_untrained_density_grid (testbed_nerf.cu:503-592) for perspective and OpenCV(-fisheye) cameras
 __global__ void k_mark_untrained(uint32_t n_elements, float* __restrict__ grid, uint32_t n_images, const Camera* __restrict__ cams,
@@ -366,331 +70,6 @@ __global__ void k_mark_untrained(uint32_t n_elements, float* __restrict__ grid, 
 
 extern "C" {
 
-int ngp_nerf_default_config(float aabb_scale, ngp_nerf_config* o) {
-	if (!o || !(aabb_scale >= 1.0f)) return NGP_INVALID;
-	memset(o, 0, sizeof(*o));
-	const float inflate = 0.5f * std::min((float)(1 << (CASCADES - 1)), aabb_scale);  // testbed_nerf.cu:3093-3094
-	for (int k = 0; k < 3; ++k) { o->aabb_min[k] = 0.5f - inflate; o->aabb_max[k] = 0.5f + inflate; }
-	uint32_t mc = 0;
-	while ((float)(1u << mc) < aabb_scale) ++mc;  // :3102-3105
-	o->max_cascade = mc;
-	o->cone_angle_constant = aabb_scale <= 1.0f ? 0.0f : 1.0f / 256.0f;  // :3109
-	o->snap_to_pixel_centers = 1;
-	o->random_bg_color = 1;
-	o->linear_colors = 0;
-	o->color_space_linear = 1;
-	o->rgb_activation = ACT_EXP;
-	o->density_activation = ACT_EXP;
-	o->loss_type = LOSS_HUBER;  // configs/nerf/base.json "loss": Huber
-	o->near_distance = 0.1f;
-	o->target_batch_size = 1u << 18;
-	return NGP_OK;
-}
-
-int ngp_nerf_dataset_create(uint32_t n_images, const ngp_nerf_image* images, const void* const* rgba8, ngp_nerf_dataset** out) {
-	if (!out || !images || !rgba8 || n_images == 0) return NGP_INVALID;
-	NERF_TRY({
-		auto d = std::make_unique<ngp_nerf_dataset>();
-		d->ds.n_images = n_images;
-		uint64_t total = 0;
-		std::vector<Camera> cams(n_images);
-		for (uint32_t i = 0; i < n_images; ++i) {
-			const ngp_nerf_image& im = images[i];
-			Camera& c = cams[i];
-			c.width = im.width; c.height = im.height;
-			c.focal[0] = im.focal_length[0]; c.focal[1] = im.focal_length[1];
-			c.principal[0] = im.principal_point[0]; c.principal[1] = im.principal_point[1];
-			NGP_CHECK(im.lens_mode <= LENS_OPENCV_FISHEYE, "nerf dataset: unsupported lens mode");
-			c.lens_mode = im.lens_mode;
-			for (int k = 0; k < 4; ++k) c.lens[k] = im.lens_params[k];
-			effective_camera_matrix(im.xform, c.m);
-			c.pixel_offset = total;
-			total += (uint64_t)im.width * im.height;
-		}
-		NGP_HIP(hipMalloc(&d->ds.d_pixels, total * 4 + 12 * 4 * n_images));
-		for (uint32_t i = 0; i < n_images; ++i)
-			NGP_HIP(hipMemcpy(d->ds.d_pixels + cams[i].pixel_offset, rgba8[i], (size_t)images[i].width * images[i].height * 4,
-			                  hipMemcpyHostToDevice));
-		// raw (start) transforms after the pixels, for mark_untrained_density_grid
-		std::vector<float> raw(12 * n_images);
-		for (uint32_t i = 0; i < n_images; ++i) memcpy(&raw[12 * i], images[i].xform, 48);
-		NGP_HIP(hipMemcpy(d->ds.d_pixels + total, raw.data(), raw.size() * 4, hipMemcpyHostToDevice));
-		d->ds.xforms = raw;
-		NGP_HIP(hipMalloc(&d->ds.d_cams, n_images * sizeof(Camera)));
-		NGP_HIP(hipMemcpy(d->ds.d_cams, cams.data(), n_images * sizeof(Camera), hipMemcpyHostToDevice));
-		d->ds.cams = cams;
-		*out = d.release();
-	});
-}
-
-void ngp_nerf_dataset_destroy(ngp_nerf_dataset* d) { delete d; }
-
-// ngp_nerf_error_cdfs -> ErrorCdfs (null: none). The position CDFs come as a pair with a resolution; without
-// cdf_x_cond_y the other two members are not looked at.
-static bool error_cdfs_arg(const ngp_nerf_error_cdfs* c, ErrorCdfs* out) {
-	*out = ErrorCdfs{};
-	if (!c) return true;
-	out->cdf_img = c->cdf_img;
-	if (c->cdf_x_cond_y) {
-		if (!c->cdf_y || c->width == 0 || c->height == 0) return false;
-		out->cdf_x_cond_y = c->cdf_x_cond_y; out->cdf_y = c->cdf_y; out->w = c->width; out->h = c->height;
-	}
-	return true;
-}
-
-// ngp_nerf_generate_training_samples, optionally tracing `cams` instead of the dataset's cameras and drawing the
-// rays' pixels from the error map's CDFs
-static int generate_training_samples(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
-                                     uint32_t ray_offset, uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples,
-                                     const uint8_t* bitfield, uint32_t* ray_indices, float* rays, uint32_t* numsteps,
-                                     float* coords, uint32_t* counters, const Camera* cams, const ErrorCdfs& cdfs = ErrorCdfs{}) {
-	if (!ds || !cfg || !bitfield || !ray_indices || !rays || !numsteps || !coords || !counters) return NGP_INVALID;
-	NERF_TRY({
-		SampleArgs a{};
-		a.cdfs = cdfs;
-		a.n_rays = n_rays; a.ray_offset = ray_offset; a.n_rays_total_for_image_idx = n_rays_total ? n_rays_total : n_rays;
-		a.max_samples = max_samples; a.rng = Rng{rng.state, rng.inc}; a.bitfield = bitfield;
-		a.ray_indices = ray_indices; a.rays = rays; a.numsteps = numsteps; a.coords = coords; a.counters = counters;
-		static thread_local Buf tmp, tmpf;
-		if (n_rays == 0) { NGP_HIP(hipMemsetAsync(counters, 0, 8, S(stream))); return NGP_OK; }
-		sample_rays(ds->ds, *cfg, a, tmp.get<uint32_t>(sample_tmp_u32(n_rays)), tmpf.get<float>(sample_tmp_f32(n_rays)), S(stream), cams);
-	});
-}
-int ngp_nerf_generate_training_samples(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
-                                       uint32_t ray_offset, uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples,
-                                       const uint8_t* bitfield, uint32_t* ray_indices, float* rays, uint32_t* numsteps,
-                                       float* coords, uint32_t* counters) {
-	return generate_training_samples(ds, cfg, stream, n_rays, ray_offset, n_rays_total, rng, max_samples, bitfield, ray_indices, rays,
-	                                 numsteps, coords, counters, nullptr);
-}
-int ngp_nerf_generate_training_samples_cdf(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
-                                           uint32_t ray_offset, uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples,
-                                           const uint8_t* bitfield, uint32_t* ray_indices, float* rays, uint32_t* numsteps,
-                                           float* coords, uint32_t* counters, const ngp_nerf_error_cdfs* cdfs) {
-	ErrorCdfs e;
-	if (!error_cdfs_arg(cdfs, &e)) return NGP_INVALID;
-	return generate_training_samples(ds, cfg, stream, n_rays, ray_offset, n_rays_total, rng, max_samples, bitfield, ray_indices, rays,
-	                                 numsteps, coords, counters, nullptr, e);
-}
-
-int ngp_nerf_training_pixels(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays, uint32_t ray_offset,
-                             uint32_t n_rays_total, ngp_rng rng, const ngp_nerf_error_cdfs* cdfs, uint32_t* img, float* uv, float* pdf) {
-	ErrorCdfs e;
-	if (!ds || !cfg || !img || !uv || !pdf || !error_cdfs_arg(cdfs, &e)) return NGP_INVALID;
-	NERF_TRY(training_pixels(ds->ds, *cfg, n_rays, ray_offset, n_rays_total ? n_rays_total : n_rays, Rng{rng.state, rng.inc}, e, img, uv,
-	                         pdf, S(stream)));
-}
-int ngp_nerf_training_pixels_host(uint32_t n_images, const ngp_nerf_image* images, const ngp_nerf_config* cfg, uint32_t n_rays,
-                                  uint32_t ray_offset, uint32_t n_rays_total, ngp_rng rng, const ngp_nerf_error_cdfs* cdfs,
-                                  uint32_t* img, float* uv, float* pdf) {
-	ErrorCdfs e;
-	if (!images || n_images == 0 || !cfg || !img || !uv || !pdf || !error_cdfs_arg(cdfs, &e)) return NGP_INVALID;
-	NERF_TRY({
-		std::vector<Camera> cams(n_images);
-		for (uint32_t i = 0; i < n_images; ++i) {
-			if (images[i].width == 0 || images[i].height == 0) return NGP_INVALID;
-			cams[i] = Camera{};
-			cams[i].width = images[i].width; cams[i].height = images[i].height;
-		}
-		training_pixels_host(cams.data(), n_images, *cfg, n_rays, ray_offset, n_rays_total ? n_rays_total : n_rays,
-		                     Rng{rng.state, rng.inc}, e, img, uv, pdf);
-	});
-}
-
-static int nerf_compute_loss(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
-                             uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples_compacted, const uint32_t* ray_counter,
-                             const void* network_output, uint32_t out_stride, const uint32_t* ray_indices, const float* rays,
-                             uint32_t* numsteps, const float* coords_in, float* coords_out, void* dloss_doutput, float* loss,
-                             uint32_t* compacted_counter, const float* mean_density, float loss_scale, bool zero_loss = false,
-                             float* error_map = nullptr, uint32_t em_w = 0, uint32_t em_h = 0, float* state = nullptr,
-                             uint64_t state_cap = 0, volatile uint32_t* pub_host = nullptr, uint32_t pub_seq = 0,
-                             const ErrorCdfs& cdfs = ErrorCdfs{}, const float* envmap = nullptr, uint32_t env_w = 0,
-                             uint32_t env_h = 0, uint32_t env_loss_type = 0, unsigned long long* env_acc = nullptr);
-
-int ngp_nerf_compute_loss(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
-                          uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples_compacted, const uint32_t* ray_counter,
-                          const void* network_output, const uint32_t* ray_indices, const float* rays, uint32_t* numsteps,
-                          const float* coords_in, float* coords_out, void* dloss_doutput, float* loss,
-                          uint32_t* compacted_counter, const float* mean_density, float loss_scale) {
-	return nerf_compute_loss(ds, cfg, stream, n_rays, n_rays_total, rng, max_samples_compacted, ray_counter, network_output, 16,
-	                         ray_indices, rays, numsteps, coords_in, coords_out, dloss_doutput, loss, compacted_counter, mean_density,
-	                         loss_scale);
-}
-
-int ngp_nerf_compute_loss_error_map(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
-                                    uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples_compacted,
-                                    const uint32_t* ray_counter, const void* network_output, const uint32_t* ray_indices,
-                                    const float* rays, uint32_t* numsteps, const float* coords_in, float* coords_out,
-                                    void* dloss_doutput, float* loss, uint32_t* compacted_counter, const float* mean_density,
-                                    float loss_scale, float* error_map, uint32_t em_width, uint32_t em_height) {
-	if (error_map && (em_width < 2 || em_height < 2)) return NGP_INVALID;  // the bilinear deposit needs a 2x2 texel block
-	return nerf_compute_loss(ds, cfg, stream, n_rays, n_rays_total, rng, max_samples_compacted, ray_counter, network_output, 16,
-	                         ray_indices, rays, numsteps, coords_in, coords_out, dloss_doutput, loss, compacted_counter, mean_density,
-	                         loss_scale, false, error_map, em_width, em_height);
-}
-
-int ngp_nerf_compute_loss_state(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
-                                uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples_compacted, const uint32_t* ray_counter,
-                                const void* network_output, const uint32_t* ray_indices, const float* rays, uint32_t* numsteps,
-                                const float* coords_in, float* coords_out, void* dloss_doutput, float* loss,
-                                uint32_t* compacted_counter, const float* mean_density, float loss_scale, float* sample_state,
-                                uint64_t state_capacity) {
-	if (!sample_state || state_capacity == 0) return NGP_INVALID;
-	return nerf_compute_loss(ds, cfg, stream, n_rays, n_rays_total, rng, max_samples_compacted, ray_counter, network_output, 16,
-	                         ray_indices, rays, numsteps, coords_in, coords_out, dloss_doutput, loss, compacted_counter, mean_density,
-	                         loss_scale, false, nullptr, 0, 0, sample_state, state_capacity);
-}
-
-int ngp_nerf_compute_loss_cdf(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
-                              uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples_compacted, const uint32_t* ray_counter,
-                              const void* network_output, const uint32_t* ray_indices, const float* rays, uint32_t* numsteps,
-                              const float* coords_in, float* coords_out, void* dloss_doutput, float* loss,
-                              uint32_t* compacted_counter, const float* mean_density, float loss_scale, float* error_map,
-                              uint32_t em_width, uint32_t em_height, const ngp_nerf_error_cdfs* cdfs) {
-	ErrorCdfs e;
-	if (!error_cdfs_arg(cdfs, &e)) return NGP_INVALID;
-	if (error_map && (em_width < 2 || em_height < 2)) return NGP_INVALID;
-	return nerf_compute_loss(ds, cfg, stream, n_rays, n_rays_total, rng, max_samples_compacted, ray_counter, network_output, 16,
-	                         ray_indices, rays, numsteps, coords_in, coords_out, dloss_doutput, loss, compacted_counter, mean_density,
-	                         loss_scale, false, error_map, em_width, em_height, nullptr, 0, nullptr, 0, e);
-}
-
-static bool envmap_dims_ok(uint32_t w, uint32_t h) { return w >= 1 && h >= 1 && w <= 8192 && h <= 8192; }
-
-int ngp_nerf_compute_loss_envmap(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
-                                 uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples_compacted, const uint32_t* ray_counter,
-                                 const void* network_output, const uint32_t* ray_indices, const float* rays, uint32_t* numsteps,
-                                 const float* coords_in, float* coords_out, void* dloss_doutput, float* loss,
-                                 uint32_t* compacted_counter, const float* mean_density, float loss_scale, const float* envmap,
-                                 uint32_t env_width, uint32_t env_height, uint32_t envmap_loss_type, float* envmap_gradient) {
-	if (!envmap || !rays || !envmap_dims_ok(env_width, env_height) || envmap_loss_type > LOSS_RELL2) return NGP_INVALID;
-	NERF_TRY({
-		static thread_local Buf acc;
-		unsigned long long* a = nullptr;
-		if (envmap_gradient) {
-			const size_t words = envmap_acc_words64(env_width, env_height);
-			a = acc.get<unsigned long long>(words);
-			NGP_HIP(hipMemsetAsync(a, 0, words * 8, S(stream)));
-		}
-		const int rc = nerf_compute_loss(ds, cfg, stream, n_rays, n_rays_total, rng, max_samples_compacted, ray_counter,
-		                                 network_output, 16, ray_indices, rays, numsteps, coords_in, coords_out, dloss_doutput, loss,
-		                                 compacted_counter, mean_density, loss_scale, false, nullptr, 0, 0, nullptr, 0, nullptr, 0,
-		                                 ErrorCdfs{}, envmap, env_width, env_height, envmap_loss_type, a);
-		if (rc != NGP_OK) return rc;  // the error string is set
-		if (envmap_gradient) envmap_gradient_f32(env_width, env_height, a, envmap_gradient, S(stream));
-	});
-}
-
-int ngp_envmap_lookup(void* stream, uint32_t width, uint32_t height, uint32_t n, const float* dirs, uint32_t* texels, float* weights) {
-	if (!envmap_dims_ok(width, height) || (n && (!dirs || !texels || !weights))) return NGP_INVALID;
-	NERF_TRY({ envmap_lookup_device(width, height, n, dirs, texels, weights, S(stream)); });
-}
-
-int ngp_envmap_lookup_host(uint32_t width, uint32_t height, uint32_t n, const float* dirs, uint32_t* texels, float* weights) {
-	if (!envmap_dims_ok(width, height) || (n && (!dirs || !texels || !weights))) return NGP_INVALID;
-	envmap_lookup_host(width, height, n, dirs, texels, weights);
-	return NGP_OK;
-}
-
-int ngp_envmap_deposit(void* stream, uint32_t width, uint32_t height, uint32_t n, const float* dirs, const void* values_f16,
-                       float* gradient) {
-	if (!envmap_dims_ok(width, height) || !gradient || (n && (!dirs || !values_f16))) return NGP_INVALID;
-	NERF_TRY({
-		static thread_local Buf acc;
-		const size_t words = envmap_acc_words64(width, height);
-		unsigned long long* a = acc.get<unsigned long long>(words);
-		NGP_HIP(hipMemsetAsync(a, 0, words * 8, S(stream)));
-		envmap_deposit_values(width, height, n, dirs, (const f16*)values_f16, a, S(stream));
-		envmap_gradient_f32(width, height, a, gradient, S(stream));
-	});
-}
-
-int ngp_envmap_optimizer_step(void* stream, const char* optimizer_json, uint32_t step, float loss_scale, uint32_t n, float* params,
-                              const float* gradient, float* first_moments, float* second_moments, uint32_t* param_steps, float* ema,
-                              float* ema_params) {
-	if (!optimizer_json || !params || !gradient || !first_moments || !second_moments || !param_steps || !(loss_scale > 0.f))
-		return NGP_INVALID;
-	NERF_TRY({
-		AdamConfig c;
-		parse_optimizer_json(optimizer_json, c);
-		AdamState st{};
-		st.w32 = params; st.g32 = gradient; st.m1 = first_moments; st.m2 = second_moments; st.steps = param_steps;
-		st.ema32 = ema; st.ema_f32 = ema_params; st.step_add = step;
-		adam_ema_update_f32(c, n, loss_scale, st, S(stream));
-	});
-}
-
-static int nerf_compute_loss(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
-                             uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples_compacted, const uint32_t* ray_counter,
-                             const void* network_output, uint32_t out_stride, const uint32_t* ray_indices, const float* rays,
-                             uint32_t* numsteps, const float* coords_in, float* coords_out, void* dloss_doutput, float* loss,
-                             uint32_t* compacted_counter, const float* mean_density, float loss_scale, bool zero_loss,
-                             float* error_map, uint32_t em_w, uint32_t em_h, float* state, uint64_t state_cap,
-                             volatile uint32_t* pub_host, uint32_t pub_seq, const ErrorCdfs& cdfs, const float* envmap,
-                             uint32_t env_w, uint32_t env_h, uint32_t env_loss_type, unsigned long long* env_acc) {
-	if (!ds || !cfg || !ray_counter || !network_output || !numsteps || !coords_in || !coords_out || !dloss_doutput ||
-	    !compacted_counter || !mean_density)
-		return NGP_INVALID;
-	NERF_TRY({
-		LossArgs a{};
-		a.n_rays = n_rays; a.n_rays_total_for_image_idx = n_rays_total ? n_rays_total : n_rays; a.rng = Rng{rng.state, rng.inc};
-		a.max_samples_compacted = max_samples_compacted; a.ray_counter = ray_counter; a.network_output = (const f16*)network_output;
-		a.out_stride = out_stride;
-		a.ray_indices = ray_indices; a.rays = rays; a.numsteps = numsteps; a.coords_in = coords_in; a.coords_out = coords_out;
-		a.dloss_doutput = (f16*)dloss_doutput; a.loss = loss; a.compacted_counter = compacted_counter;
-		a.mean_density = mean_density; a.loss_scale = loss_scale; a.zero_loss = zero_loss;
-		a.error_map = error_map; a.em_w = em_w; a.em_h = em_h;
-		a.state = state; a.state_cap = state ? state_cap : 0;
-		a.pub_host = pub_host; a.pub_seq = pub_seq;
-		a.cdfs = cdfs;
-		a.envmap = envmap; a.env_w = env_w; a.env_h = env_h; a.env_loss_type = env_loss_type; a.env_acc = envmap ? env_acc : nullptr;
-		NGP_CHECK(n_rays > 0 || !pub_host, "compute_loss: the counters are published by the scan, which needs rays");
-		if (n_rays == 0) { NGP_HIP(hipMemsetAsync(compacted_counter, 0, 4, S(stream))); return NGP_OK; }
-		static thread_local Buf tmp, tmpf;
-		compute_loss(ds->ds, *cfg, a, tmp.get<uint32_t>(2 * (size_t)n_rays), tmpf.get<float>(loss_tmp_f32(n_rays)), S(stream));
-	});
-}
-
-int ngp_nerf_fill_rollover(void* stream, uint32_t n_elements, uint32_t stride, const uint32_t* n_input, void* data, int dtype,
-                           int rescale) {
-	if (!n_input || !data) return NGP_INVALID;
-	NERF_TRY({
-		if (dtype == 1) fill_rollover_f16(n_elements, stride, n_input, (f16*)data, rescale != 0, S(stream));
-		else fill_rollover_f32(n_elements, stride, n_input, (float*)data, S(stream));
-	});
-}
-
-int ngp_nerf_grid_generate_samples(void* stream, const ngp_nerf_config* cfg, uint32_t n, ngp_rng rng, uint32_t step,
-                                   const float* grid, uint32_t n_cascades, float thresh, float* positions, uint32_t* indices) {
-	if (!cfg || !grid || !positions || !indices) return NGP_INVALID;
-	NERF_TRY({
-		static thread_local Buf mask;
-		grid_generate_samples(n, Rng{rng.state, rng.inc}, step, *cfg, grid, n_cascades, thresh, positions, indices,
-		                      mask.get<uint32_t>(grid_mask_words(n_cascades)), S(stream));
-	});
-}
-int ngp_nerf_grid_splat_max(void* stream, uint32_t n, const uint32_t* indices, const void* density_rm, uint32_t act, float* tmp) {
-	if (!indices || !density_rm || !tmp) return NGP_INVALID;
-	NERF_TRY(grid_splat_max(n, indices, (const f16*)density_rm, act, tmp, S(stream)));
-}
-int ngp_nerf_grid_splat_max_cells(void* stream, uint32_t n, const uint32_t* indices, const void* density_rm, uint32_t act,
-                                  float* tmp, uint32_t n_cells) {
-	if ((n && (!indices || !density_rm)) || !tmp || n_cells == 0 || n_cells % 8192 || n_cells > 8 * GRID_N_CELLS) return NGP_INVALID;
-	NERF_TRY({
-		static thread_local Buf scratch;
-		grid_splat_max_binned(n, indices, (const f16*)density_rm, act, tmp, n_cells,
-		                      scratch.get<uint32_t>(grid_splat_scratch_u32(n, n_cells)), S(stream));
-	});
-}
-int ngp_nerf_grid_ema(void* stream, uint32_t n, float decay, float* grid, const float* tmp) {
-	if (!grid || !tmp) return NGP_INVALID;
-	NERF_TRY(grid_ema(n, decay, grid, tmp, S(stream)));
-}
-int ngp_nerf_grid_mean_and_bitfield(void* stream, const float* grid, uint32_t max_cascade, float* mean, uint8_t* bitfield) {
-	if (!grid || !mean || !bitfield || max_cascade >= CASCADES) return NGP_INVALID;
-	NERF_TRY(grid_mean_bitfield(grid, max_cascade, mean, bitfield, S(stream)));
-}
-
 // ---- Testbed-level ---------------------------------------------------------------------------
 int ngp_nerf_trainer_create(ngp_model* model, ngp_trainer* trainer, const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg,
                             uint64_t seed, ngp_nerf_trainer** out) {
@@ -741,8 +120,6 @@ int ngp_nerf_trainer_set_config(ngp_nerf_trainer* t, const ngp_nerf_config* cfg)
 		if (t->early() != early_was) NGP_HIP(hipDeviceSynchronize());
 	});
 }
-
-static void check_rc(int rc) { if (rc != NGP_OK) throw Error(ngp_last_error()); }
 
 // ---- camera pose refinement: the trainer's cameras -----------------------------------------------------------------
 // Training::update_transforms (testbed_nerf.cu:2980-3024) for image i: its transform with the optimisers' offsets
@@ -946,95 +323,6 @@ int ngp_nerf_trainer_last_samples(const ngp_nerf_trainer* t, ngp_rng* rng, uint3
 int ngp_nerf_trainer_pose_optimizer_state(const ngp_nerf_trainer* t, uint32_t i, ngp_adam_state* pos, ngp_adam_state* rot) {
 	if (!t || i >= t->cams.size()) return NGP_INVALID;
 	return ngp_pose_optimizer_get(t->pose, i, pos, rot);
-}
-
-// ---- rendering ---------------------------------------------------------------------------------
-int ngp_nerf_renderer_create(ngp_nerf_renderer** out) {
-	if (!out) return NGP_INVALID;
-	NERF_TRY({ *out = new ngp_nerf_renderer(); });
-}
-void ngp_nerf_renderer_destroy(ngp_nerf_renderer* r) { delete r; }
-int ngp_nerf_renderer_set_mode(ngp_nerf_renderer* r, int render_mode) {
-	if (!r || render_mode < (int)RENDER_AO || (render_mode > (int)RENDER_DEPTH && render_mode != (int)RENDER_ENCODING_VIS))
-		return NGP_INVALID;
-	r->render_mode = (uint32_t)render_mode;
-	return NGP_OK;
-}
-int ngp_nerf_renderer_set_show_accel(ngp_nerf_renderer* r, int show_accel) {
-	if (!r || show_accel < -1 || show_accel >= (int)CASCADES) return NGP_INVALID;
-	r->show_accel = show_accel;
-	return NGP_OK;
-}
-int ngp_nerf_renderer_set_depth_scale(ngp_nerf_renderer* r, float depth_scale) {
-	if (!r) return NGP_INVALID;
-	r->depth_scale = depth_scale;
-	return NGP_OK;
-}
-int ngp_nerf_renderer_set_envmap(ngp_nerf_renderer* r, const float* envmap, uint32_t width, uint32_t height) {
-	if (!r || (envmap && !envmap_dims_ok(width, height))) return NGP_INVALID;
-	r->envmap = envmap;
-	r->env_w = envmap ? width : 0;
-	r->env_h = envmap ? height : 0;
-	return NGP_OK;
-}
-
-int ngp_nerf_render(ngp_nerf_renderer* r, ngp_model* model, const ngp_nerf_config* cfg, void* stream, const ngp_nerf_image* camera,
-                    const uint8_t* bitfield, uint32_t spp, uint32_t sample_index, float min_transmittance, const float* background_rgba,
-                    int use_inference_params, float* out_rgba) {
-	if (!r || !model || !cfg || !camera || !out_rgba || spp == 0) return NGP_INVALID;
-	NERF_TRY({
-		hipStream_t s = S(stream);
-		RenderArgs a{};
-		a.width = camera->width; a.height = camera->height;
-		a.focal[0] = camera->focal_length[0]; a.focal[1] = camera->focal_length[1];
-		// m_screen_center = 1 - principal point (set_camera_to_training_view, testbed.cu:852), then
-		// render_screen_center (testbed.cu:4376-4379, zoom 1): (0.5 - m_screen_center) + 0.5 = principal point
-		for (int k = 0; k < 2; ++k) a.screen_center[k] = (0.5f - (1.0f - camera->principal_point[k])) * 1.0f + 0.5f;
-		effective_camera_matrix(camera->xform, a.cam);
-		NGP_CHECK(camera->lens_mode <= LENS_OPENCV_FISHEYE, "render: unsupported lens mode");
-		a.lens_mode = camera->lens_mode;
-		for (int k = 0; k < 4; ++k) a.lens[k] = camera->lens_params[k];
-		a.near_distance = 0.0f;  // m_render_near_distance (testbed.h:914)
-		for (int k = 0; k < 3; ++k) { a.aabb_min[k] = cfg->aabb_min[k]; a.aabb_max[k] = cfg->aabb_max[k]; }
-		a.cone_angle_constant = cfg->cone_angle_constant;
-		a.max_mip = cfg->max_cascade;
-		a.bitfield = bitfield;
-		a.sample_index = sample_index;
-		a.snap_to_pixel_centers = cfg->snap_to_pixel_centers;
-		a.linear_colors = cfg->linear_colors;
-		a.rgb_activation = cfg->rgb_activation;
-		a.density_activation = cfg->density_activation;
-		a.min_transmittance = min_transmittance;
-		for (int k = 0; k < 4; ++k) a.background[k] = background_rgba ? background_rgba[k] : 0.f;
-		const uint32_t n_px = a.width * a.height;
-		const size_t max_q = (size_t)std::max(n_px, 2u * 1024 * 1024) + 256;
-		RenderWorkspace ws{};
-		const size_t pb = render_payload_bytes();
-		ws.payload[0] = r->pay0.get<char>(pb * n_px);
-		ws.payload[1] = r->pay1.get<char>(pb * n_px);
-		ws.payload_hit = r->payh.get<char>(pb * n_px);
-		ws.rgba[0] = r->rgba0.get<float>(4 * (size_t)n_px);
-		ws.rgba[1] = r->rgba1.get<float>(4 * (size_t)n_px);
-		ws.rgba_hit = r->rgbah.get<float>(4 * (size_t)n_px);
-		ws.coords = r->coords.get<float>(7 * max_q);
-		ws.out = r->out.get<f16>(16 * max_q);
-		ws.frame = r->frame.get<float>(4 * (size_t)n_px);
-		ws.counters = r->counters.get<uint32_t>(2);
-		if (!r->host_counters) NGP_HIP(hipHostMalloc(&r->host_counters, 16));
-		ws.host_counters = r->host_counters;
-		a.render_mode = r->render_mode;
-		a.depth_scale = r->depth_scale;
-		a.show_accel = r->show_accel;
-		a.envmap = r->envmap; a.env_w = r->env_w; a.env_h = r->env_h;
-		auto infer =[&](uint32_t n, const float* coords, f16* out) {
-			check_rc(ngp_inference(model, s, n, coords, 7, out, n, NGP_LAYOUT_SOA, use_inference_params));
-		};
-		// Normals: tcnn input_gradient's default backprop_scale (128); it reads the inference parameters
-		auto grad = [&](uint32_t n, float* coords) {
-			check_rc(ngp_input_gradient(model, s, 3, n, coords, 7, coords, 7, 128.0f));
-		};
-		render_frame(a, spp, ws, infer, out_rgba, s, grad);
-	});
 }
 
 int ngp_nerf_trainer_set_data_parallel(ngp_nerf_trainer* t, uint32_t rank, uint32_t world, ngp_allreduce_fn allreduce, void* user) {
@@ -1252,9 +540,11 @@ static SamplePlan sample_plan(ngp_nerf_trainer* t) {
 }
 static void launch_sampler(ngp_nerf_trainer* t, const SamplePlan& p, hipStream_t s) {
 	ProfScope ps("nerf_sample", s);
-	const ngp_rng rng{t->rng.state, t->rng.inc};
-	check_rc(generate_training_samples(t->data, &t->cfg, s, p.Rl, p.r_lo, p.R, rng, p.max_inference, (const uint8_t*)t->bitfield.p,
-	                                   p.ray_indices, p.rays, p.numsteps, p.coords, p.ctr, t->d_cams, t->sampling_cdfs()));
+	SampleArgs a{};
+	a.n_rays = p.Rl; a.ray_offset = p.r_lo; a.n_rays_total_for_image_idx = p.R; a.cdfs = t->sampling_cdfs();
+	a.max_samples = p.max_inference; a.rng = t->rng.dev(); a.bitfield = (const uint8_t*)t->bitfield.p;
+	a.ray_indices = p.ray_indices; a.rays = p.rays; a.numsteps = p.numsteps; a.coords = p.coords; a.counters = p.ctr;
+	check_rc(run_sampler(t->data, &t->cfg, s, a, t->d_cams));
 }
 static bool density_grid_update_due(uint32_t step) {
 	const uint32_t skip = std::min(std::max(step / 16u, 1u), 16u);
@@ -1492,11 +782,18 @@ static void step_loss_and_publish(ngp_nerf_trainer* t, hipStream_t s, const Step
 		ProfScope ps("nerf_loss", s);
 		// pass 1 keeps each composited sample's state for pass 2 (indexed like the sampler's samples, at most max_samples)
 		float* lstate = t->knobs.loss_state ? t->loss_state.get<float>((size_t)5 * sp.max_samples) : nullptr;
-		check_rc(nerf_compute_loss(t->data, &t->cfg, s, Rl, R, c.rng, Bl, ctr, c.mlp_out, 4, sp.ray_indices, sp.rays, sp.numsteps,
-		                           sp.coords, c.coords_c, c.dloss, c.loss, ctr + 2, (const float*)t->mean.p,
-		                           c.dp ? loss_scale_local : 128.0f, true, error_map, t->em_w, t->em_h, lstate, sp.max_samples,
-		                           c.early_pub ? t->host_ctr : nullptr, pub_seq, t->sampling_cdfs(),
-		                           env.bound() ? (const float*)env.params.p : nullptr, env.w, env.h, t->envmap_loss_type(), env_acc));
+		LossArgs a{};
+		a.n_rays = Rl; a.n_rays_total_for_image_idx = R; a.rng = Rng{c.rng.state, c.rng.inc};
+		a.max_samples_compacted = Bl; a.ray_counter = ctr; a.network_output = c.mlp_out; a.out_stride = 4;
+		a.ray_indices = sp.ray_indices; a.rays = sp.rays; a.numsteps = sp.numsteps; a.coords_in = sp.coords; a.coords_out = c.coords_c;
+		a.dloss_doutput = c.dloss; a.loss = c.loss; a.compacted_counter = ctr + 2;
+		a.mean_density = (const float*)t->mean.p; a.loss_scale = c.dp ? loss_scale_local : 128.0f; a.zero_loss = true;
+		a.error_map = error_map; a.em_w = t->em_w; a.em_h = t->em_h;
+		a.state = lstate; a.state_cap = sp.max_samples;
+		a.pub_host = c.early_pub ? t->host_ctr : nullptr; a.pub_seq = pub_seq; a.cdfs = t->sampling_cdfs();
+		a.envmap = env.bound() ? (const float*)env.params.p : nullptr; a.env_w = env.w; a.env_h = env.h;
+		a.env_loss_type = t->envmap_loss_type(); a.env_acc = env_acc;
+		check_rc(run_compute_loss(t->data, &t->cfg, s, a));
 	}
 	if (!c.dp) {
 		// single GPU: the rollover launch (fill_rollover_and_rescale + fill_rollover) also publishes the counters
@@ -1715,440 +1012,4 @@ int ngp_nerf_train_step(ngp_nerf_trainer* t, void* stream, int get_loss, ngp_ner
 		NGP_CHECK(t->measured_batch_size > 0, "Nerf training generated 0 samples (testbed_nerf.cu:3693-3697)");
 	});
 }
-
-
-// ---- snapshots (.ingp) ---------------------------------------------------------------------------
-// Testbed::save_snapshot / load_snapshot (src/testbed.cu:4873-5057) for a NeRF testbed: msgpack of the
-// network config with a "snapshot" member; .ingp files are gzip streams (zstr), others raw msgpack.
-// tcnn Trainer::serialize writes n_params / params_type / params_binary (fp16 params); the optimizer
-// member (include_optimizer_state) is this engine's own layout (tcnn absent: parity unpinned).
-}  // extern "C"
-
-namespace {
-using ngp::mp::Value;
-
-constexpr uint32_t SNAPSHOT_FORMAT_VERSION = 1;  // testbed.cu:80
-
-bool ends_with_ci(const std::string& s, const std::string& suf) {
-	return s.size() >= suf.size() && ngp::iequals(s.substr(s.size() - suf.size()), suf);
-}
-
-std::string gzip_bytes(const std::string& in, int level) {
-	z_stream z{};
-	NGP_CHECK(deflateInit2(&z, level, Z_DEFLATED, 15 + 16, 8, Z_DEFAULT_STRATEGY) == Z_OK, "snapshot: deflateInit2 failed");
-	std::string out(deflateBound(&z, in.size()) + 64, '\0');
-	z.next_in = (Bytef*)in.data();
-	z.avail_in = (uInt)in.size();
-	z.next_out = (Bytef*)out.data();
-	z.avail_out = (uInt)out.size();
-	const int rc = deflate(&z, Z_FINISH);
-	const size_t n = out.size() - z.avail_out;
-	deflateEnd(&z);
-	NGP_CHECK(rc == Z_STREAM_END, "snapshot: deflate failed");
-	out.resize(n);
-	return out;
-}
-
-std::string maybe_inflate(const std::string& in) {
-	const bool gz = in.size() >= 2 && (uint8_t)in[0] == 0x1f && (uint8_t)in[1] == 0x8b;
-	const bool zl = in.size() >= 2 && ((uint8_t)in[0] & 0x0f) == 8 && (((uint8_t)in[0] << 8) | (uint8_t)in[1]) % 31 == 0;
-	if (!gz && !zl) return in;  // raw msgpack
-	z_stream z{};
-	NGP_CHECK(inflateInit2(&z, 15 + 32) == Z_OK, "snapshot: inflateInit2 failed");
-	z.next_in = (Bytef*)in.data();
-	z.avail_in = (uInt)in.size();
-	std::string out;
-	char buf[1 << 16];
-	int rc;
-	do {
-		z.next_out = (Bytef*)buf;
-		z.avail_out = sizeof buf;
-		rc = inflate(&z, Z_NO_FLUSH);
-		NGP_CHECK(rc == Z_OK || rc == Z_STREAM_END, "snapshot: corrupt compressed stream");
-		out.append(buf, sizeof buf - z.avail_out);
-	} while (rc != Z_STREAM_END);
-	inflateEnd(&z);
-	return out;
-}
-
-std::string read_file(const char* path) {
-	std::ifstream f(path, std::ios::binary);
-	NGP_CHECK(f.good(), std::string("snapshot: cannot open '") + path + "'");
-	std::stringstream ss;
-	ss << f.rdbuf();
-	return ss.str();
-}
-
-Value load_network_config(const char* path) {  // Testbed::load_network_config (testbed.cu:246): msgpack branch
-	return ngp::mp::decode(maybe_inflate(read_file(path)));
-}
-
-Value vec3(const float* v) {
-	Value a = Value::array();
-	for (int k = 0; k < 3; ++k) a.arr.push_back(Value::real(v[k]));
-	return a;
-}
-
-// one per-camera optimiser with the reference's member names (adam_optimizer.h:174-194)
-Value adam_to_value(const ngp_adam_state& a) {
-	Value v = Value::object();
-	v["iter"] = Value::uint(a.iter);
-	v["first_moment"] = vec3(a.first_moment);
-	v["second_moment"] = vec3(a.second_moment);
-	v["variable"] = vec3(a.variable);
-	v["learning_rate"] = Value::real(a.learning_rate);
-	v["epsilon"] = Value::real(a.epsilon);
-	v["beta1"] = Value::real(a.beta1);
-	v["beta2"] = Value::real(a.beta2);
-	return v;
-}
-ngp_adam_state adam_from_value(const Value& v) {
-	ngp_adam_state a;
-	a.iter = (uint32_t)v.at("iter").number();
-	const char* names[3] = {"first_moment", "second_moment", "variable"};
-	float* dst[3] = {a.first_moment, a.second_moment, a.variable};
-	for (int m = 0; m < 3; ++m) {
-		const Value& x = v.at(names[m]);
-		NGP_CHECK(x.type == Value::Array && x.arr.size() == 3, "snapshot: a camera optimiser's vectors hold three numbers");
-		for (int k = 0; k < 3; ++k) dst[m][k] = (float)x.arr[k].number();
-	}
-	a.learning_rate = (float)v.at("learning_rate").number();
-	a.epsilon = (float)v.at("epsilon").number();
-	a.beta1 = (float)v.at("beta1").number();
-	a.beta2 = (float)v.at("beta2").number();
-	return a;
-}
-
-template <typename T> std::vector<T> device_to_host(const void* d, size_t n) {
-	std::vector<T> h(n);
-	if (n) NGP_HIP(hipMemcpy(h.data(), d, n * sizeof(T), hipMemcpyDeviceToHost));
-	return h;
-}
-
-void check_ok(int rc) {
-	if (rc != NGP_OK) throw ngp::Error(ngp_last_error());
-}
-
-const char* const OPT_NAMES[5] = {"full_precision_params_binary", "first_moments_binary", "second_moments_binary",
-                                  "ema_params_binary", "param_steps_binary"};
-
-// tcnn Trainer::serialize(include_optimizer_state) (testbed.cu:4874): n_params, params_type, params_binary (the fp16
-// parameters) and, with the optimizer state, an "optimizer" member: the Adam moments and per-parameter steps, the
-// EMA weights and the fp32 master weights under tcnn-style names (tcnn absent: the member names are a restatement,
-// parity unpinned)
-void trainer_to_snapshot(ngp_trainer* tr, uint64_t n, bool include_optimizer_state, Value& snap) {
-	snap["n_params"] = Value::uint(n);
-	snap["params_type"] = Value::str("__half");
-	{
-		auto p = device_to_host<uint16_t>(ngp_trainer_params(tr), n);
-		snap["params_binary"] = Value::bin(p.data(), p.size() * 2);
-	}
-	if (!include_optimizer_state) return;
-	uint64_t bytes = 0;
-	check_ok(ngp_trainer_serialize(tr, nullptr, &bytes));
-	std::string blob(bytes, '\0');
-	check_ok(ngp_trainer_serialize(tr, blob.data(), &bytes));
-	uint64_t hdr[4];
-	memcpy(hdr, blob.data(), 32);
-	Value opt = Value::object();
-	opt["otype"] = Value::str("Ema(ExponentialDecay(Adam))");
-	opt["current_step"] = Value::uint(hdr[3]);
-	for (int k = 0; k < 5; ++k) opt[OPT_NAMES[k]] = Value::bin(blob.data() + 32 + (size_t)k * n * 4, (size_t)n * 4);
-	snap["optimizer"] = opt;
-}
-
-// tcnn Trainer::deserialize (testbed.cu:5040): the parameters, then the optimizer state when the snapshot has one.
-// An optimizer member without some of this engine's arrays (one written by another implementation of the chain)
-// fills them from what is there: fp32 master weights and EMA from the parameters, moments and steps from 0.
-void trainer_from_snapshot(ngp_trainer* tr, uint64_t n, const Value& snap) {
-	NGP_CHECK((uint64_t)snap.at("n_params").number() == n, "snapshot: parameter count differs from this network");
-	const Value& pb = snap.at("params_binary");
-	const std::string type = snap.find("params_type") ? snap.at("params_type").s : std::string("__half");
-	std::vector<float> w(n);
-	if (type == "float") {
-		NGP_CHECK(pb.s.size() == n * 4, "snapshot: params_binary size");
-		memcpy(w.data(), pb.s.data(), n * 4);
-	} else {
-		NGP_CHECK(type == "__half" && pb.s.size() == n * 2, "snapshot: params_binary size/type");
-		const ngp::f16* h = (const ngp::f16*)pb.s.data();
-		for (uint64_t k = 0; k < n; ++k) w[k] = (float)h[k];
-	}
-	check_ok(ngp_trainer_set_params_full_precision(tr, w.data(), n));
-	const Value* opt = snap.find("optimizer");
-	if (!opt) return;
-	std::string blob(32 + (size_t)n * 20, '\0');
-	const uint64_t hdr[4] = {0x4e47504d49333535ULL, 1, n, (uint64_t)opt->number_or("current_step", 0.0)};
-	memcpy(blob.data(), hdr, 32);
-	for (int k = 0; k < 5; ++k) {
-		char* dst = blob.data() + 32 + (size_t)k * n * 4;
-		if (const Value* b = opt->find(OPT_NAMES[k])) {
-			NGP_CHECK(b->s.size() == n * 4, std::string("snapshot: optimizer ") + OPT_NAMES[k] + " size");
-			memcpy(dst, b->s.data(), n * 4);
-		} else if (k == 0 || k == 3) {
-			memcpy(dst, w.data(), n * 4);  // master weights / EMA: the parameters
-		}  // moments, steps: 0
-	}
-	check_ok(ngp_trainer_deserialize(tr, blob.data(), blob.size()));
-}
-
-void write_snapshot(const char* path, Value& root, Value& snap, int compress) {
-	root["snapshot"] = snap;
-	std::string bytes;
-	ngp::mp::encode(root, bytes);
-	if (ends_with_ci(path, ".ingp")) bytes = gzip_bytes(bytes, compress ? Z_DEFAULT_COMPRESSION : Z_NO_COMPRESSION);
-	std::ofstream f(path, std::ios::binary);
-	NGP_CHECK(f.good(), std::string("snapshot: cannot write '") + path + "'");
-	f.write(bytes.data(), (std::streamsize)bytes.size());
-	NGP_CHECK(f.good(), "snapshot: write failed");
-}
-
-Value snapshot_root(const char* network_config_json) {
-	Value root = network_config_json && *network_config_json ? ngp::mp::from_json(ngp::Json::parse(network_config_json))
-	                                                          : Value::object();
-	root.erase("snapshot");
-	return root;
-}
-}  // namespace
-
-extern "C" {
-
-int ngp_nerf_save_snapshot(ngp_nerf_trainer* t, void* stream, const char* path, const char* network_config_json,
-                           int include_optimizer_state, int compress) {
-	if (!t || !path) return NGP_INVALID;
-	NERF_TRY({
-		NGP_HIP(hipStreamSynchronize(S(stream)));
-		Value root = snapshot_root(network_config_json);
-		Value snap = Value::object();
-		trainer_to_snapshot(t->trainer, ngp_model_n_params(t->model), include_optimizer_state != 0, snap);
-		snap["version"] = Value::uint(SNAPSHOT_FORMAT_VERSION);
-		snap["mode"] = Value::str("nerf");
-		snap["density_grid_size"] = Value::uint(GRIDSIZE);
-		{
-			const uint32_t n_el = GRID_N_CELLS * (t->cfg.max_cascade + 1);
-			auto g = device_to_host<float>(t->grid.p, n_el);
-			std::vector<f16> h(n_el);
-			for (uint32_t k = 0; k < n_el; ++k) h[k] = (f16)g[k];  // (__half)density_grid[i]
-			snap["density_grid_binary"] = Value::bin(h.data(), h.size() * 2);
-		}
-		Value& nerf = snap["nerf"];
-		nerf["aabb_scale"] = Value::real(t->cfg.aabb_max[0] - t->cfg.aabb_min[0]);
-		nerf["rgb"]["rays_per_batch"] = Value::uint(t->rays_per_batch);
-		nerf["rgb"]["measured_batch_size"] = Value::uint(t->measured_batch_size);
-		nerf["rgb"]["measured_batch_size_before_compaction"] = Value::uint(t->measured_before_compaction);
-		// the per-camera optimisers, as VarAdamOptimizer::to_json writes them (testbed.cu:4891-4892)
-		{
-			Value pos = Value::array(), rot = Value::array();
-			for (uint32_t i = 0; i < t->cams.size(); ++i) {
-				ngp_adam_state p, r;
-				check_ok(ngp_pose_optimizer_get(t->pose, i, &p, &r));
-				pos.arr.push_back(adam_to_value(p));
-				rot.arr.push_back(adam_to_value(r));
-			}
-			nerf["cam_pos_offset"] = pos;
-			nerf["cam_rot_offset"] = rot;
-		}
-		snap["training_step"] = Value::uint(t->training_step);
-		snap["loss"] = Value::real(t->loss_scalar);
-		snap["aabb"]["min"] = vec3(t->cfg.aabb_min);
-		snap["aabb"]["max"] = vec3(t->cfg.aabb_max);
-		snap["density_grid_ema_step"] = Value::uint(t->ema_step);
-		// engine extension (the reference does not save m_envmap): the environment map and its optimizer
-		if (t->env.bound()) {
-			NGP_HIP(hipDeviceSynchronize());
-			const ngp_nerf_trainer::Envmap& e = t->env;
-			const size_t n = e.n();
-			auto put = [&](Value& to, const char* name, const void* d) {
-				auto h = device_to_host<float>(d, n);
-				to[name] = Value::bin(h.data(), n * 4);
-			};
-			Value em = Value::object();
-			em["width"] = Value::uint(e.w);
-			em["height"] = Value::uint(e.h);
-			put(em, "params_binary", e.params.p);
-			put(em, "ema_params_binary", t->envmap_inference());
-			if (include_optimizer_state) {
-				Value opt = Value::object();
-				opt["current_step"] = Value::uint(e.step);
-				opt["ema_valid"] = Value::uint(e.ema_valid ? 1 : 0);
-				put(opt, "ema_binary", e.ema.p);
-				put(opt, "first_moments_binary", e.m1.p);
-				put(opt, "second_moments_binary", e.m2.p);
-				put(opt, "param_steps_binary", e.steps.p);
-				em["optimizer"] = opt;
-			}
-			snap["envmap"] = em;
-		}
-		write_snapshot(path, root, snap, compress);
-	});
-}
-
-int ngp_nerf_load_snapshot(ngp_nerf_trainer* t, void* stream, const char* path) {
-	if (!t || !path) return NGP_INVALID;
-	NERF_TRY({
-		t->drain();
-		hipStream_t s = S(stream);
-		NGP_HIP(hipStreamSynchronize(s));
-		const Value root = load_network_config(path);
-		NGP_CHECK(root.find("snapshot"), std::string("File '") + path + "' does not contain a snapshot.");
-		const Value& snap = root.at("snapshot");
-		NGP_CHECK(snap.number_or("version", 0) >= SNAPSHOT_FORMAT_VERSION, "Snapshot uses an old format and can not be loaded.");
-		if (const Value* m = snap.find("mode")) NGP_CHECK(m->type == Value::Str && m->s == "nerf", "snapshot: not a NeRF snapshot");
-		NGP_CHECK((uint32_t)snap.at("density_grid_size").number() == GRIDSIZE, "Incompatible grid size.");
-		trainer_from_snapshot(t->trainer, ngp_model_n_params(t->model), snap);  // tcnn Trainer::deserialize
-		// density grid (fp16 in the file)
-		const Value& gb = snap.at("density_grid_binary");
-		const uint32_t n_el = GRID_N_CELLS * (t->cfg.max_cascade + 1);
-		const size_t n_file = gb.s.size() / 2;
-		if (n_file == n_el) {
-			std::vector<float> g(n_el);
-			const f16* h = (const f16*)gb.s.data();
-			for (uint32_t k = 0; k < n_el; ++k) g[k] = (float)h[k];
-			NGP_HIP(hipMemcpy(t->grid.p, g.data(), (size_t)n_el * 4, hipMemcpyHostToDevice));
-			grid_mean_bitfield((const float*)t->grid.p, t->cfg.max_cascade, (float*)t->mean.p, (uint8_t*)t->bitfield.p, s);
-		} else {
-			// a size of 0 is a never-populated grid (testbed.cu:5000-5005)
-			NGP_CHECK(n_file == 0, "Incompatible number of grid cascades.");
-		}
-		const Value& rgb = snap.at("nerf").at("rgb");
-		t->rays_per_batch = (uint32_t)rgb.at("rays_per_batch").number();
-		t->measured_batch_size = (uint32_t)rgb.at("measured_batch_size").number();
-		t->measured_before_compaction = (uint32_t)rgb.at("measured_batch_size_before_compaction").number();
-		t->measured_before_compaction_local = t->measured_before_compaction / t->world;
-		t->training_step = (uint32_t)snap.at("training_step").number();
-		t->loss_scalar = (float)snap.number_or("loss", 0.0);
-		t->ema_step = (uint32_t)snap.number_or("density_grid_ema_step", (double)t->training_step);
-		// the refined poses (testbed.cu:5048-5051): the optimisers where the snapshot has them for this many images,
-		// zero offsets otherwise; then the cameras from them
-		{
-			const Value& nerf = snap.at("nerf");
-			const Value* pos = nerf.find("cam_pos_offset");
-			const Value* rot = nerf.find("cam_rot_offset");
-			const size_t n = t->cams.size();
-			check_ok(ngp_pose_optimizer_reset(t->pose));
-			if (pos && pos->type == Value::Array && pos->arr.size() == n)
-				for (uint32_t i = 0; i < n; ++i) {
-					const ngp_adam_state st = adam_from_value(pos->arr[i]);
-					check_ok(ngp_pose_optimizer_set_state(t->pose, i, &st, nullptr));
-				}
-			if (rot && rot->type == Value::Array && rot->arr.size() == n)
-				for (uint32_t i = 0; i < n; ++i) {
-					const ngp_adam_state st = adam_from_value(rot->arr[i]);
-					check_ok(ngp_pose_optimizer_set_state(t->pose, i, nullptr, &st));
-				}
-			t->n_steps_since_cam_update = 0;
-			NGP_HIP(hipDeviceSynchronize());
-			t->rebuild_cameras(s);
-		}
-		// the environment map, where the snapshot has one (a snapshot without it leaves this trainer's as it is)
-		if (const Value* em = snap.find("envmap")) {
-			const uint32_t w = (uint32_t)em->at("width").number(), h = (uint32_t)em->at("height").number();
-			NGP_CHECK(envmap_dims_ok(w, h), "snapshot: envmap resolution");
-			const size_t n = (size_t)w * h * 4;
-			auto bin = [&](const Value& v, const char* name) -> const float* {
-				const Value* b = v.find(name);
-				if (!b) return nullptr;
-				NGP_CHECK(b->s.size() == n * 4, std::string("snapshot: envmap ") + name + " size");
-				return (const float*)b->s.data();
-			};
-			const float* params = bin(*em, "params_binary");
-			NGP_CHECK(params, "snapshot: envmap without params_binary");
-			check_ok(ngp_nerf_trainer_set_envmap(t, w, h, params));
-			ngp_nerf_trainer::Envmap& e = t->env;
-			auto up = [&](Buf& dst, const float* src) {
-				if (src) NGP_HIP(hipMemcpy(dst.p, src, n * 4, hipMemcpyHostToDevice));
-			};
-			if (const float* ema = bin(*em, "ema_params_binary")) {
-				up(e.ema_out, ema);
-				e.ema_valid = true;
-			}
-			if (const Value* opt = em->find("optimizer")) {
-				e.step = (uint32_t)opt->number_or("current_step", 0.0);
-				e.ema_valid = opt->number_or("ema_valid", 1.0) != 0.0;
-				up(e.ema, bin(*opt, "ema_binary"));
-				up(e.m1, bin(*opt, "first_moments_binary"));
-				up(e.m2, bin(*opt, "second_moments_binary"));
-				up(e.steps, bin(*opt, "param_steps_binary"));
-			}
-		}
-		NGP_HIP(hipStreamSynchronize(s));
-	});
-}
-
-// Testbed::save_snapshot / load_snapshot for the image and SDF testbeds (testbed.cu:4873-4937, 4939-5057): the
-// mode-independent members (Trainer::serialize, version, mode, training_step, loss, aabb, bounding_radius).
-int ngp_save_snapshot(ngp_trainer* t, void* stream, const char* path, const char* network_config_json, const char* mode,
-                      const float* aabb_min, const float* aabb_max, float bounding_radius, uint32_t training_step, float loss,
-                      int include_optimizer_state, int compress) {
-	if (!t || !path || !mode) return NGP_INVALID;
-	NERF_TRY({
-		NGP_HIP(hipStreamSynchronize(S(stream)));
-		Value root = snapshot_root(network_config_json);
-		Value snap = Value::object();
-		trainer_to_snapshot(t, ngp_trainer_n_params(t), include_optimizer_state != 0, snap);
-		snap["version"] = Value::uint(SNAPSHOT_FORMAT_VERSION);
-		snap["mode"] = Value::str(mode);
-		snap["training_step"] = Value::uint(training_step);
-		snap["loss"] = Value::real(loss);
-		const float zero[3] = {0.f, 0.f, 0.f}, one[3] = {1.f, 1.f, 1.f};
-		snap["aabb"]["min"] = vec3(aabb_min ? aabb_min : zero);
-		snap["aabb"]["max"] = vec3(aabb_max ? aabb_max : one);
-		snap["bounding_radius"] = Value::real(bounding_radius);
-		write_snapshot(path, root, snap, compress);
-	});
-}
-
-int ngp_load_snapshot(ngp_trainer* t, void* stream, const char* path, uint32_t* training_step, float* loss, float* aabb_min,
-                      float* aabb_max, float* bounding_radius) {
-	if (!t || !path) return NGP_INVALID;
-	NERF_TRY({
-		NGP_HIP(hipStreamSynchronize(S(stream)));
-		const Value root = load_network_config(path);
-		NGP_CHECK(root.find("snapshot"), std::string("File '") + path + "' does not contain a snapshot.");
-		const Value& snap = root.at("snapshot");
-		NGP_CHECK(snap.number_or("version", 0) >= SNAPSHOT_FORMAT_VERSION, "Snapshot uses an old format and can not be loaded.");
-		trainer_from_snapshot(t, ngp_trainer_n_params(t), snap);
-		if (training_step) *training_step = (uint32_t)snap.number_or("training_step", 0.0);
-		if (loss) *loss = (float)snap.number_or("loss", 0.0);
-		if (bounding_radius) *bounding_radius = (float)snap.number_or("bounding_radius", (double)*bounding_radius);
-		if (const Value* a = snap.find("aabb")) {
-			for (int d = 0; d < 3; ++d) {
-				if (aabb_min) aabb_min[d] = (float)a->at("min").arr.at(d).number();
-				if (aabb_max) aabb_max[d] = (float)a->at("max").arr.at(d).number();
-			}
-		}
-	});
-}
-
-// The snapshot's mode ("nerf", "sdf", "image", ...; testbed.cu:4950-4957: a snapshot without one but with a "nerf"
-// member is a NeRF snapshot), so that a Testbed can switch mode before reset_network
-int ngp_snapshot_mode(const char* path, char* mode_buf, uint64_t cap) {
-	if (!path || !mode_buf || cap == 0) return NGP_INVALID;
-	NERF_TRY({
-		const Value root = load_network_config(path);
-		NGP_CHECK(root.find("snapshot"), std::string("File '") + path + "' does not contain a snapshot.");
-		const Value& snap = root.at("snapshot");
-		std::string m;
-		if (const Value* v = snap.find("mode")) m = v->s;
-		else if (snap.find("nerf")) m = "nerf";
-		NGP_CHECK(!m.empty(), "Unknown snapshot mode. Snapshot must be regenerated with a new version of instant-ngp.");
-		NGP_CHECK(m.size() + 1 <= cap, "snapshot mode: buffer too small");
-		memcpy(mode_buf, m.c_str(), m.size() + 1);
-	});
-}
-
-int ngp_snapshot_network_config(const char* path, char* json_buf, uint64_t* size) {
-	if (!path || !size) return NGP_INVALID;
-	NERF_TRY({
-		Value root = load_network_config(path);
-		NGP_CHECK(root.is_map(), "snapshot: top level is not a map");
-		root.erase("snapshot");
-		std::string text;
-		ngp::mp::to_json_text(root, text);
-		if (!json_buf) { *size = text.size() + 1; return NGP_OK; }
-		NGP_CHECK(*size >= text.size() + 1, "snapshot: buffer too small");
-		memcpy(json_buf, text.c_str(), text.size() + 1);
-		*size = text.size() + 1;
-	});
-}
-
 }  // extern "C"
