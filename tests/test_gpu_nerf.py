@@ -203,7 +203,14 @@ def test_sampler_and_loss_cone_at_scale(pkg, orc, scene, aabb_scale, cone, n_ray
     np.testing.assert_array_equal(gl["coords_compacted"].cpu().numpy()[:n_used], rl["coords_compacted"][:n_used])
 
 
-@pytest.mark.parametrize("loss_type,act,aabb_scale", [(4, 3, 1.0), (0, 2, 1.0), (1, 3, 1.0), (4, 3, 8.0), (0, 2, 4.0)])
+def activation_pair(act):
+    """(rgb_activation, density_activation) of a case's `act`: a number is the rgb activation over Exponential density."""
+    return act if isinstance(act, tuple) else (act, 3)
+
+
+@pytest.mark.parametrize("loss_type,act,aabb_scale", [(4, 3, 1.0), (0, 2, 1.0), (1, 3, 1.0), (4, 3, 8.0), (0, 2, 4.0),
+                                                      (2, 3, 1.0), (3, 3, 1.0), (5, 3, 1.0), (6, 3, 1.0),  # MAPE, SMAPE, LogL1, RelativeL2
+                                                      pytest.param(0, (1, 2), 1.0, id="0-relu_logistic-1.0")])
 def test_compute_loss(pkg, orc, scene, loss_type, act, aabb_scale):
     """compute_loss_kernel_train_nerf (testbed_nerf.cu:1660-2012). Compositing weights use the shared
     ngp_expf (the reference's __expf site :1744), so where each ray terminates, the compacted count,
@@ -211,7 +218,8 @@ def test_compute_loss(pkg, orc, scene, loss_type, act, aabb_scale):
     Losses and dL/doutput are floating point: the sRGB targets go through powf (ocml vs glibc), so
     losses agree to rtol 1e-4 and each fp16 gradient to 2 fp16 ulp (+1e-7 absolute)."""
     ds, ims, pix = scene
-    cfg = pkg.nerf.default_config(aabb_scale, loss_type=loss_type, rgb_activation=act, density_activation=3)
+    rgb_act, density_act = activation_pair(act)
+    cfg = pkg.nerf.default_config(aabb_scale, loss_type=loss_type, rgb_activation=rgb_act, density_activation=density_act)
     _, bf = occupancy(orc, seed=2, frac=0.5, max_cascade=cfg.max_cascade)
     n_rays, max_samples = 2000, 1 << 17
     r = rng(pkg, 7)
@@ -247,7 +255,8 @@ def test_compute_loss(pkg, orc, scene, loss_type, act, aabb_scale):
     assert not bad.any(), (int(bad.sum()), dl_got[bad][:5], dl_ref[bad][:5])
 
 
-@pytest.mark.parametrize("loss_type,act,aabb_scale", [(4, 3, 1.0), (0, 2, 4.0)])
+@pytest.mark.parametrize("loss_type,act,aabb_scale", [(4, 3, 1.0), (0, 2, 4.0),
+                                                      pytest.param(3, (1, 2), 1.0, id="3-relu_logistic-1.0")])
 def test_compute_loss_kept_state_is_bitwise_equal(pkg, scene, orc, loss_type, act, aabb_scale):
     """The training step's form of the loss (pass 1 keeps each composited sample's weight, transmittance and
     rgb prefix; pass 2 reads them instead of compositing each ray again) gives the same bits as the two
@@ -255,7 +264,8 @@ def test_compute_loss_kept_state_is_bitwise_equal(pkg, scene, orc, loss_type, ac
     capacity shorter than the samples (a C-ABI caller's smaller buffer): pass 2 composites the rays past it
     again instead of reading unwritten state, with the same bits."""
     ds, ims, pix = scene
-    cfg = pkg.nerf.default_config(aabb_scale, loss_type=loss_type, rgb_activation=act, density_activation=3)
+    rgb_act, density_act = activation_pair(act)
+    cfg = pkg.nerf.default_config(aabb_scale, loss_type=loss_type, rgb_activation=rgb_act, density_activation=density_act)
     _, bf = occupancy(orc, seed=3, frac=0.5, max_cascade=cfg.max_cascade)
     n_rays, max_samples, max_c = 2000, 1 << 17, 1 << 15
     r = rng(pkg, 11)
