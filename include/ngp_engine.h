@@ -851,6 +851,44 @@ int ngp_nerf_trainer_set_envmap_training(ngp_nerf_trainer* t, int loss_type, con
  * owned by the caller and read by every later ngp_nerf_render; NULL unbinds. */
 int ngp_nerf_renderer_set_envmap(ngp_nerf_renderer* r, const float* envmap, uint32_t width, uint32_t height);
 
+/* ---- depth supervision (Training::depth_supervision_lambda, depth_loss_type; NerfDataset depth images) ---------- */
+/* NerfDataset::set_training_image's depth part (nerf_loader.cu:943-960, copy_depth :81-90): image `image` gets an fp32
+ * depth image [height][width] on the device, depth[i] = (float)pixel[i] * depth_scale (one fp32 multiply) from HOST
+ * pixels of dtype 0 (uint16) or 1 (float32). depth_host NULL or depth_scale <= 0 stores zeros (a depth of 0 means "no
+ * depth at this pixel"); depth_host NULL with depth_scale < 0 removes the image's depth. Images without depth keep a
+ * null pointer and cost nothing. A NULL dataset, an image index out of range, another dtype or a NaN scale return
+ * NGP_INVALID before any HIP call. Waits for the device: no loss pass may be reading the image. */
+int ngp_nerf_dataset_set_depth(ngp_nerf_dataset* ds, uint32_t image, const void* depth_host, int dtype, float depth_scale);
+/* Copies the image's depth to HOST memory (out_host nullable: only has_depth; capacity in floats, at least width *
+ * height when the image has depth). has_depth (nullable): 1 when the image has a depth image, else 0 and out_host is
+ * left alone. */
+int ngp_nerf_dataset_depth(const ngp_nerf_dataset* ds, uint32_t image, float* out_host, uint64_t capacity, int* has_depth);
+/* ngp_nerf_compute_loss with every optional input at once and the depth term (testbed_nerf.cu:1725-1748, 1848-1856,
+ * 1912-1956): error_map / cdfs as in _cdf, envmap / envmap_gradient as in _envmap (envmap NULL: none), sample_state /
+ * state_capacity as in _state (NULL: none) but with SIX planes, [6][state_capacity] floats: the sixth keeps the depth
+ * prefix. depth_supervision_lambda > 0 on a dataset in which an image has depth: each ray also composites its samples'
+ * distances from the ray origin (depth_ray), target_depth = |ray.d| * depth of the target texel (-|ray.d| for an image
+ * without depth), and where target_depth > 0 the density gradient of every compacted sample takes lambda *
+ * dL(target_depth, depth_ray)/d(depth_ray) * (T depth - depth suffix), the loss being depth_loss_type (ELossType). The
+ * term enters neither loss[] nor the error map. With lambda 0, or no image with depth, this is the entry point without
+ * it, bit for bit, and launches the same kernels. A negative or non-finite lambda or an unknown loss: NGP_INVALID. */
+int ngp_nerf_compute_loss_depth(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
+                                uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples_compacted,
+                                const uint32_t* ray_counter, const void* network_output, const uint32_t* ray_indices,
+                                const float* rays, uint32_t* numsteps, const float* coords_in, float* coords_out,
+                                void* dloss_doutput, float* loss, uint32_t* compacted_counter, const float* mean_density,
+                                float loss_scale, float* error_map, uint32_t em_width, uint32_t em_height,
+                                const ngp_nerf_error_cdfs* cdfs, const float* envmap, uint32_t env_width,
+                                uint32_t env_height, uint32_t envmap_loss_type, float* envmap_gradient, float* sample_state,
+                                uint64_t state_capacity, float depth_supervision_lambda, uint32_t depth_loss_type);
+/* Training::depth_supervision_lambda (default 0: off) and depth_loss_type (ELossType, default L1) of the trainer's
+ * steps (testbed.h:719, 745). Only the loss pass reads them: nothing is discarded, and with lambda 0 or a dataset
+ * without depth the step issues exactly the launches it would have. Works with the error-map CDFs, an environment
+ * map, optimize_extrinsics and data-parallel training (the term is per ray). Exposure, sharpness and replacing an
+ * image's colours after creation stay unimplemented. */
+int ngp_nerf_trainer_set_depth_supervision(ngp_nerf_trainer* t, float lambda, uint32_t loss_type);
+int ngp_nerf_trainer_get_depth_supervision(const ngp_nerf_trainer* t, float* lambda, uint32_t* loss_type);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

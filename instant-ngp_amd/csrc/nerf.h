@@ -51,6 +51,12 @@ struct Dataset {
 	uint32_t* d_pixels = nullptr;  // RGBA8 packed, sRGB
 	std::vector<Camera> cams;
 	std::vector<float> xforms;  // [n_images x 12] the raw (start) transforms, as uploaded after the pixels
+	// Depth images (NerfDataset::depthmemory, nerf_loader.cu:943-960): per image fp32 [height][width] on the device or
+	// null. The loss pass reads the device array of these pointers, d_depth [n_images], which exists once an image
+	// has had depth set; Camera, which is also compiled for the host, keeps its layout.
+	std::vector<float*> depth;
+	float** d_depth = nullptr;
+	uint32_t n_depth = 0;  // images with depth
 	~Dataset();
 };
 
@@ -121,6 +127,13 @@ struct LossArgs {
 	const float* envmap;
 	uint32_t env_w, env_h, env_loss_type;
 	unsigned long long* env_acc;
+	// depth supervision (testbed_nerf.cu:1725-1748, 1848-1856, 1912-1956): with depth_lambda > 0 and a dataset in which
+	// an image has depth, the kernels' depth instantiations run: pass 1 also composites the samples' distances from the
+	// ray origin, pass 2 adds depth_lambda * dL_depth/d(depth_ray) * (T depth - depth suffix) to the density gradient of
+	// rays whose texel has a depth > 0, with the gradient of depth_loss_type. The kept state then has a sixth plane,
+	// the depth prefix through the sample ([6][state_cap]). Otherwise nothing of this is read.
+	float depth_lambda;
+	uint32_t depth_loss_type;
 };
 
 // The environment map's stand-alone forms (envmap.hip): dirs [n x 3] normalized; texels, weights [n x 4] as
@@ -188,6 +201,9 @@ void grid_ema_mean_bitfield(uint32_t n_el, float decay, float* grid, const float
                             uint8_t* bitfield, hipStream_t s);
 size_t sample_tmp_f32(uint32_t n_rays);  // floats of sample_rays' tmp_f32 (stored t per step + ray geometry)
 size_t loss_tmp_f32(uint32_t n_rays);    // floats of compute_loss' tmp_f32 (per-ray pass-1 results)
+// whether compute_loss runs its depth instantiations, and the floats of tmp_f32 they need (one more per ray)
+bool loss_depth_on(const Dataset& ds, const LossArgs& a);
+size_t loss_tmp_f32_depth(uint32_t n_rays);
 // construct_cdf_2d / construct_cdf_1d (testbed_nerf.cu:2356-2410) over the error map
 void error_map_cdfs(uint32_t n_images, uint32_t w, uint32_t h, const float* data, float* cdf_x_cond_y, float* cdf_y,
                     float* cdf_img, hipStream_t s);

@@ -1115,8 +1115,9 @@ void sample_rays(const Dataset& ds, const ngp_nerf_config& cfg, const SampleArgs
 // compute_loss_kernel_train_nerf (testbed_nerf.cu:1660-2012), split at its atomicAdd into two passes
 // around a prefix scan. The error map deposit (:1869-1899, always on in the reference's training) is
 // done in pass 2 after the compaction early-out, as there, and so is the environment map's gradient
-// deposit (:1988-2011; envmap.h); sharpness / exposure / depth supervision are off in the
-// reference's default training and not implemented.
+// deposit (:1988-2011; envmap.h), and depth supervision (:1725-1748, 1848-1856, 1912-1956;
+// DESIGN.md §8e) is the kernels' DEPTH instantiation; sharpness / exposure are off in the reference's default
+// training and not implemented.
 // A ray owns one DPP row: lanes load and activate 16 samples at once (network output, dt, exp), and
 // the compositing recurrence (T *= 1 - alpha, rgb += alpha T c) runs over the row in sample order
 // with row_newbcast broadcasts, i.e. with the reference's float ops in the reference's order.
@@ -1136,16 +1137,27 @@ __device__ __forceinline__ V3 unwarp_pos(const float* c, const Aabb& b) {
 	return v3(b.mn.x + c[0] * (b.mx.x - b.mn.x), b.mn.y + c[1] * (b.mx.y - b.mn.y), b.mn.z + c[2] * (b.mx.z - b.mn.z));
 }
 
+// distance(unwarp_position(c), ray_o): a sample's depth along its ray, one expression for both passes
+__device__ __forceinline__ float sample_depth(const float* c, const Aabb& b, float ox, float oy, float oz) {
+	const V3 pos = unwarp_pos(c, b);
+	const float dx = pos.x - ox, dy = pos.y - oy, dz = pos.z - oz;
+	return sqrtf(dx * dx + dy * dy + dz * dz);
+}
+
 #define NGP_ROW_UNROLL16(M) M(0) M(1) M(2) M(3) M(4) M(5) M(6) M(7) M(8) M(9) M(10) M(11) M(12) M(13) M(14) M(15)
 
 // ENV: an environment map is bound (LossArgs::envmap): a separate instantiation, as CDF is
-template <bool CDF, bool ENV>
+// DEPTH: depth supervision is on (loss_depth_on): the lanes also load their sample's position, and the row recurrence
+// carries depth_ray += weight * distance(pos, ray_o) under rgb's stop rule; the ray's sum goes to depth_ray[i]
+template <bool CDF, bool ENV, bool DEPTH>
 __global__ void __launch_bounds__(256) k_loss_pass1(const Camera* __restrict__ cams, const uint32_t* __restrict__ pixels,
                                                     uint32_t n_images, const ngp_nerf_config cfg, LossArgs a,
-                                                    uint32_t* __restrict__ craw, LossRay* __restrict__ lr) {
+                                                    uint32_t* __restrict__ craw, LossRay* __restrict__ lr,
+                                                    float* __restrict__ depth_ray) {
 	// XCD-aware ray order (NGP_LOSS_XCD): the block on XCD x = blockIdx % 8 takes the rays whose samples
 	// k_sample_write wrote from XCD x (a wave per ray there: ray i on XCD (i / 4) % 8), so their coordinates
 	// can still be in that XCD's L2: rays 128 m + 32 q + 4 x + j (q, j in 0..3) for block 8 m + x
+	static_assert(!DEPTH || NGP_LOSS_SELECT, "the depth recurrence is written in the select form only");
 	uint32_t i;
 	const uint32_t L = threadIdx.x % LG;
 	if (NGP_LOSS_XCD) {
@@ -1193,9 +1205,18 @@ __global__ void __launch_bounds__(256) k_loss_pass1(const Camera* __restrict__ c
 	float t = 1.f;
 	const float eps = 1e-4f;
 	float rr = 0.f, rg = 0.f, rb = 0.f;
+	float dd = 0.f;  // DEPTH: depth_ray
 	uint32_t cn = 0;
 	bool stop = false;
 	const bool keep_state = NGP_LOSS_SELECT && a.state != nullptr;
+	Aabb box;
+	float ro0 = 0.f, ro1 = 0.f, ro2 = 0.f;
+	float pb[NGP_LOSS_PF][3];
+	if (DEPTH) {
+		box = cfg_aabb(cfg);
+		const float* ro = a.rays + (size_t)i * 6;
+		ro0 = ro[0]; ro1 = ro[1]; ro2 = ro[2];
+	}
 	// software pipelining: the loads of the next NGP_LOSS_PF chunks are in flight while a chunk's
 	// compositing chain runs (the chunk loop is unrolled by the depth, so every buffer keeps its registers)
 	f16x4 ob[NGP_LOSS_PF];
@@ -1204,9 +1225,14 @@ __global__ void __launch_bounds__(256) k_loss_pass1(const Camera* __restrict__ c
 	for (uint32_t d = 0; d < NGP_LOSS_PF; ++d) {
 		ob[d] = f16x4{(f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f};
 		db[d] = 0.f;
+		if (DEPTH) pb[d][0] = pb[d][1] = pb[d][2] = 0.f;
 		if (L + d * LG < numsteps) {
 			ob[d] = *(const f16x4*)(out + (size_t)(L + d * LG) * a.out_stride);
 			db[d] = ci[(size_t)(L + d * LG) * 7 + 3];
+			if (DEPTH) {
+#pragma unroll
+				for (int k = 0; k < 3; ++k) pb[d][k] = ci[(size_t)(L + d * LG) * 7 + k];
+			}
 		}
 	}
 	for (uint32_t c0 = 0; c0 < numsteps && !stop; c0 += NGP_LOSS_PF * LG)
@@ -1217,11 +1243,18 @@ __global__ void __launch_bounds__(256) k_loss_pass1(const Camera* __restrict__ c
 		const uint32_t jj = c + L;
 		const f16x4 o = ob[d];
 		const float dtw = db[d];
+		float pc[3] = {0.f, 0.f, 0.f};
+		if (DEPTH) { pc[0] = pb[d][0]; pc[1] = pb[d][1]; pc[2] = pb[d][2]; }
 		if (jj + NGP_LOSS_PF * LG < numsteps) {
 			ob[d] = *(const f16x4*)(out + (size_t)(jj + NGP_LOSS_PF * LG) * a.out_stride);
 			db[d] = ci[(size_t)(jj + NGP_LOSS_PF * LG) * 7 + 3];
+			if (DEPTH) {
+#pragma unroll
+				for (int k = 0; k < 3; ++k) pb[d][k] = ci[(size_t)(jj + NGP_LOSS_PF * LG) * 7 + k];
+			}
 		}
-		float alpha = 0.f, cr = 0.f, cg = 0.f, cb = 0.f;
+		float alpha = 0.f, cr = 0.f, cg = 0.f, cb = 0.f, cd = 0.f;
+		if (DEPTH && jj < numsteps) cd = sample_depth(pc, box, ro0, ro1, ro2);
 		if (jj < numsteps) {
 			const float dt = unwarp_dt(dtw);
 			const float density = network_to_density((float)o[3], cfg.density_activation);
@@ -1245,6 +1278,11 @@ __global__ void __launch_bounds__(256) k_loss_pass1(const Camera* __restrict__ c
 			rr = upd ? nr : rr; rg = upd ? ng : rg; rb = upd ? nb : rb; t = upd ? nt : t;              \
 			cn += upd ? 1u : 0u;                                                                       \
 			if (keep_state && L == K) { sw = weight; sT = nt; sr = nr; sg = ng; sb = nb; su = upd; }   \
+			if (DEPTH) {                                                                               \
+				const float nd = dd + weight * row_bcast<K>(cd);                                       \
+				dd = upd ? nd : dd;                                                                    \
+				if (keep_state && L == K) sd = nd;                                                     \
+			}                                                                                          \
 		}
 #else
 #define NGP_LOSS1_STEP(K)                                                                              \
@@ -1261,7 +1299,7 @@ __global__ void __launch_bounds__(256) k_loss_pass1(const Camera* __restrict__ c
 			}                                                                                          \
 		}
 #endif
-		float sw = 0.f, sT = 0.f, sr = 0.f, sg = 0.f, sb = 0.f;
+		float sw = 0.f, sT = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, sd = 0.f;
 		bool su = false;
 		NGP_ROW_UNROLL16(NGP_LOSS1_STEP)
 #undef NGP_LOSS1_STEP
@@ -1269,6 +1307,7 @@ __global__ void __launch_bounds__(256) k_loss_pass1(const Camera* __restrict__ c
 			const size_t si = (size_t)base + jj;
 			a.state[si] = sw; a.state[a.state_cap + si] = sT;
 			a.state[2 * a.state_cap + si] = sr; a.state[3 * a.state_cap + si] = sg; a.state[4 * a.state_cap + si] = sb;
+			if (DEPTH) a.state[5 * a.state_cap + si] = sd;
 		}
 	}
 	// channel ch of the target, the background and the loss (every lane of the row holds rr, rg, rb, t, cn)
@@ -1327,6 +1366,7 @@ __global__ void __launch_bounds__(256) k_loss_pass1(const Camera* __restrict__ c
 	q.u = u; q.v = v; q.img = img;
 	q.env[0] = eh0 | (eh1 << 16); q.env[1] = eh2;
 	lr[i] = q;
+	if (DEPTH) depth_ray[i] = dd;  // the background adds nothing to it
 }
 
 // error map deposit of one compacted ray (testbed_nerf.cu:1869-1899 without the sharpness factor,
@@ -1352,10 +1392,14 @@ __device__ __forceinline__ void deposit_error(const LossArgs& a, const Camera* _
 // where the samples are independent: a ray's samples then take ceil(cn / 64) rounds of loads instead of
 // ceil(cn / 16), and the long rays, each round a memory latency, set the kernel's time (fox: up to ~26 rounds)
 // ENV: an environment map's gradient accumulator is bound (LossArgs::env_acc): lane 0 deposits the ray's gradient
-template <uint32_t LANES, bool ENV>
+// DEPTH: depth supervision (loss_depth_on): every lane works out the ray's depth_loss_gradient from pass 1's depth_ray
+// and the target texel's depth (depth_imgs: the dataset's per-image pointers), after the compaction early-out as in the
+// reference, and each sample's density gradient takes depth_loss_gradient * (T depth - depth suffix) in all three forms
+template <uint32_t LANES, bool ENV, bool DEPTH>
 __global__ void __launch_bounds__(256) k_loss_pass2(const Camera* __restrict__ cams, const ngp_nerf_config cfg, LossArgs a,
                                                     const uint32_t* __restrict__ craw, const uint32_t* __restrict__ gpre,
-                                                    const LossRay* __restrict__ lr) {
+                                                    const LossRay* __restrict__ lr, const float* __restrict__ depth_ray_in,
+                                                    const float* const* __restrict__ depth_imgs) {
 	const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
 	const uint32_t i = gid / LANES, L = gid % LANES;
 	if (i >= a.n_rays || i >= *a.ray_counter) return;
@@ -1395,15 +1439,35 @@ __global__ void __launch_bounds__(256) k_loss_pass2(const Camera* __restrict__ c
 	const float* ci = a.coords_in + (size_t)base * 7;
 	float* co = a.coords_out + (size_t)compacted_base * 7;
 	f16* dl = a.dloss_doutput + (size_t)compacted_base * 16;
+	// target_depth, lg_depth and depth_loss_gradient (testbed_nerf.cu:1848-1856); the depth term enters neither loss[]
+	// nor the error map deposit
+	float depth_ray = 0.f, depth_loss_gradient = 0.f;
+	if (DEPTH) {
+		depth_ray = depth_ray_in[i];
+		const float d0 = ray[3], d1 = ray[4], d2 = ray[5];
+		const float* dimg = depth_imgs[q.img];
+		const Camera& cam = cams[q.img];
+		const float target_depth = sqrtf(d0 * d0 + d1 * d1 + d2 * d2) *
+		                           (a.depth_lambda > 0.0f && dimg ? dimg[pixel_index(q.u, q.v, cam.width, cam.height)] : -1.0f);
+		float ld, gd;
+		loss_channel(target_depth, depth_ray, a.depth_loss_type, &ld, &gd);
+		depth_loss_gradient = target_depth > 0.0f ? a.depth_lambda * gd : 0.0f;
+	}
 	// the gradient of compacted sample jj (cc its coordinates, o its network output, its weight my_w, the
 	// transmittance after it my_t and the rgb prefix through it my_r2), written with its coordinates
+	// my_d2 (DEPTH): the depth prefix through the sample
 	auto emit = [&](uint32_t jj, const float (&cc)[7], const f16x4& o, const float (&rgb)[3], float dt, float my_w, float my_t,
-	                const float (&my_r2)[3]) __attribute__((always_inline)) {
+	                const float (&my_r2)[3], float my_d2) __attribute__((always_inline)) {
 #pragma unroll
 		for (int k = 0; k < 7; ++k) co[(size_t)jj * 7 + k] = cc[k];
 		const V3 pos = unwarp_pos(cc, box);
 		const float ddx = pos.x - ro0, ddy = pos.y - ro1, ddz = pos.z - ro2;
 		const float depth = sqrtf(ddx * ddx + ddy * ddy + ddz * ddz);
+		float depth_supervision = 0.0f;
+		if (DEPTH) {
+			const float depth_suffix = depth_ray - my_d2;
+			depth_supervision = depth_loss_gradient * (my_t * depth - depth_suffix);
+		}
 		float suffix[3];
 		for (int k = 0; k < 3; ++k) suffix[k] = q.rgb_ray[k] - my_r2[k];
 		f16x4 g;
@@ -1415,7 +1479,7 @@ __global__ void __launch_bounds__(256) k_loss_pass2(const Camera* __restrict__ c
 		const float density_derivative = network_to_density_derivative((float)o[3], cfg.density_activation);
 		const float dotv = q.grad[0] * (my_t * rgb[0] - suffix[0]) + q.grad[1] * (my_t * rgb[1] - suffix[1]) +
 		                   q.grad[2] * (my_t * rgb[2] - suffix[2]);
-		const float dloss_by_dmlp = density_derivative * (dt * (dotv + 0.0f));
+		const float dloss_by_dmlp = density_derivative * (dt * (dotv + depth_supervision));
 		const float o3 = (float)o[3];
 		g[3] = (f16)(loss_scale * dloss_by_dmlp + (o3 < 0.0f ? -output_l1_reg_density : 0.0f) +
 		             (o3 > -10.0f && depth < cfg.near_distance ? 1e-4f : 0.0f));
@@ -1433,13 +1497,13 @@ __global__ void __launch_bounds__(256) k_loss_pass2(const Camera* __restrict__ c
 				const float my_r2[3] = {a.state[2 * a.state_cap + si], a.state[3 * a.state_cap + si], a.state[4 * a.state_cap + si]};
 				float rgb[3];
 				for (int k = 0; k < 3; ++k) rgb[k] = network_to_rgb((float)o[k], cfg.rgb_activation);
-				emit(jj, cc, o, rgb, unwarp_dt(cc[3]), my_w, my_t, my_r2);
+				emit(jj, cc, o, rgb, unwarp_dt(cc[3]), my_w, my_t, my_r2, DEPTH ? a.state[5 * a.state_cap + si] : 0.0f);
 			}
 			return;
 		}
 		// the ray's samples reach past the caller's state capacity (pass 1 kept no state there): every lane
 		// composites the ray in sample order itself, with pass 1's operations, and emits its own samples
-		float t = 1.f, r2[3] = {0.f, 0.f, 0.f};
+		float t = 1.f, r2[3] = {0.f, 0.f, 0.f}, d2 = 0.f;
 		for (uint32_t jj = 0; jj < cn; ++jj) {
 			float cc[7];
 #pragma unroll
@@ -1451,13 +1515,14 @@ __global__ void __launch_bounds__(256) k_loss_pass2(const Camera* __restrict__ c
 			const float alpha = 1.f - ngp_expf_fast(-network_to_density((float)o[3], cfg.density_activation) * dt);
 			const float weight = alpha * t;
 			r2[0] = r2[0] + weight * rgb[0]; r2[1] = r2[1] + weight * rgb[1]; r2[2] = r2[2] + weight * rgb[2];
+			if (DEPTH) d2 = d2 + weight * sample_depth(cc, box, ro0, ro1, ro2);
 			t = t * (1.f - alpha);
-			if (jj % LANES == L) emit(jj, cc, o, rgb, dt, weight, t, r2);
+			if (jj % LANES == L) emit(jj, cc, o, rgb, dt, weight, t, r2, d2);
 		}
 		return;
 	}
 	if constexpr (LANES == LG) {
-	float r2[3] = {0.f, 0.f, 0.f};
+	float r2[3] = {0.f, 0.f, 0.f}, d2 = 0.f;
 	float t = 1.0f;
 	// software pipelining as in pass 1: NGP_LOSS2_PF chunks' loads in flight ahead of the compositing
 	float cb[NGP_LOSS2_PF][7];
@@ -1489,7 +1554,8 @@ __global__ void __launch_bounds__(256) k_loss_pass2(const Camera* __restrict__ c
 			for (int k = 0; k < 7; ++k) cb[d][k] = ci[(size_t)(jj + NGP_LOSS2_PF * LG) * 7 + k];
 			ob[d] = *(const f16x4*)(out + (size_t)(jj + NGP_LOSS2_PF * LG) * a.out_stride);
 		}
-		float rgb[3] = {0.f, 0.f, 0.f}, alpha = 0.f, dt = 0.f;
+		float rgb[3] = {0.f, 0.f, 0.f}, alpha = 0.f, dt = 0.f, cd = 0.f;
+		if (DEPTH && valid) cd = sample_depth(cc, box, ro0, ro1, ro2);
 		if (valid) {
 			for (int k = 0; k < 3; ++k) rgb[k] = network_to_rgb((float)o[k], cfg.rgb_activation);
 			dt = unwarp_dt(cc[3]);
@@ -1502,31 +1568,42 @@ __global__ void __launch_bounds__(256) k_loss_pass2(const Camera* __restrict__ c
 #define NGP_LOSS2_STEP(K)                                                                              \
 		{                                                                                              \
 			const float ak = row_bcast<K>(alpha), rk = row_bcast<K>(rgb[0]), gk = row_bcast<K>(rgb[1]), bk = row_bcast<K>(rgb[2]); \
+			const float dk = DEPTH ? row_bcast<K>(cd) : 0.0f;                                              \
 			if (c0 + K < cn && K <= L) {                                                               \
 				const float weight = ak * t;                                                           \
 				r2[0] += weight * rk; r2[1] += weight * gk; r2[2] += weight * bk;                      \
+				if (DEPTH) d2 += weight * dk;                                                          \
 				t *= (1.0f - ak);                                                                      \
 				my_w = weight;                                                                         \
 			}                                                                                          \
 		}
 		NGP_ROW_UNROLL16(NGP_LOSS2_STEP)
 #undef NGP_LOSS2_STEP
-		const float my_t = t, my_r2[3] = {r2[0], r2[1], r2[2]};
+		const float my_t = t, my_r2[3] = {r2[0], r2[1], r2[2]}, my_d2 = d2;
 		t = row_bcast<15>(t);  // a next chunk exists only if this one is full: lane 15 then took all 16 samples
 		r2[0] = row_bcast<15>(r2[0]); r2[1] = row_bcast<15>(r2[1]); r2[2] = row_bcast<15>(r2[2]);
+		if (DEPTH) d2 = row_bcast<15>(d2);
 		if (!valid) continue;
-		emit(jj, cc, o, rgb, dt, my_w, my_t, my_r2);
+		emit(jj, cc, o, rgb, dt, my_w, my_t, my_r2, my_d2);
 	}
 	}
 }
 
 size_t loss_tmp_f32(uint32_t n_rays) { return (size_t)n_rays * (sizeof(LossRay) / 4); }
+// depth_ray, one float per ray after the LossRay array: LossRay and the default path's scratch keep their size
+size_t loss_tmp_f32_depth(uint32_t n_rays) { return loss_tmp_f32(n_rays) + n_rays; }
+bool loss_depth_on(const Dataset& ds, const LossArgs& a) { return a.depth_lambda > 0.0f && ds.n_depth > 0 && ds.d_depth != nullptr; }
 
 void compute_loss(const Dataset& ds, const ngp_nerf_config& cfg, const LossArgs& a, uint32_t* tmp, float* tmpf, hipStream_t s) {
 	if (a.n_rays == 0) return;
 	uint32_t* craw = tmp;
 	uint32_t* gpre = tmp + a.n_rays;  // per group of 4 rays
 	LossRay* lr = (LossRay*)tmpf;
+	// depth supervision: the kernels' DEPTH instantiations, and one more float per ray behind the LossRay array (tmpf
+	// then holds loss_tmp_f32_depth floats); off: the launches and bytes written are those of a build without it
+	const bool depth_on = loss_depth_on(ds, a);
+	float* depth_ray = depth_on ? tmpf + loss_tmp_f32(a.n_rays) : nullptr;
+	const float* const* dimgs = depth_on ? ds.d_depth : nullptr;
 	const uint32_t blocks = div_round_up((size_t)a.n_rays * LG, 256);
 	{
 		ProfScope ps("loss_pass1", s);
@@ -1534,9 +1611,15 @@ void compute_loss(const Dataset& ds, const ngp_nerf_config& cfg, const LossArgs&
 		const uint32_t b1 = NGP_LOSS_XCD ? 8 * div_round_up(a.n_rays, 128) : blocks;
 		NGP_CHECK(!a.envmap || (a.env_w > 0 && a.env_h > 0 && a.rays), "compute_loss: environment map without a resolution or rays");
 		NGP_CHECK(!a.env_acc || a.envmap, "compute_loss: an environment map gradient needs the map");
-		auto pass1 = a.envmap ? (a.cdfs.any() ? k_loss_pass1<true, true> : k_loss_pass1<false, true>)
-		                      : (a.cdfs.any() ? k_loss_pass1<true, false> : k_loss_pass1<false, false>);
-		pass1<<<b1, 256, 0, s>>>(ds.d_cams, ds.d_pixels, ds.n_images, cfg, a, craw, lr);
+		auto pass1 = a.envmap ? (a.cdfs.any() ? k_loss_pass1<true, true, false> : k_loss_pass1<false, true, false>)
+		                      : (a.cdfs.any() ? k_loss_pass1<true, false, false> : k_loss_pass1<false, false, false>);
+		if (depth_on) {
+			NGP_CHECK(a.rays, "compute_loss: depth supervision needs the rays");
+			NGP_CHECK(a.depth_loss_type <= LOSS_RELL2, "compute_loss: unknown depth loss");
+			pass1 = a.envmap ? (a.cdfs.any() ? k_loss_pass1<true, true, true> : k_loss_pass1<false, true, true>)
+			                 : (a.cdfs.any() ? k_loss_pass1<true, false, true> : k_loss_pass1<false, false, true>);
+		}
+		pass1<<<b1, 256, 0, s>>>(ds.d_cams, ds.d_pixels, ds.n_images, cfg, a, craw, lr, depth_ray);
 		NGP_HIP(hipGetLastError());
 	}
 	{
@@ -1548,11 +1631,13 @@ void compute_loss(const Dataset& ds, const ngp_nerf_config& cfg, const LossArgs&
 	static_assert(NGP_LOSS_SELECT, "pass 1 keeps the compositing state pass 2 reads only in its select form");
 	if (a.state) {
 		constexpr uint32_t W = NGP_LOSS2_LANES;  // a wave per ray: see k_loss_pass2
-		auto pass2 = a.env_acc ? k_loss_pass2<W, true> : k_loss_pass2<W, false>;
-		pass2<<<div_round_up((size_t)a.n_rays * W, 256), 256, 0, s>>>(ds.d_cams, cfg, a, craw, gpre, lr);
+		auto pass2 = depth_on ? (a.env_acc ? k_loss_pass2<W, true, true> : k_loss_pass2<W, false, true>)
+		                      : (a.env_acc ? k_loss_pass2<W, true, false> : k_loss_pass2<W, false, false>);
+		pass2<<<div_round_up((size_t)a.n_rays * W, 256), 256, 0, s>>>(ds.d_cams, cfg, a, craw, gpre, lr, depth_ray, dimgs);
 	} else {
-		auto pass2 = a.env_acc ? k_loss_pass2<LG, true> : k_loss_pass2<LG, false>;
-		pass2<<<blocks, 256, 0, s>>>(ds.d_cams, cfg, a, craw, gpre, lr);
+		auto pass2 = depth_on ? (a.env_acc ? k_loss_pass2<LG, true, true> : k_loss_pass2<LG, false, true>)
+		                      : (a.env_acc ? k_loss_pass2<LG, true, false> : k_loss_pass2<LG, false, false>);
+		pass2<<<blocks, 256, 0, s>>>(ds.d_cams, cfg, a, craw, gpre, lr, depth_ray, dimgs);
 	}
 	NGP_HIP(hipGetLastError());
 }
@@ -2530,6 +2615,8 @@ void effective_camera_matrix(const float xf[12], float out[12]) {
 }
 
 Dataset::~Dataset() {
+	for (float* d : depth) if (d) (void)hipFree(d);
+	if (d_depth) (void)hipFree(d_depth);
 	if (d_cams) (void)hipFree(d_cams);
 	if (d_pixels) (void)hipFree(d_pixels);
 }

@@ -29,7 +29,8 @@ int run_compute_loss(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, voi
 		NGP_CHECK(a.n_rays > 0 || !a.pub_host, "compute_loss: the counters are published by the scan, which needs rays");
 		if (a.n_rays == 0) { NGP_HIP(hipMemsetAsync(a.compacted_counter, 0, 4, S(stream))); return NGP_OK; }
 		static thread_local Buf tmp, tmpf;
-		compute_loss(ds->ds, *cfg, a, tmp.get<uint32_t>(2 * (size_t)a.n_rays), tmpf.get<float>(loss_tmp_f32(a.n_rays)), S(stream));
+		const size_t nf = loss_depth_on(ds->ds, a) ? loss_tmp_f32_depth(a.n_rays) : loss_tmp_f32(a.n_rays);
+		compute_loss(ds->ds, *cfg, a, tmp.get<uint32_t>(2 * (size_t)a.n_rays), tmpf.get<float>(nf), S(stream));
 	});
 }
 
@@ -123,6 +124,42 @@ int ngp_nerf_dataset_create(uint32_t n_images, const ngp_nerf_image* images, con
 }
 
 void ngp_nerf_dataset_destroy(ngp_nerf_dataset* d) { delete d; }
+
+// NerfDataset::set_training_image's depth part (nerf_loader.cu:943-960) with copy_depth (:81-90): one fp32 multiply
+// per pixel, done on the host, so the stored value is (float)pixel * depth_scale bit for bit
+int ngp_nerf_dataset_set_depth(ngp_nerf_dataset* d, uint32_t image, const void* depth_host, int dtype, float depth_scale) {
+	if (!d || image >= d->ds.n_images || (dtype != 0 && dtype != 1) || std::isnan(depth_scale)) return NGP_INVALID;
+	NERF_TRY({
+		Dataset& ds = d->ds;
+		NGP_HIP(hipDeviceSynchronize());  // no loss pass may still be reading the pointers or the image
+		if (ds.depth.empty()) ds.depth.assign(ds.n_images, nullptr);
+		const size_t n = (size_t)ds.cams[image].width * ds.cams[image].height;
+		if (!depth_host && depth_scale < 0.f) {
+			if (ds.depth[image]) { NGP_HIP(hipFree(ds.depth[image])); ds.depth[image] = nullptr; --ds.n_depth; }
+		} else {
+			std::vector<float> v(n, 0.0f);  // no depth data for this image: zeros
+			if (depth_host && depth_scale > 0.f) {
+				if (dtype == 0) for (size_t k = 0; k < n; ++k) v[k] = (float)((const uint16_t*)depth_host)[k] * depth_scale;
+				else for (size_t k = 0; k < n; ++k) v[k] = ((const float*)depth_host)[k] * depth_scale;
+			}
+			if (!ds.depth[image]) { NGP_HIP(hipMalloc(&ds.depth[image], n * 4)); ++ds.n_depth; }
+			NGP_HIP(hipMemcpy(ds.depth[image], v.data(), n * 4, hipMemcpyHostToDevice));
+		}
+		if (!ds.d_depth) NGP_HIP(hipMalloc(&ds.d_depth, ds.n_images * sizeof(float*)));
+		NGP_HIP(hipMemcpy(ds.d_depth, ds.depth.data(), ds.n_images * sizeof(float*), hipMemcpyHostToDevice));
+	});
+}
+
+int ngp_nerf_dataset_depth(const ngp_nerf_dataset* d, uint32_t image, float* out_host, uint64_t cap, int* has_depth) {
+	if (!d || image >= d->ds.n_images) return NGP_INVALID;
+	const Dataset& ds = d->ds;
+	const float* src = ds.depth.empty() ? nullptr : ds.depth[image];
+	const size_t n = (size_t)ds.cams[image].width * ds.cams[image].height;
+	if (src && out_host && cap < n) return NGP_INVALID;
+	if (has_depth) *has_depth = src ? 1 : 0;
+	if (!src || !out_host) return NGP_OK;
+	NERF_TRY(NGP_HIP(hipMemcpy(out_host, src, n * 4, hipMemcpyDeviceToHost)));
+}
 
 int ngp_nerf_generate_training_samples(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
                                        uint32_t ray_offset, uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples,
@@ -240,6 +277,43 @@ int ngp_nerf_compute_loss_envmap(const ngp_nerf_dataset* ds, const ngp_nerf_conf
 		const int rc = run_compute_loss(ds, cfg, stream, a);
 		if (rc != NGP_OK) return rc;  // the error string is set
 		if (envmap_gradient) envmap_gradient_f32(env_width, env_height, a.env_acc, envmap_gradient, S(stream));
+	});
+}
+
+int ngp_nerf_compute_loss_depth(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
+                                uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples_compacted, const uint32_t* ray_counter,
+                                const void* network_output, const uint32_t* ray_indices, const float* rays, uint32_t* numsteps,
+                                const float* coords_in, float* coords_out, void* dloss_doutput, float* loss,
+                                uint32_t* compacted_counter, const float* mean_density, float loss_scale, float* error_map,
+                                uint32_t em_width, uint32_t em_height, const ngp_nerf_error_cdfs* cdfs, const float* envmap,
+                                uint32_t env_width, uint32_t env_height, uint32_t envmap_loss_type, float* envmap_gradient,
+                                float* sample_state, uint64_t state_capacity, float depth_supervision_lambda,
+                                uint32_t depth_loss_type) {
+	if (!(depth_supervision_lambda >= 0.0f) || std::isinf(depth_supervision_lambda) || depth_loss_type > LOSS_RELL2) return NGP_INVALID;
+	if (depth_supervision_lambda > 0.0f && !rays) return NGP_INVALID;
+	if (envmap ? (!rays || !envmap_dims_ok(env_width, env_height) || envmap_loss_type > LOSS_RELL2) : envmap_gradient != nullptr)
+		return NGP_INVALID;
+	if (sample_state && state_capacity == 0) return NGP_INVALID;
+	if (error_map && (em_width < 2 || em_height < 2)) return NGP_INVALID;
+	NERF_TRY({
+		static thread_local Buf acc;
+		LossArgs a = public_loss_args(n_rays, n_rays_total, rng, max_samples_compacted, ray_counter, network_output, ray_indices, rays,
+		                              numsteps, coords_in, coords_out, dloss_doutput, loss, compacted_counter, mean_density, loss_scale);
+		if (!error_cdfs_arg(cdfs, &a.cdfs)) return NGP_INVALID;
+		a.error_map = error_map; a.em_w = em_width; a.em_h = em_height;
+		a.state = sample_state; a.state_cap = state_capacity;
+		a.depth_lambda = depth_supervision_lambda; a.depth_loss_type = depth_loss_type;
+		if (envmap) {
+			a.envmap = envmap; a.env_w = env_width; a.env_h = env_height; a.env_loss_type = envmap_loss_type;
+			if (envmap_gradient) {
+				const size_t words = envmap_acc_words64(env_width, env_height);
+				a.env_acc = acc.get<unsigned long long>(words);
+				NGP_HIP(hipMemsetAsync(a.env_acc, 0, words * 8, S(stream)));
+			}
+		}
+		const int rc = run_compute_loss(ds, cfg, stream, a);
+		if (rc != NGP_OK) return rc;  // the error string is set
+		if (a.env_acc) envmap_gradient_f32(env_width, env_height, a.env_acc, envmap_gradient, S(stream));
 	});
 }
 

@@ -237,6 +237,9 @@ struct ngp_nerf_trainer {
 	// published) instead of waiting for this step's release
 	bool two_sets() const { return early() || (cam.optimize_extrinsics != 0 && !dp()); }
 	Buf loss_state;  // compute_loss: pass 1's per-sample compositing state for pass 2 (LossArgs::state)
+	// depth supervision (ngp_nerf_trainer_set_depth_supervision): off at 0, or while no image of the dataset has depth
+	float depth_lambda = 0.0f;
+	uint32_t depth_loss_type = LOSS_L1;
 	// Camera pose refinement (Testbed::Nerf::Training::optimize_extrinsics and its neighbours, testbed.h:716-785). The
 	// trainer traces its own device copy of the cameras: the dataset's array to begin with (bit for bit), rebuilt from
 	// `xforms` and the per-camera offsets (ngp_pose_apply, then effective_camera_matrix) whenever those change; d_raw

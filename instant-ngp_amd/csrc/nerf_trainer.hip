@@ -169,6 +169,22 @@ int ngp_nerf_trainer_get_error_sampling(const ngp_nerf_trainer* t, int* focal_pl
 	return NGP_OK;
 }
 
+// ---- depth supervision -------------------------------------------------------------------------------------------
+// Training::depth_supervision_lambda / depth_loss_type (testbed.h:719, 745). Only the loss pass reads them: the sampler,
+// and so a prelaunched one, does not depend on them, and nothing is discarded.
+int ngp_nerf_trainer_set_depth_supervision(ngp_nerf_trainer* t, float lambda, uint32_t loss_type) {
+	if (!t || !(lambda >= 0.0f) || std::isinf(lambda) || loss_type > LOSS_RELL2) return NGP_INVALID;
+	t->depth_lambda = lambda;
+	t->depth_loss_type = loss_type;
+	return NGP_OK;
+}
+int ngp_nerf_trainer_get_depth_supervision(const ngp_nerf_trainer* t, float* lambda, uint32_t* loss_type) {
+	if (!t) return NGP_INVALID;
+	if (lambda) *lambda = t->depth_lambda;
+	if (loss_type) *loss_type = t->depth_loss_type;
+	return NGP_OK;
+}
+
 // ---- environment map ---------------------------------------------------------------------------------------------
 // The map's gradient is summed on one GPU and stepped there; all-reducing it is not implemented
 static const char* const TRAIN_ENVMAP_VS_DATA_PARALLEL =
@@ -781,8 +797,11 @@ static void step_loss_and_publish(ngp_nerf_trainer* t, hipStream_t s, const Step
 	{
 		ProfScope ps("nerf_loss", s);
 		// pass 1 keeps each composited sample's state for pass 2 (indexed like the sampler's samples, at most max_samples)
-		float* lstate = t->knobs.loss_state ? t->loss_state.get<float>((size_t)5 * sp.max_samples) : nullptr;
+		// (a sixth plane, the depth prefix, with depth supervision on)
 		LossArgs a{};
+		a.depth_lambda = t->depth_lambda; a.depth_loss_type = t->depth_loss_type;
+		const size_t planes = loss_depth_on(t->data->ds, a) ? 6 : 5;
+		float* lstate = t->knobs.loss_state ? t->loss_state.get<float>(planes * sp.max_samples) : nullptr;
 		a.n_rays = Rl; a.n_rays_total_for_image_idx = R; a.rng = Rng{c.rng.state, c.rng.inc};
 		a.max_samples_compacted = Bl; a.ray_counter = ctr; a.network_output = c.mlp_out; a.out_stride = 4;
 		a.ray_indices = sp.ray_indices; a.rays = sp.rays; a.numsteps = sp.numsteps; a.coords_in = sp.coords; a.coords_out = c.coords_c;

@@ -80,9 +80,26 @@ void load_training_data(Testbed& tb, const std::string& path) {
 			envmap = py::array_t<float, py::array::c_style | py::array::forcecast>(d.attr("envmap"));
 			if (envmap.ndim() != 3 || envmap.shape(2) != 4) throw std::runtime_error("load_training_data: the envmap is an [H, W, 4] RGBA image");
 		}
+		// the frames' depth images (uint16) and the scale the dataset multiplies them by (nerf_loader.cu:609-621, 711)
+		std::vector<py::array_t<uint16_t, py::array::c_style | py::array::forcecast>> depth(meta.size());
+		std::vector<float> depth_scale(meta.size(), -1.0f);
+		std::vector<bool> has_depth(meta.size(), false);
+		if (py::hasattr(d, "depth") && py::hasattr(d, "depth_scale")) {
+			py::list dl = d.attr("depth"), sl = d.attr("depth_scale");
+			for (size_t i = 0; i < meta.size() && i < py::len(dl) && i < py::len(sl); ++i) {
+				if (py::object(dl[i]).is_none()) continue;
+				depth[i] = py::array_t<uint16_t, py::array::c_style | py::array::forcecast>(dl[i]);
+				if (depth[i].ndim() != 2 || (uint32_t)depth[i].shape(0) != meta[i].height || (uint32_t)depth[i].shape(1) != meta[i].width)
+					throw std::runtime_error("load_training_data: depth image shape does not match its image");
+				depth_scale[i] = py::object(sl[i]).cast<float>();
+				has_depth[i] = true;
+			}
+		}
 		py::gil_scoped_release nogil;
 		tb.load_nerf(meta, ptrs, aabb_scale, scale, offset);
 		if (has_envmap) tb.set_dataset_envmap((uint32_t)envmap.shape(1), (uint32_t)envmap.shape(0), envmap.data());
+		for (size_t i = 0; i < meta.size(); ++i)
+			if (has_depth[i]) tb.set_image_depth((uint32_t)i, depth[i].data(), 0, depth_scale[i]);
 		break;
 	}
 	case ETestbedMode::Image: {
@@ -397,6 +414,44 @@ PYBIND11_MODULE(pyngp, m) {
 			     return std::move(out);
 		     }, py::arg("ema") = false,
 		     "Engine extension: the environment map [H, W, 4] (the raw parameters, or the EMA parameters rendering reads); None without one.")
+		// depth supervision (python_api.cu:616, 635, 657)
+		.def_property("depth_supervision_lambda", [](NerfTrainingView& v) { return v.t->depth_supervision_lambda(); },
+		              [](NerfTrainingView& v, float x) { v.t->set_depth_supervision(x, v.t->depth_loss_type()); })
+		.def_property("depth_loss_type", [](NerfTrainingView& v) { return (ELossType)v.t->depth_loss_type(); },
+		              [](NerfTrainingView& v, ELossType l) { v.t->set_depth_supervision(v.t->depth_supervision_lambda(), (uint32_t)l); })
+		.def("set_image",
+		     [](NerfTrainingView& v, int frame_idx, py::object img, py::object depth_img, float depth_scale) {
+			     if (!img.is_none() && py::len(img) != 0)
+				     throw std::runtime_error("set_image: replacing a training image's colours is not supported; pass img=None "
+				                              "(or an empty array) to set only its depth image");
+			     if (frame_idx < 0) throw std::runtime_error("set_image: no such training view");
+			     if (depth_img.is_none()) { v.t->set_image_depth((uint32_t)frame_idx, nullptr, 0, depth_scale); return; }
+			     py::array a = py::array::ensure(depth_img);
+			     if (!a || a.ndim() != 2) throw std::runtime_error("set_image: depth_img is a [H, W] uint16 or float32 array");
+			     const ngp_nerf_image& im = v.t->nerf_images().at((size_t)frame_idx);
+			     if ((uint32_t)a.shape(0) != im.height || (uint32_t)a.shape(1) != im.width)
+				     throw std::runtime_error("set_image: depth_img has the wrong resolution");
+			     const float s = depth_scale;  // as given, as in the reference (the loader's is integer_depth_scale * dataset scale)
+			     if (a.dtype().is(py::dtype::of<uint16_t>())) {
+				     py::array_t<uint16_t, py::array::c_style | py::array::forcecast> u(a);
+				     v.t->set_image_depth((uint32_t)frame_idx, u.data(), 0, s);
+			     } else {
+				     py::array_t<float, py::array::c_style | py::array::forcecast> f(a);
+				     v.t->set_image_depth((uint32_t)frame_idx, f.data(), 1, s);
+			     }
+		     },
+		     py::arg("frame_idx"), py::arg("img") = py::none(), py::arg("depth_img") = py::none(), py::arg("depth_scale") = 1.0f,
+		     "The depth part of Testbed.nerf.training.set_image: depth_img [H, W] (uint16 or float32) times depth_scale "
+		     "becomes the image's depth; None: zeros (with a negative depth_scale: no depth). img must be None.")
+		.def("depth_image", [](NerfTrainingView& v, int frame_idx) -> py::object {
+			     if (frame_idx < 0) throw std::runtime_error("depth_image: no such training view");
+			     const std::vector<float> d = v.t->image_depth((uint32_t)frame_idx);
+			     if (d.empty()) return py::none();
+			     const ngp_nerf_image& im = v.t->nerf_images().at((size_t)frame_idx);
+			     py::array_t<float> out({(py::ssize_t)im.height, (py::ssize_t)im.width});
+			     std::memcpy(out.mutable_data(), d.data(), d.size() * sizeof(float));
+			     return std::move(out);
+		     }, py::arg("frame_idx"), "Engine extension: the stored depth image [H, W] of a training view; None without one.")
 		// error-driven sampling (python_api.cu:624-625); not reproducible from run to run while on
 		.def_property("sample_focal_plane_proportional_to_error", [](NerfTrainingView& v) { return v.t->sample_focal_plane_by_error(); },
 		              [](NerfTrainingView& v, bool x) { v.t->set_error_sampling(x, v.t->sample_image_by_error()); })

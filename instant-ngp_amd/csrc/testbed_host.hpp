@@ -385,6 +385,7 @@ public:
 			push_camera_training();
 			push_error_sampling();
 			push_envmap();
+			push_depth_supervision();
 		}
 	}
 	uint64_t n_params() const { return m_model ? ngp_model_n_params(m_model) : 0; }
@@ -759,6 +760,38 @@ public:
 			check(ngp_nerf_trainer_set_error_sampling(m_nerf_trainer, m_sample_focal_plane_by_error, m_sample_image_by_error),
 			      "ngp_nerf_trainer_set_error_sampling");
 	}
+	// ---- depth supervision (nerf.training.depth_supervision_lambda / depth_loss_type, python_api.cu:616, 635; the depth
+	// part of set_image, :657): kept here until there is a trainer, pushed to a live one. The depth images live in the
+	// dataset (NerfDataset::set_training_image, nerf_loader.cu:943-960), so they outlast reset_network.
+	float depth_supervision_lambda() const { return m_depth_lambda; }
+	uint32_t depth_loss_type() const { return m_depth_loss_type; }
+	void set_depth_supervision(float lambda, uint32_t loss_type) {
+		if (!(lambda >= 0.f) || std::isinf(lambda)) throw std::runtime_error("depth_supervision_lambda: a finite value >= 0");
+		if (loss_type > 6) throw std::runtime_error("depth_loss_type: unknown loss");
+		m_depth_lambda = lambda;
+		m_depth_loss_type = loss_type;
+		push_depth_supervision();
+	}
+	void push_depth_supervision() {
+		if (m_nerf_trainer)
+			check(ngp_nerf_trainer_set_depth_supervision(m_nerf_trainer, m_depth_lambda, m_depth_loss_type),
+			      "ngp_nerf_trainer_set_depth_supervision");
+	}
+	// dtype 0 uint16, 1 float32; pixels null: zeros (or, with a negative scale, no depth)
+	void set_image_depth(uint32_t frame_idx, const void* pixels, int dtype, float depth_scale) {
+		if (!m_nerf_dataset) throw std::runtime_error("set_image: no NeRF training data loaded");
+		if (frame_idx >= m_nerf_images.size()) throw std::runtime_error("set_image: no such training view");
+		check(ngp_nerf_dataset_set_depth(m_nerf_dataset, frame_idx, pixels, dtype, depth_scale), "ngp_nerf_dataset_set_depth");
+	}
+	// the stored depth image of a training view (empty: none)
+	std::vector<float> image_depth(uint32_t frame_idx) const {
+		if (!m_nerf_dataset || frame_idx >= m_nerf_images.size()) throw std::runtime_error("depth: no such training view");
+		std::vector<float> out((size_t)m_nerf_images[frame_idx].width * m_nerf_images[frame_idx].height);
+		int has = 0;
+		check(ngp_nerf_dataset_depth(m_nerf_dataset, frame_idx, out.data(), out.size(), &has), "ngp_nerf_dataset_depth");
+		if (!has) out.clear();
+		return out;
+	}
 	// ---- environment map (Testbed::m_envmap, Training::train_envmap; testbed.cu:4133-4147, python_api.cu:618-653) ----
 	// The dataset's "envmap" image (nerf_loader.cu:516-528), or zeros of a resolution asked for with create_envmap
 	// when the dataset brings none: the trainer's map after every reset_network. Without either, train_envmap does
@@ -1000,6 +1033,8 @@ private:
 	ngp_nerf_camera_training m_cam_training{0, 16, 1e-4f, 1e-3f};  // testbed.h:716-785 defaults
 	bool m_sample_focal_plane_by_error = false, m_sample_image_by_error = false;  // testbed.h:733-734
 	bool m_train_envmap = false;            // Training::train_envmap
+	float m_depth_lambda = 0.f;             // Training::depth_supervision_lambda (testbed.h:719)
+	uint32_t m_depth_loss_type = 1;         // Training::depth_loss_type: L1 (testbed.h:745)
 	uint32_t m_envmap_res[2] = {0, 0};      // NerfDataset::envmap_resolution, or create_envmap's; 0: no map
 	std::vector<float> m_envmap_init;       // NerfDataset::envmap_data; empty: zeros
 	ngp_nerf_renderer* m_renderer = nullptr;

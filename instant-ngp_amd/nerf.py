@@ -106,6 +106,29 @@ class NerfDataset:
     def __len__(self):
         return len(self.images)
 
+    def set_depth(self, i, array, scale=1.0):
+        """Image i's depth image (NerfDataset::set_training_image's depth part): a uint16 or float32 array [h, w]; the
+        device keeps float32(pixel) * float32(scale). None or scale <= 0 stores zeros (no depth anywhere in the image);
+        None with a negative scale removes the image's depth."""
+        im = self.images[i]
+        if array is None:
+            check(lib().ngp_nerf_dataset_set_depth(self.handle, int(i), None, 0, float(scale)))
+            return
+        a = np.asarray(array)
+        if a.dtype not in (np.uint16, np.float32):
+            raise ValueError(f"depth image: uint16 or float32, not {a.dtype}")
+        if a.shape != (im.height, im.width):
+            raise ValueError(f"depth image shape {a.shape} != {(im.height, im.width)}")
+        a = np.ascontiguousarray(a)
+        check(lib().ngp_nerf_dataset_set_depth(self.handle, int(i), a.ctypes.data, 0 if a.dtype == np.uint16 else 1, float(scale)))
+
+    def depth(self, i):
+        """Image i's depth as stored, float32 [h, w], or None when the image has none."""
+        im = self.images[i]
+        out, has = np.zeros((im.height, im.width), np.float32), C.c_int32(0)
+        check(lib().ngp_nerf_dataset_depth(self.handle, int(i), out.ctypes.data, out.size, C.byref(has)))
+        return out if has.value else None
+
     def __del__(self):
         h = getattr(self, "handle", None)
         if h:
@@ -206,7 +229,7 @@ def training_pixels(ds, cfg, n_rays, rng, cdfs=None, ray_offset=0, n_rays_total=
 
 def compute_loss(ds, cfg, n_rays, rng, max_compacted, samples, network_output, mean_density, loss_scale=128.0,
                  n_rays_total=None, stream=None, error_map=None, keep_state=False, state_capacity=None, cdfs=None,
-                 envmap=None, envmap_gradient=None, envmap_loss=None):
+                 envmap=None, envmap_gradient=None, envmap_loss=None, depth_lambda=0.0, depth_loss="L1", depth_entry=None):
     """compute_loss_kernel_train_nerf (testbed_nerf.cu:1660-2012). `samples` is the dict returned by
     generate_training_samples (its numsteps is rewritten to the compacted {n, base}). error_map: a
     float32 device tensor [n_images, h, w] the compacted rays' losses are added into (:1869-1899).
@@ -218,7 +241,11 @@ def compute_loss(ds, cfg, n_rays, rng, max_compacted, samples, network_output, m
     envmap: a contiguous float32 device tensor [h, w, 4], the environment map behind every ray (testbed_nerf.cu:1781-1792;
     ngp_nerf_compute_loss_envmap, on its own: no error_map, keep_state or cdfs). envmap_gradient: a tensor of the same
     shape that is overwritten with the map's gradient (:1988-2011, an exact sum: the same bits in every run);
-    envmap_loss: the gradient's loss name or number (default: cfg.loss_type)."""
+    envmap_loss: the gradient's loss name or number (default: cfg.loss_type).
+    depth_lambda, depth_loss: depth supervision (testbed_nerf.cu:1848-1856, 1952-1956) against the dataset's depth images
+    (NerfDataset.set_depth) with the loss of that name or number. With depth_lambda > 0 (or depth_entry=True) the call
+    goes through ngp_nerf_compute_loss_depth, which takes error_map, cdfs, envmap and keep_state in any combination
+    (the kept state then has six planes); with depth_lambda 0 that entry point gives the others' bits."""
     dev = network_output.device
     # the kernel reads one output row per sample; samples never exceed the sampler's coords buffer
     if network_output.shape[0] < samples["coords"].shape[0]:
@@ -238,7 +265,22 @@ def compute_loss(ds, cfg, n_rays, rng, max_compacted, samples, network_output, m
         raise ValueError("error_map: a contiguous float32 tensor [n_images, h, w]")
     if envmap is None and envmap_gradient is not None:
         raise ValueError("envmap_gradient: needs envmap")
-    if envmap is not None:
+    if (depth_lambda > 0) if depth_entry is None else depth_entry:
+        for t in (envmap, envmap_gradient):
+            if t is not None and (t.dtype != torch.float32 or t.dim() != 3 or t.shape[2] != 4 or not t.is_contiguous()
+                                  or t.shape != envmap.shape or t.device != dev):
+                raise ValueError("envmap / envmap_gradient: contiguous float32 device tensors [h, w, 4] of one shape")
+        e, keep = _error_cdfs(cdfs, dev, len(ds))
+        em = (_ptr(error_map), error_map.shape[2], error_map.shape[1]) if error_map is not None else (None, 0, 0)
+        lt = cfg.loss_type if envmap_loss is None else (LOSS[envmap_loss] if isinstance(envmap_loss, str) else int(envmap_loss))
+        env = (_ptr(envmap), envmap.shape[1], envmap.shape[0], lt, _ptr(envmap_gradient)) if envmap is not None else (None, 0, 0, 0, None)
+        cap = (samples["coords"].shape[0] if state_capacity is None else int(state_capacity)) if keep_state else 0
+        state = torch.empty((6, cap), dtype=torch.float32, device=dev) if keep_state else None
+        dl = LOSS[depth_loss] if isinstance(depth_loss, str) else int(depth_loss)
+        check(lib().ngp_nerf_compute_loss_depth(*args, *em, C.byref(e) if e is not None else None, *env, _ptr(state), cap,
+                                                float(depth_lambda), dl))
+        torch.cuda.synchronize(dev)  # the kernels read `keep` and `state`
+    elif envmap is not None:
         if error_map is not None or keep_state or cdfs is not None:
             raise ValueError("envmap: without error_map, keep_state and cdfs (the C-ABI form takes none of them)")
         for t in (envmap, envmap_gradient):
@@ -614,6 +656,19 @@ class NerfTraining:
         f, i = C.c_int(), C.c_int()
         check(lib().ngp_nerf_trainer_get_error_sampling(self.handle, C.byref(f), C.byref(i)))
         return {"focal_plane": bool(f.value), "image": bool(i.value)}
+
+    # ---- depth supervision (nerf.training.depth_supervision_lambda / depth_loss_type, python_api.cu:616, 635) ----
+    def set_depth_supervision(self, lambda_, loss="L1"):
+        """Training::depth_supervision_lambda and depth_loss_type (defaults 0 and L1): the steps' loss pass adds the
+        depth term for rays whose training pixel has a depth > 0 (NerfDataset.set_depth). Only the loss pass reads them."""
+        check(lib().ngp_nerf_trainer_set_depth_supervision(self.handle, float(lambda_),
+                                                           LOSS[loss] if isinstance(loss, str) else int(loss)))
+
+    def depth_supervision(self):
+        """(lambda, loss name)."""
+        lam, lt = C.c_float(0), C.c_uint32(0)
+        check(lib().ngp_nerf_trainer_get_depth_supervision(self.handle, C.byref(lam), C.byref(lt)))
+        return lam.value, {v: k for k, v in LOSS.items()}[lt.value]
 
     # ---- environment map (nerf.training.train_envmap, python_api.cu:618-653; testbed.cu:4133-4147) ----
     ENVMAP_ARRAYS = {"params": 0, "ema": 1, "gradient": 2, "first_moments": 3, "second_moments": 4, "param_steps": 5}

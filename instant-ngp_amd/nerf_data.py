@@ -5,9 +5,10 @@ formats the training path consumes: the original NeRF/instant-ngp `transforms.js
 files), 8-bit images (PNG/JPEG/BMP... decoded to RGBA8 sRGB, EImageDataType::Byte), perspective and
 OpenCV / OpenCV-fisheye lenses, per-frame intrinsics overrides, `scale` / `offset` / `aabb` /
 `aabb_scale`, the sharpness filter, `n_frames`, `white_transparent` / `black_transparent`,
-`<file>.alpha.<ext>` alpha images, `dynamic_mask_<name>.png` masks and the `envmap` image. Not handled (the loader
-raises): EXR/HDR images, depth supervision, per-pixel ray files, rolling shutter, FTheta / LatLong /
-equirectangular lenses, Mitsuba scenes — none of the in-scope datasets use them.
+`<file>.alpha.<ext>` alpha images, `dynamic_mask_<name>.png` masks, the `envmap` image, and depth supervision:
+`integer_depth_scale`, `enable_depth_loading` and per-frame `depth_path` 16-bit images (nerf_loader.cu:404-422, 471,
+609-621, 711). Not handled (the loader raises): EXR/HDR images, per-pixel ray files, rolling shutter, FTheta /
+LatLong / equirectangular lenses, Mitsuba scenes — none of the in-scope datasets use them.
 Image decoding is PIL's (the reference uses stb_image); the pixels then travel to the device
 unchanged, as `set_training_image` does with `convert_rgba32` (nerf_loader.cu:49-71).
 """
@@ -123,6 +124,16 @@ def _decode(path):
         return np.array(im.convert("RGBA"), dtype=np.uint8)
 
 
+def _decode_depth(path):
+    """load_stbi_16(path, 1 channel): a single-channel 16-bit image as uint16 [h, w] (8-bit files widen as stb does,
+    v * 257)."""
+    from PIL import Image
+    with Image.open(path) as im:
+        if im.mode in ("I;16", "I;16L", "I;16B", "I"):
+            return np.ascontiguousarray(np.array(im).astype(np.uint16))
+        return np.ascontiguousarray(np.array(im.convert("L"), dtype=np.uint16) * np.uint16(257))
+
+
 def _srgb_to_linear(x):
     return np.where(x <= 0.04045, x / 12.92, ((x + 0.055) / 1.055) ** 2.4)
 
@@ -150,6 +161,10 @@ class LoadedNerf:
         self.scale, self.offset, self.aabb_scale = NERF_SCALE, [0.5, 0.5, 0.5], 1.0
         self.up = [0.0, 1.0, 0.0]
         self.envmap = None  # the "envmap" image: linear RGBA float32 [h, w, 4] (NerfTraining.set_envmap takes it)
+        # depth supervision: per image the uint16 pixels of its depth_path [h, w], or None (no depth_path, a missing
+        # file, enable_depth_loading false or no integer_depth_scale), and per image the scale the dataset multiplies
+        # them by: integer_depth_scale * scale (nerf_loader.cu:711)
+        self.depth, self.depth_scale = [], []
 
     @property
     def envmap_resolution(self):
@@ -161,7 +176,11 @@ class LoadedNerf:
 
     def to_device(self):
         """NerfDataset (pixels and cameras uploaded: set_training_image)."""
-        return NerfDataset(self.images, self.rgba8)
+        ds = NerfDataset(self.images, self.rgba8)
+        for i, (d, s) in enumerate(zip(self.depth, self.depth_scale)):
+            if d is not None:   # an image without depth pixels stays without depth: the same loss as the zeros the
+                ds.set_depth(i, d, s)   # reference stores for it, at no cost
+        return ds
 
 
 def load_nerf(jsonpaths, max_images=None):
@@ -178,6 +197,7 @@ def load_nerf(jsonpaths, max_images=None):
     res = LoadedNerf()
     jsons = [_load_json(p) for p in jsonpaths]
     per_json_frames = []
+    enable_depth_loading = True
     for path, j in zip(jsonpaths, jsons):
         base = os.path.dirname(path)
         if not isinstance(j.get("frames"), list):
@@ -224,8 +244,9 @@ def load_nerf(jsonpaths, max_images=None):
             res.up = [float(j["up"][1]), float(j["up"][2]), float(j["up"][0])]
         if "envmap" in j:  # the initial environment map; its resolution is the map's (nerf_loader.cu:516-528)
             res.envmap = _load_envmap(_resolve(base, j["envmap"]))
-        if "integer_depth_scale" in j or any("depth_path" in fr for fr in frames):
-            pass  # depth supervision is not part of the training path here: ignored like a missing depth file
+        if "enable_depth_loading" in j:   # like the reference's flag, it carries over to the files after this one
+            enable_depth_loading = bool(j["enable_depth_loading"])
+        integer_depth_scale = np.float32(j["integer_depth_scale"]) if "integer_depth_scale" in j else np.float32(-1.0)
         lens0 = {"mode": LENS_PERSPECTIVE, "params": [0.0] * 4, "principal": [0.5, 0.5]}
         _read_lens(j, lens0)
         for fr in frames:
@@ -272,6 +293,17 @@ def load_nerf(jsonpaths, max_images=None):
                                          lens_params=lens["params"]))
             res.rgba8.append(px)
             res.paths.append(p)
+            depth = None
+            if enable_depth_loading and integer_depth_scale > 0 and "depth_path" in fr:
+                dp = _resolve(base, fr["depth_path"])
+                if os.path.exists(dp):   # a missing depth file is ignored
+                    depth = _decode_depth(dp)
+                    if depth.shape != (h, w):
+                        raise ValueError(f"Depth image {dp} has wrong resolution.")
+            res.depth.append(depth)
+            res.depth_scale.append(integer_depth_scale)
     if not res.images:
         raise ValueError("No training images were found for NeRF training!")
+    # m.depth_scale * result.scale, in float, with the scale every file has had its say on (nerf_loader.cu:711)
+    res.depth_scale = [float(s * np.float32(res.scale)) for s in res.depth_scale]
     return res

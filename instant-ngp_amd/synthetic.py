@@ -56,8 +56,10 @@ _BOXES = [  # min, max, colour
 ]
 
 
-def render(c2w, width, height, camera_angle_x=LEGO_CAMERA_ANGLE_X, device="cpu"):
-    """RGBA8 [H, W, 4] of the procedural scene from Blender pose c2w."""
+def render(c2w, width, height, camera_angle_x=LEGO_CAMERA_ANGLE_X, device="cpu", return_depth=False):
+    """RGBA8 [H, W, 4] of the procedural scene from Blender pose c2w. return_depth: also the scene's z-depth per pixel,
+    float32 [H, W] in Blender units (distance along the camera's forward axis, what a depth image stores; 0 where the
+    ray misses): NerfDataset.set_depth(i, depth, scale=0.33) puts it into the engine's units."""
     f = 0.5 * width / math.tan(0.5 * camera_angle_x)
     j, i = torch.meshgrid(torch.arange(height, device=device, dtype=torch.float32),
                           torch.arange(width, device=device, dtype=torch.float32), indexing="ij")
@@ -65,6 +67,7 @@ def render(c2w, width, height, camera_angle_x=LEGO_CAMERA_ANGLE_X, device="cpu")
     R = torch.tensor(c2w[:3, :3], dtype=torch.float32, device=device)
     o = torch.tensor(c2w[:3, 3], dtype=torch.float32, device=device)
     d = d @ R.T
+    forward = 1.0 / d.norm(dim=-1)   # the unit direction's component along the camera's forward axis
     d = d / d.norm(dim=-1, keepdim=True)
     best = torch.full(d.shape[:2], float("inf"), device=device)
     col = torch.zeros(d.shape, device=device)
@@ -98,7 +101,10 @@ def render(c2w, width, height, camera_angle_x=LEGO_CAMERA_ANGLE_X, device="cpu")
     alpha = torch.isfinite(best)
     rgb = (col * shade[..., None]).clamp(0, 1)
     out = torch.cat([rgb, alpha[..., None].float()], -1) * alpha[..., None]
-    return (out * 255 + 0.5).clamp(0, 255).to(torch.uint8).cpu().numpy()
+    rgba8 = (out * 255 + 0.5).clamp(0, 255).to(torch.uint8).cpu().numpy()
+    if not return_depth:
+        return rgba8
+    return rgba8, torch.where(alpha, best * forward, torch.zeros_like(best)).cpu().numpy().astype(np.float32)
 
 
 def lego_like_dataset(n_images=100, width=800, height=800, seed=0, device="cpu", return_host=False):
