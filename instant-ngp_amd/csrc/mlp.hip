@@ -1,6 +1,7 @@
 // mlp.hip — MFMA kernels for the NerfNetwork MLP pair and for a single MLP (see mlp.h for the
 // register/LDS layout contract).
 #include "mlp.h"
+#include "mlp_image.h"
 #include "knobs.h"
 #include "slab_reduce.h"
 
@@ -221,45 +222,53 @@ __device__ __forceinline__ void mask_pack(const f32x16 (&acc)[TILES], const f16x
 		}
 }
 
+// The [sample][feature] images below are laid out by mlp_image.h (16-feature column blocks, sample rows permuted so
+// that img_frag's transposed reads are bank-conflict-free); every writer and reader goes through its offsets.
+//
 // Write packed accumulator-layout fragments (frags[2t+s] = tile t regs 8s..8s+7) of one sample
-// column into the wave's [sample][feature] image: features 32t + 16s + 8k + 4h + (0..3).
+// column into the wave's [sample][feature] image: features 32t + 16s + 8k + 4h + (0..3), i.e. frag q is the
+// image's 16-feature block q.
 template <int NFRAG>
-__device__ __forceinline__ void img_store_acc(f16* img, int stride, const f16x8* f, int lane, int feat0 = 0) {
+__device__ __forceinline__ void img_store_acc(f16* img, const f16x8* f, int lane) {
 	const int smp = lane & 31, h = lane >> 5;
-	f16* row = img + smp * stride + feat0 + 4 * h;
+	f16* row = img + mlp_image::offset(smp, 4 * h);
 #pragma unroll
 	for (int q = 0; q < NFRAG; ++q) {
-		// frag q covers tile q>>1, regs 8(q&1)..: features 32(q>>1) + 16(q&1) + 8k + 4h, k = 0,1
-		const int base = 32 * (q >> 1) + 16 * (q & 1);
-		*(f16x4*)(row + base) = f16x4{f[q][0], f[q][1], f[q][2], f[q][3]};
-		*(f16x4*)(row + base + 8) = f16x4{f[q][4], f[q][5], f[q][6], f[q][7]};
+		f16* p = row + q * mlp_image::BLOCK_HALVES;
+		*(f16x4*)p = f16x4{f[q][0], f[q][1], f[q][2], f[q][3]};
+		*(f16x4*)(p + 8) = f16x4{f[q][4], f[q][5], f[q][6], f[q][7]};
 	}
 }
 
 // Standard-order fragment (lane half h holds features 16s + 8h + 0..7) into the image.
-__device__ __forceinline__ void img_store_std(f16* img, int stride, const f16x8& f, int s, int lane) {
+__device__ __forceinline__ void img_store_std(f16* img, const f16x8& f, int s, int lane) {
 	const int smp = lane & 31, h = lane >> 5;
-	*(f16x8*)(img + smp * stride + 16 * s + 8 * h) = f;
+	const f16x8 v = mlp_image::quads_swapped(smp) ? f16x8{f[4], f[5], f[6], f[7], f[0], f[1], f[2], f[3]} : f;
+	*(f16x8*)(img + s * mlp_image::BLOCK_HALVES + mlp_image::offset16(smp, 8 * h)) = v;
 }
 
 // Operand for v_mfma_f32_16x16x32_f16 with K = the 32 samples: lane gets feature feat0 + (lane&15),
 // samples 8(lane>>4) + 0..7, via two ds_read_b64_tr_b16 (4 samples x 16 features per 16-lane group).
-__device__ __forceinline__ f16x8 img_frag(const f16* img, int stride, int feat0, int lane) {
-	const int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
-	const f16* a0 = img + (8 * g + q) * stride + feat0 + 4 * p;
+// feat0 is a multiple of 16; the second read's rows (+4) sit one octet (mlp_image.h) after the first's in every lane.
+__device__ __forceinline__ f16x8 img_frag_at(const f16* a0) {  // a0 = block start + this lane's frag_offset
 	const f16x4 lo = lds_read_tr16(a0);
-	const f16x4 hi = lds_read_tr16(a0 + 4 * stride);
+	const f16x4 hi = lds_read_tr16(a0 + mlp_image::FRAG_RD1_HALVES);
 	return f16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 }
+__device__ __forceinline__ f16x8 img_frag(const f16* img, int feat0, int lane) {
+	return img_frag_at(img + (feat0 >> 4) * mlp_image::BLOCK_HALVES + mlp_image::frag_offset(lane, 0, 0));
+}
+static_assert(mlp_image::frag_offset(37, 1, 32) == mlp_image::frag_offset(37, 0, 0) + 2 * mlp_image::BLOCK_HALVES + mlp_image::FRAG_RD1_HALVES,
+              "img_frag's address arithmetic follows mlp_image::frag_offset");
 
 // dW[out x in] += dZ * X^T over the wave's 32 samples, 16x16 tiles (mt over out, nt over in).
 template <int MT, int NT>
-__device__ __forceinline__ void dw_accum(f32x4* dw, const f16* dz_img, int dz_stride, const f16* x_img, int x_stride, int lane) {
+__device__ __forceinline__ void dw_accum(f32x4* dw, const f16* dz_img, const f16* x_img, int lane) {
 	f16x8 a[MT], b[NT];
 #pragma unroll
-	for (int m = 0; m < MT; ++m) a[m] = img_frag(dz_img, dz_stride, 16 * m, lane);
+	for (int m = 0; m < MT; ++m) a[m] = img_frag(dz_img, 16 * m, lane);
 #pragma unroll
-	for (int n = 0; n < NT; ++n) b[n] = img_frag(x_img, x_stride, 16 * n, lane);
+	for (int n = 0; n < NT; ++n) b[n] = img_frag(x_img, 16 * n, lane);
 #pragma unroll
 	for (int m = 0; m < MT; ++m)
 #pragma unroll
@@ -419,16 +428,17 @@ struct NerfLayout {
 	static constexpr int B_D0 = B_DH + 8 * (DH - 1);
 	static constexpr int ET = (ES + 1) / 2;               // 32-row tiles of the encoding gradient
 	static constexpr int N_ALL = B_D0 + 4 * ET;
-	// per-wave LDS images (halves); strides padded by 4 halves (8 B) against bank conflicts
-	static constexpr int S_XE = 16 * ES + 4;
-	static constexpr int S_64 = 64 + 4;
-	static constexpr int S_RIN = 32 + 4;
+	// per-wave LDS images (halves), laid out by mlp_image.h
+	static constexpr int N_XE = mlp_image::image_halves(16 * ES);
+	static constexpr int N_64 = mlp_image::image_halves(64);
+	static constexpr int N_RIN = mlp_image::image_halves(32);
+	static constexpr int N_16 = mlp_image::image_halves(16);
 	static constexpr int I_XE = 0;
-	static constexpr int I_HD = I_XE + 32 * S_XE;         // DH images
-	static constexpr int I_RIN = I_HD + DH * 32 * S_64;
-	static constexpr int I_HR = I_RIN + 32 * S_RIN;       // RH images
-	static constexpr int I_DZ = I_HR + RH * 32 * S_64;
-	static constexpr int IMG_HALVES = I_DZ + 32 * S_64;
+	static constexpr int I_HD = I_XE + N_XE;         // DH images
+	static constexpr int I_RIN = I_HD + DH * N_64;
+	static constexpr int I_HR = I_RIN + N_RIN;       // RH images
+	static constexpr int I_DZ = I_HR + RH * N_64;
+	static constexpr int IMG_HALVES = I_DZ + N_64;
 	// dW accumulator tiles (16x16)
 	static constexpr int W_RO = 0;                        // 1 x 4
 	static constexpr int W_RH = W_RO + 4;                 // (RH-1) x 16
@@ -587,7 +597,7 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(1, 
 		// ---- density forward -------------------------------------------------------------------
 		if constexpr (TRAIN) {
 #pragma unroll
-			for (int s = 0; s < ES; ++s) img_store_std(img + Lay::I_XE, Lay::S_XE, xe[s], s, lane);
+			for (int s = 0; s < ES; ++s) img_store_std(img + Lay::I_XE, xe[s], s, lane);
 		}
 		f32x16 acc[2];
 		f16x8 hd[DH][4];
@@ -610,20 +620,19 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(1, 
 		// add_density_gradient, or density_backward's own dL/doutput): dW of the density layers, dL/d(encoding)
 		auto density_backward = [&](f16x8 (&dd)[1], f16* dz_img) {
 			f16x8 dz[4];
-			img_store_acc<1>(dz_img, Lay::S_64, dd, lane);
-			dw_accum<1, 4>(dw + Lay::W_DO, dz_img, Lay::S_64, img + Lay::I_HD + (DH - 1) * 32 * Lay::S_64, Lay::S_64, lane);
+			img_store_acc<1>(dz_img, dd, lane);
+			dw_accum<1, 4>(dw + Lay::W_DO, dz_img, img + Lay::I_HD + (DH - 1) * Lay::N_64, lane);
 			layer_fwd<2, 1>(acc, dd, lfrag + Lay::B_DO * 64, lane);
 			mask_pack<2>(acc, hd[DH - 1], dz);
 #pragma unroll
 			for (int l = DH - 1; l >= 1; --l) {
-				img_store_acc<4>(dz_img, Lay::S_64, dz, lane);
-				dw_accum<4, 4>(dw + Lay::W_DH + 16 * (DH - 1 - l), dz_img, Lay::S_64, img + Lay::I_HD + (l - 1) * 32 * Lay::S_64,
-				               Lay::S_64, lane);
+				img_store_acc<4>(dz_img, dz, lane);
+				dw_accum<4, 4>(dw + Lay::W_DH + 16 * (DH - 1 - l), dz_img, img + Lay::I_HD + (l - 1) * Lay::N_64, lane);
 				layer_fwd<2, 4>(acc, dz, lfrag + (Lay::B_DH + 8 * (DH - 1 - l)) * 64, lane);
 				mask_pack<2>(acc, hd[l - 1], dz);
 			}
-			img_store_acc<4>(dz_img, Lay::S_64, dz, lane);
-			dw_accum<4, ES>(dw + Lay::W_D0, dz_img, Lay::S_64, img + Lay::I_XE, Lay::S_XE, lane);
+			img_store_acc<4>(dz_img, dz, lane);
+			dw_accum<4, ES>(dw + Lay::W_D0, dz_img, img + Lay::I_XE, lane);
 			if (a.dL_denc) {
 				// the MFMAs run with the full wave (every lane supplies A rows); only the stores are masked
 				f32x16 ae[Lay::ET];
@@ -648,7 +657,7 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(1, 
 			// NerfNetwork::density_forward / density_backward (nerf_network.h:355-428)
 			if (a.out && valid) store_out16(a.out, a.out_stride, a.out_layout, a.n, sample, h, dout[0]);
 #pragma unroll
-			for (int l = 0; l < DH; ++l) img_store_acc<4>(img + Lay::I_HD + l * 32 * Lay::S_64, Lay::S_64, hd[l], lane);
+			for (int l = 0; l < DH; ++l) img_store_acc<4>(img + Lay::I_HD + l * Lay::N_64, hd[l], lane);
 			f16x8 dd[1] = {valid ? dd_cur : f16x8{}};
 			density_backward(dd, img + Lay::I_DZ);
 			continue;
@@ -677,14 +686,14 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(1, 
 		else {
 			// ---- images of the forward activations (dW operands) ------------------------------
 #pragma unroll
-			for (int l = 0; l < DH; ++l) img_store_acc<4>(img + Lay::I_HD + l * 32 * Lay::S_64, Lay::S_64, hd[l], lane);
+			for (int l = 0; l < DH; ++l) img_store_acc<4>(img + Lay::I_HD + l * Lay::N_64, hd[l], lane);
 			{
 				f16x8 d1[1] = {dout[0]};
-				img_store_acc<1>(img + Lay::I_RIN, Lay::S_RIN, d1, lane);
-				img_store_std(img + Lay::I_RIN, Lay::S_RIN, rin[1], 1, lane);
+				img_store_acc<1>(img + Lay::I_RIN, d1, lane);
+				img_store_std(img + Lay::I_RIN, rin[1], 1, lane);
 			}
 #pragma unroll
-			for (int l = 0; l < RH; ++l) img_store_acc<4>(img + Lay::I_HR + l * 32 * Lay::S_64, Lay::S_64, hr[l], lane);
+			for (int l = 0; l < RH; ++l) img_store_acc<4>(img + Lay::I_HR + l * Lay::N_64, hr[l], lane);
 
 			// ---- rgb backward ---------------------------------------------------------------
 			f16* dz_img = img + Lay::I_DZ;
@@ -696,21 +705,20 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(1, 
 				// extract_rgb (nerf_network.h:46-60): rows 0..2 of dL/drgb, the rest zero
 				dz1[0] = h == 0 ? f16x8{d[0], d[1], d[2], (f16)0.f, 0, 0, 0, 0} : f16x8{};
 			}
-			img_store_acc<1>(dz_img, Lay::S_64, dz1, lane);
-			dw_accum<1, 4>(dw + Lay::W_RO, dz_img, Lay::S_64, img + Lay::I_HR + (RH - 1) * 32 * Lay::S_64, Lay::S_64, lane);
+			img_store_acc<1>(dz_img, dz1, lane);
+			dw_accum<1, 4>(dw + Lay::W_RO, dz_img, img + Lay::I_HR + (RH - 1) * Lay::N_64, lane);
 			f16x8 dz[4];
 			layer_fwd<2, 1>(acc, dz1, lfrag + Lay::B_RO * 64, lane);
 			mask_pack<2>(acc, hr[RH - 1], dz);
 #pragma unroll
 			for (int l = RH - 1; l >= 1; --l) {
-				img_store_acc<4>(dz_img, Lay::S_64, dz, lane);
-				dw_accum<4, 4>(dw + Lay::W_RH + 16 * (RH - 1 - l), dz_img, Lay::S_64, img + Lay::I_HR + (l - 1) * 32 * Lay::S_64,
-				               Lay::S_64, lane);
+				img_store_acc<4>(dz_img, dz, lane);
+				dw_accum<4, 4>(dw + Lay::W_RH + 16 * (RH - 1 - l), dz_img, img + Lay::I_HR + (l - 1) * Lay::N_64, lane);
 				layer_fwd<2, 4>(acc, dz, lfrag + (Lay::B_RH + 8 * (RH - 1 - l)) * 64, lane);
 				mask_pack<2>(acc, hr[l - 1], dz);
 			}
-			img_store_acc<4>(dz_img, Lay::S_64, dz, lane);
-			dw_accum<4, 2>(dw + Lay::W_R0, dz_img, Lay::S_64, img + Lay::I_RIN, Lay::S_RIN, lane);
+			img_store_acc<4>(dz_img, dz, lane);
+			dw_accum<4, 2>(dw + Lay::W_R0, dz_img, img + Lay::I_RIN, lane);
 			f32x16 a1[1];
 			layer_fwd<1, 4>(a1, dz, lfrag + Lay::B_R0 * 64, lane);
 			// dL/d(rgb input): rows 0..15 = dL/d(density output), rows 16..31 = dL/d(SH encoding);
@@ -757,8 +765,8 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(1, 
 //      registers (no LDS reads), and writes the activations and every layer's output gradient dZ
 //      to its LDS image [sample][feature];
 //   B  after a barrier, wave w accumulates its quarter of dW over the 4 images (K = 128 samples):
-//      row block m = w of the 64-row layers, column block n = w of the 16-row output layers
-//      (9 tiles = 36 registers at C2), then a second barrier frees the images.
+//      whole rows of one or two layers (TrainTiles below; 9 tiles = 36 registers at C2). The barrier
+//      that frees the images again sits in the next iteration, after its register-only forward chains.
 // Each wave ends up with disjoint dW tiles and stores them straight into the block's slab (no
 // cross-wave reduction). Sum order is fixed (block iterations, then waves 0..3): bitwise
 // reproducible like the one-wave-per-tile kernel.
@@ -766,151 +774,196 @@ template <int ES, int DH, int RH>
 struct NerfTrainLayout {
 	using L = NerfLayout<ES, DH, RH>;
 	static constexpr int N_BWD = L::N_ALL - L::N_FWD;
-	static constexpr int S_16 = 16 + 4;
 	// per-wave images (halves)
 	static constexpr int I_XE = 0;                                  // [32][16 ES]
-	static constexpr int I_HD = I_XE + 32 * L::S_XE;                // DH x [32][64]
-	static constexpr int I_RIN = I_HD + DH * 32 * L::S_64;          // [32][32] density out | SH
-	static constexpr int I_HR = I_RIN + 32 * L::S_RIN;              // RH x [32][64]
-	static constexpr int I_ZRO = I_HR + RH * 32 * L::S_64;          // dZ rgb output [32][16]
-	static constexpr int I_ZRH = I_ZRO + 32 * S_16;                 // (RH-1) x [32][64], j-th = layer RH-1-j
-	static constexpr int I_ZR0 = I_ZRH + (RH - 1) * 32 * L::S_64;   // dZ rgb layer 0
-	static constexpr int I_ZDO = I_ZR0 + 32 * L::S_64;              // dZ density output [32][16]
-	static constexpr int I_ZDH = I_ZDO + 32 * S_16;                 // (DH-1) x [32][64]
-	static constexpr int I_ZD0 = I_ZDH + (DH - 1) * 32 * L::S_64;   // dZ density layer 0
-	static constexpr int IMG_HALVES = I_ZD0 + 32 * L::S_64;
+	static constexpr int I_HD = I_XE + L::N_XE;                // DH x [32][64]
+	static constexpr int I_RIN = I_HD + DH * L::N_64;          // [32][32] density out | SH
+	static constexpr int I_HR = I_RIN + L::N_RIN;              // RH x [32][64]
+	static constexpr int I_ZRO = I_HR + RH * L::N_64;          // dZ rgb output [32][16]
+	static constexpr int I_ZRH = I_ZRO + L::N_16;                 // (RH-1) x [32][64], j-th = layer RH-1-j
+	static constexpr int I_ZR0 = I_ZRH + (RH - 1) * L::N_64;   // dZ rgb layer 0
+	static constexpr int I_ZDO = I_ZR0 + L::N_64;              // dZ density output [32][16]
+	static constexpr int I_ZDH = I_ZDO + L::N_16;                 // (DH-1) x [32][64]
+	static constexpr int I_ZD0 = I_ZDH + (DH - 1) * L::N_64;   // dZ density layer 0
+	static constexpr int IMG_HALVES = I_ZD0 + L::N_64;
 	static constexpr size_t LDS_BYTES = 4 * (size_t)IMG_HALVES * sizeof(f16);
-	// this wave's dW tiles
-	static constexpr int W_RO = 0;                    // rgb output:  m 0,    n = wave
-	static constexpr int W_RH = 1;                    // rgb hidden:  m = wave, n 0..3 (RH-1 layers)
-	static constexpr int W_R0 = W_RH + 4 * (RH - 1);  // rgb layer 0: m = wave, n 0..1
-	static constexpr int W_DO = W_R0 + 2;             // density out: m 0,    n = wave
-	static constexpr int W_DH = W_DO + 1;             // density hidden: m = wave, n 0..3
-	static constexpr int W_D0 = W_DH + 4 * (DH - 1);  // density layer 0: m = wave, n 0..ES-1
-	static constexpr int N_DW = W_D0 + ES;
 };
 
-// dW[m0+m][n0+n] += dZ^T X over one image's 32 samples (16x16x32 MFMAs, K = samples)
-template <int MC, int NC>
-__device__ __forceinline__ void dw_part(f32x4* dw, const f16* dz_img, int dz_stride, int m0, const f16* x_img, int x_stride, int n0,
-                                        int lane) {
-	f16x8 a[MC], b[NC];
-#pragma unroll
-	for (int m = 0; m < MC; ++m) a[m] = img_frag(dz_img, dz_stride, 16 * (m0 + m), lane);
-#pragma unroll
-	for (int n = 0; n < NC; ++n) b[n] = img_frag(x_img, x_stride, 16 * (n0 + n), lane);
-#pragma unroll
-	for (int m = 0; m < MC; ++m)
-#pragma unroll
-		for (int n = 0; n < NC; ++n) dw[m * NC + n] = mfma16(a[m], b[n], dw[m * NC + n]);
-}
-
-// Store dW tiles (16x16, 4 regs: out = 16m + 4(lane>>4) + r, in = 16n + (lane&15)) into the slab at
-// their parameter-slice positions [out x in].
-template <int MC, int NC>
-__device__ __forceinline__ void dw_store(const f32x4* dw, float* slab, uint32_t woff, uint32_t in_dim, int m0, int n0, int lane) {
-#pragma unroll
-	for (int m = 0; m < MC; ++m)
-#pragma unroll
-		for (int n = 0; n < NC; ++n)
-#pragma unroll
-			for (int r = 0; r < 4; ++r) {
-				const uint32_t o = 16 * (m0 + m) + 4 * (lane >> 4) + r, i = 16 * (n0 + n) + (lane & 15);
-				slab[woff + o * in_dim + i] = dw[m * NC + n][r];
-			}
-}
-
-// One image's phase-B operands (16x16x32 A/B fragments) for this wave's dW tiles (NerfTrainLayout W_*)
+// Phase B's dW tiles (16x16 fp32, out block m x in block n of one layer) and their split over the block's 4 waves.
+// Every wave holds N_DW = (all tiles) / 4 of them. A tile costs its wave one A fragment (dZ image, block m) and
+// one B fragment (activation image, block n) per image, shared with the wave's other tiles of that layer row or
+// column, so tiles are handed out in layer-major, row-major order: a wave gets whole rows of one layer (2 x 4 tiles
+// = 6 fragments) rather than a strip of every layer (9 tiles = 14 fragments at C2). Layer order: the rgb hidden
+// layers, rgb layer 0, the density hidden layers, the two 16-row output layers, then density layer 0. With one
+// encoding step, density layer 0 is a single column of 4 tiles: each wave takes one, so that the rest stays a
+// multiple of 8. Fragments per image over the block, C2: 8 + 8 + 8 + 12 = 36 (strips: 56); C2': 7 + 10 + 12 + 9 = 38
+// (60). The largest wave sets the registers of the double-buffered operands (2 x 12 fragments).
 template <int ES, int DH, int RH>
-struct PhaseBOps {
-	f16x8 ro_a, ro_b;
-	f16x8 rh_a[RH > 1 ? RH - 1 : 1], rh_b[RH > 1 ? RH - 1 : 1][4];
-	f16x8 r0_a, r0_b[2];
-	f16x8 do_a, do_b;
-	f16x8 dh_a[DH > 1 ? DH - 1 : 1], dh_b[DH > 1 ? DH - 1 : 1][4];
-	f16x8 d0_a, d0_b[ES];
-};
-
-// Phase B: this wave's quarter of dW over the block's four images (NerfTrainLayout W_*), between the
-// two barriers of an iteration.
-// DB: the next image's operands are requested before this image's MFMAs (two operand sets live)
-template <int ES, int DH, int RH, bool DB = true>
-__device__ __forceinline__ void train_phase_b(f32x4* dw, const f16* img_all, int wave, int lane) {
-	using Lay = NerfLayout<ES, DH, RH>;
+struct TrainTiles {
+	using L = NerfLayout<ES, DH, RH>;
 	using T = NerfTrainLayout<ES, DH, RH>;
-	// The operands of image w + 1 (28 ds_read_b64_tr_b16) are requested before image w's 9 MFMA tiles,
-	// which lets the scheduler keep more reads in flight (30.9 -> 30.5 us at C2; pinning that order
-	// with sched_barrier measured 31.4 us: at most 15 LDS reads can be outstanding per wave). Same
-	// products in the same order as dw_part: the gradients are unchanged bit for bit.
-	PhaseBOps<ES, DH, RH> ops[DB ? 2 : 1];
-	auto load_ops = [&](int w, PhaseBOps<ES, DH, RH>& o) {
-		const f16* im = img_all + w * T::IMG_HALVES;
-		o.ro_a = img_frag(im + T::I_ZRO, T::S_16, 0, lane);
-		o.ro_b = img_frag(im + T::I_HR + (RH - 1) * 32 * Lay::S_64, Lay::S_64, 16 * wave, lane);
-#pragma unroll
-		for (int j = 0; j < RH - 1; ++j) {
-			o.rh_a[j] = img_frag(im + T::I_ZRH + j * 32 * Lay::S_64, Lay::S_64, 16 * wave, lane);
-#pragma unroll
-			for (int n = 0; n < 4; ++n) o.rh_b[j][n] = img_frag(im + T::I_HR + (RH - 2 - j) * 32 * Lay::S_64, Lay::S_64, 16 * n, lane);
+	struct Layer { int mt, nt, a_img, b_img, rgb, woff, in_dim; };
+	static constexpr int NL = RH + DH + 2;
+	static constexpr int L_R0 = RH - 1, L_RO = RH + DH - 1, L_DO = RH + DH, L_D0 = RH + DH + 1;
+	static constexpr Layer layer(int i) {
+		if (i < RH - 1) return Layer{4, 4, T::I_ZRH + i * L::N_64, T::I_HR + (RH - 2 - i) * L::N_64, 1, 64 * 32 + 64 * 64 * (RH - 2 - i), 64};
+		if (i == L_R0) return Layer{4, 2, T::I_ZR0, T::I_RIN, 1, 0, 32};
+		if (i < L_RO) {
+			const int j = i - RH;
+			return Layer{4, 4, T::I_ZDH + j * L::N_64, T::I_HD + (DH - 2 - j) * L::N_64, 0, 64 * 16 * ES + 64 * 64 * (DH - 2 - j), 64};
 		}
-		o.r0_a = img_frag(im + T::I_ZR0, Lay::S_64, 16 * wave, lane);
-#pragma unroll
-		for (int n = 0; n < 2; ++n) o.r0_b[n] = img_frag(im + T::I_RIN, Lay::S_RIN, 16 * n, lane);
-		o.do_a = img_frag(im + T::I_ZDO, T::S_16, 0, lane);
-		o.do_b = img_frag(im + T::I_HD + (DH - 1) * 32 * Lay::S_64, Lay::S_64, 16 * wave, lane);
-#pragma unroll
-		for (int j = 0; j < DH - 1; ++j) {
-			o.dh_a[j] = img_frag(im + T::I_ZDH + j * 32 * Lay::S_64, Lay::S_64, 16 * wave, lane);
-#pragma unroll
-			for (int n = 0; n < 4; ++n) o.dh_b[j][n] = img_frag(im + T::I_HD + (DH - 2 - j) * 32 * Lay::S_64, Lay::S_64, 16 * n, lane);
+		if (i == L_RO) return Layer{1, 4, T::I_ZRO, T::I_HR + (RH - 1) * L::N_64, 1, 64 * 32 + 64 * 64 * (RH - 1), 64};
+		if (i == L_DO) return Layer{1, 4, T::I_ZDO, T::I_HD + (DH - 1) * L::N_64, 0, 64 * 16 * ES + 64 * 64 * (DH - 1), 64};
+		return Layer{4, ES, T::I_ZD0, T::I_XE, 0, 0, 16 * ES};
+	}
+	static constexpr int n_tiles() {
+		int n = 0;
+		for (int i = 0; i < NL; ++i) n += layer(i).mt * layer(i).nt;
+		return n;
+	}
+	static_assert(n_tiles() % 4 == 0, "dW tiles split evenly over the 4 waves");
+	static constexpr int N_DW = n_tiles() / 4;
+	static constexpr bool SPREAD_D0 = ES == 1;  // density layer 0's 4 x 1 tiles: one per wave
+	struct Tile { int layer, m, n; };
+	// tile t of wave w
+	static constexpr Tile tile(int w, int t) {
+		if (SPREAD_D0 && t == 0) return Tile{L_D0, w, 0};
+		int s = SPREAD_D0 ? w * (N_DW - 1) + t - 1 : w * N_DW + t;
+		for (int i = 0; i < NL; ++i) {
+			if (SPREAD_D0 && i == L_D0) continue;
+			const int k = layer(i).mt * layer(i).nt;
+			if (s < k) return Tile{i, s / layer(i).nt, s % layer(i).nt};
+			s -= k;
 		}
-		o.d0_a = img_frag(im + T::I_ZD0, Lay::S_64, 16 * wave, lane);
-#pragma unroll
-		for (int n = 0; n < ES; ++n) o.d0_b[n] = img_frag(im + T::I_XE, Lay::S_XE, 16 * n, lane);
+		return Tile{-1, 0, 0};
+	}
+	// wave w's operand fragments per image (each read once) and, per tile, which of them it multiplies
+	struct Plan {
+		int n_a, n_b;
+		int a_off[N_DW], b_off[N_DW];   // half offsets into a wave's images
+		int a_key[N_DW], b_key[N_DW];
+		int ta[N_DW], tb[N_DW];
 	};
-	if (DB) load_ops(0, ops[0]);
+	static constexpr Plan plan(int w) {
+		Plan p{};
+		for (int t = 0; t < N_DW; ++t) {
+			const Tile tl = tile(w, t);
+			const Layer ly = layer(tl.layer);
+			const int ka = tl.layer * 4 + tl.m, kb = tl.layer * 4 + tl.n;
+			int ia = -1, ib = -1;
+			for (int i = 0; i < p.n_a; ++i) if (p.a_key[i] == ka) ia = i;
+			for (int i = 0; i < p.n_b; ++i) if (p.b_key[i] == kb) ib = i;
+			if (ia < 0) { ia = p.n_a++; p.a_key[ia] = ka; p.a_off[ia] = ly.a_img + tl.m * mlp_image::BLOCK_HALVES; }
+			if (ib < 0) { ib = p.n_b++; p.b_key[ib] = kb; p.b_off[ib] = ly.b_img + tl.n * mlp_image::BLOCK_HALVES; }
+			p.ta[t] = ia; p.tb[t] = ib;
+		}
+		return p;
+	}
+	static constexpr int reads(int w) { return plan(w).n_a + plan(w).n_b; }
+	static constexpr int total_reads() { return reads(0) + reads(1) + reads(2) + reads(3); }
+	// every tile of every layer is held by exactly one wave
+	static constexpr bool covers() {
+		for (int i = 0; i < NL; ++i)
+			for (int m = 0; m < layer(i).mt; ++m)
+				for (int n = 0; n < layer(i).nt; ++n) {
+					int c = 0;
+					for (int w = 0; w < 4; ++w)
+						for (int t = 0; t < N_DW; ++t) {
+							const Tile tl = tile(w, t);
+							c += tl.layer == i && tl.m == m && tl.n == n;
+						}
+					if (c != 1) return false;
+				}
+		return true;
+	}
+	static_assert(covers(), "the waves' dW tiles partition the layers' tiles");
+};
+// the seven networks dispatch_nerf lists: no wave holds more tiles than with one strip of every layer per wave
+static_assert(TrainTiles<1, 1, 1>::N_DW == 5 && TrainTiles<1, 2, 2>::N_DW == 13 && TrainTiles<1, 1, 3>::N_DW == 13 &&
+              TrainTiles<2, 1, 3>::N_DW == 14 && TrainTiles<2, 2, 2>::N_DW == 14, "a quarter of the tiles per wave");
+static_assert(TrainTiles<1, 1, 2>::N_DW == 9 && TrainTiles<1, 1, 2>::total_reads() == 36, "C2: 36 fragment reads per image");
+static_assert(TrainTiles<2, 1, 2>::N_DW == 10 && TrainTiles<2, 1, 2>::total_reads() == 38 && TrainTiles<2, 1, 2>::reads(2) == 12,
+              "C2': 38 fragment reads per image, at most 12 in one wave");
+
+// Phase B of wave W: its dW tiles (TrainTiles) over the block's four images, between the two barriers of an
+// iteration. The operands of image w + 1 are requested before image w's MFMAs (two operand sets live), which
+// keeps LDS reads in flight under the MFMAs (at most 12 fragments = 24 reads per image and wave; lgkmcnt counts
+// 15). Each tile sums the images in the order 0..3.
+template <int ES, int DH, int RH, int W>
+__device__ __forceinline__ void train_phase_b_wave(f32x4* dw, const f16* img_all, int lane) {
+	using T = NerfTrainLayout<ES, DH, RH>;
+	using TT = TrainTiles<ES, DH, RH>;
+	constexpr typename TT::Plan P = TT::plan(W);
+	const f16* base = img_all + mlp_image::frag_offset(lane, 0, 0);
+	f16x8 fa[2][P.n_a], fb[2][P.n_b];
 #pragma unroll
-	for (int w = 0; w < 4; ++w) {
-		if (!DB) load_ops(w, ops[0]);
-		else if (w < 3) load_ops(w + 1, ops[(w + 1) & (DB ? 1 : 0)]);
-		const PhaseBOps<ES, DH, RH>& o = ops[w & (DB ? 1 : 0)];
-		dw[T::W_RO] = mfma16(o.ro_a, o.ro_b, dw[T::W_RO]);
+	for (int w = -1; w < 4; ++w) {
+		// the order "all of the next image's reads, then this image's MFMAs" is pinned: left to the scheduler, reads
+		// and MFMAs are interleaved with a short lgkmcnt wait before most MFMAs, each exposing LDS latency
+		__builtin_amdgcn_sched_barrier(0);
+		if (w < 3) {
+			// one address register per image: left to the compiler, every fragment further than the 64-KB
+			// offset field of a DS instruction from the block's base gets a loop-invariant register of its own
+			int im_off = (w + 1) * T::IMG_HALVES;
+			asm volatile("" : "+v"(im_off));
+			const f16* im = base + im_off;
 #pragma unroll
-		for (int j = 0; j < RH - 1; ++j)
+			for (int i = 0; i < P.n_a; ++i) fa[(w + 1) & 1][i] = img_frag_at(im + P.a_off[i]);
 #pragma unroll
-			for (int n = 0; n < 4; ++n) dw[T::W_RH + 4 * j + n] = mfma16(o.rh_a[j], o.rh_b[j][n], dw[T::W_RH + 4 * j + n]);
+			for (int i = 0; i < P.n_b; ++i) fb[(w + 1) & 1][i] = img_frag_at(im + P.b_off[i]);
+		}
+		__builtin_amdgcn_sched_barrier(0);
+		if (w >= 0) {
 #pragma unroll
-		for (int n = 0; n < 2; ++n) dw[T::W_R0 + n] = mfma16(o.r0_a, o.r0_b[n], dw[T::W_R0 + n]);
-		dw[T::W_DO] = mfma16(o.do_a, o.do_b, dw[T::W_DO]);
-#pragma unroll
-		for (int j = 0; j < DH - 1; ++j)
-#pragma unroll
-			for (int n = 0; n < 4; ++n) dw[T::W_DH + 4 * j + n] = mfma16(o.dh_a[j], o.dh_b[j][n], dw[T::W_DH + 4 * j + n]);
-#pragma unroll
-		for (int n = 0; n < ES; ++n) dw[T::W_D0 + n] = mfma16(o.d0_a, o.d0_b[n], dw[T::W_D0 + n]);
+			for (int t = 0; t < TT::N_DW; ++t) dw[t] = mfma16(fa[w & 1][P.ta[t]], fb[w & 1][P.tb[t]], dw[t]);
+		}
 	}
 }
 
-// this wave's dW tiles -> the block's slab (parameter-slice layout; the waves' tiles are disjoint)
+template <int ES, int DH, int RH>
+__device__ __forceinline__ void train_phase_b(f32x4* dw, const f16* img_all, int wave, int lane) {
+	switch (wave) {  // wave-uniform (an SGPR): the transposed reads need every lane active
+		case 0: train_phase_b_wave<ES, DH, RH, 0>(dw, img_all, lane); break;
+		case 1: train_phase_b_wave<ES, DH, RH, 1>(dw, img_all, lane); break;
+		case 2: train_phase_b_wave<ES, DH, RH, 2>(dw, img_all, lane); break;
+		default: train_phase_b_wave<ES, DH, RH, 3>(dw, img_all, lane); break;
+	}
+}
+
+// wave W's dW tiles (16x16, 4 regs: out = 16m + 4(lane>>4) + r, in = 16n + (lane&15)) -> the block's slab at their
+// parameter-slice positions [out x in]; the waves' tiles are disjoint
+template <int ES, int DH, int RH, int W>
+__device__ __forceinline__ void train_store_dw_wave(const f32x4* dw, const NerfMlpArgs& a, int lane) {
+	using TT = TrainTiles<ES, DH, RH>;
+	float* slab = a.dw_slab + (size_t)blockIdx.x * a.n_matrix;
+#pragma unroll
+	for (int t = 0; t < TT::N_DW; ++t) {
+		const typename TT::Tile tl = TT::tile(W, t);
+		const typename TT::Layer ly = TT::layer(tl.layer);
+		const uint32_t woff = (ly.rgb ? a.rgb_woff : a.density_woff) + ly.woff;
+#pragma unroll
+		for (int r = 0; r < 4; ++r) {
+			const uint32_t o = 16 * tl.m + 4 * (lane >> 4) + r, i = 16 * tl.n + (lane & 15);
+			slab[woff + o * ly.in_dim + i] = dw[t][r];
+		}
+	}
+}
+
 template <int ES, int DH, int RH>
 __device__ __forceinline__ void train_store_dw(const f32x4* dw, const NerfMlpArgs& a, int wave, int lane) {
-	using T = NerfTrainLayout<ES, DH, RH>;
-	float* slab = a.dw_slab + (size_t)blockIdx.x * a.n_matrix;
-	const uint32_t dw0 = a.density_woff, rw0 = a.rgb_woff;
-	dw_store<1, 1>(dw + T::W_RO, slab, rw0 + 64 * 32 + 64 * 64 * (RH - 1), 64, 0, wave, lane);
-#pragma unroll
-	for (int j = 0; j < RH - 1; ++j) dw_store<1, 4>(dw + T::W_RH + 4 * j, slab, rw0 + 64 * 32 + 64 * 64 * (RH - 2 - j), 64, wave, 0, lane);
-	dw_store<1, 2>(dw + T::W_R0, slab, rw0, 32, wave, 0, lane);
-	dw_store<1, 1>(dw + T::W_DO, slab, dw0 + 64 * 16 * ES + 64 * 64 * (DH - 1), 64, 0, wave, lane);
-#pragma unroll
-	for (int j = 0; j < DH - 1; ++j) dw_store<1, 4>(dw + T::W_DH + 4 * j, slab, dw0 + 64 * 16 * ES + 64 * 64 * (DH - 2 - j), 64, wave, 0, lane);
-	dw_store<1, ES>(dw + T::W_D0, slab, dw0, 16 * ES, wave, 0, lane);
+	switch (wave) {
+		case 0: train_store_dw_wave<ES, DH, RH, 0>(dw, a, lane); break;
+		case 1: train_store_dw_wave<ES, DH, RH, 1>(dw, a, lane); break;
+		case 2: train_store_dw_wave<ES, DH, RH, 2>(dw, a, lane); break;
+		default: train_store_dw_wave<ES, DH, RH, 3>(dw, a, lane); break;
+	}
 }
 
 // Timing experiments only (-DNGP_TRAIN_CLOCK, DESIGN §6 phase costs; tools/train_clock.py): thread 0 of blocks
 // 0..1023 (wave 0) stamps the 100-MHz wall clock at the phase boundaries: slot 0 entry, 1 weights loaded, then per
 // iteration i slots 2 + 10 i + k for k = 0 inputs taken, 1 density forward, 2 rgb forward (+ output store),
-// 3 images written, 4 rgb backward chain, 5 density backward chain, 6 dL/denc stored, 7 barrier, 8 dW, 9 barrier;
+// 3 barrier (the previous iteration's images are free), 4 images written, 5 rgb backward chain, 6 density backward chain,
+// 7 dL/denc stored, 8 barrier, 9 dW;
 // slot 127 exit. Scheduling barriers keep the phases apart, so the stamped kernel is slower than the plain one.
 #ifdef NGP_TRAIN_CLOCK
 constexpr int TRC_SLOTS = 128;
@@ -938,24 +991,6 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(1, 
 	f16* img_all = (f16*)smem;
 	f16* img = img_all + wave * T::IMG_HALVES;
 
-	// every weight fragment in registers for the whole kernel (loaded once from global)
-	f16x8 wreg[Lay::N_FWD], breg[T::N_BWD];
-#pragma unroll
-	for (int q = 0; q < Lay::N_FWD; ++q) wreg[q] = a.frags[q * 64 + lane];
-#pragma unroll
-	for (int q = 0; q < T::N_BWD; ++q) breg[q] = a.frags[(Lay::N_FWD + q) * 64 + lane];
-	// The fragments live in the accumulator file (AGPRs can be an MFMA's A operand): left to itself the
-	// register allocator parks them there anyway under VGPR pressure and copies them back with one
-	// v_accvgpr_read per register before each use (~100 VALU per tile); pinned, the MFMAs read them in place.
-#pragma unroll
-	for (int q = 0; q < Lay::N_FWD; ++q) asm volatile("" : "+a"(wreg[q]));
-#pragma unroll
-	for (int q = 0; q < T::N_BWD; ++q) asm volatile("" : "+a"(breg[q]));
-	f32x4 dw[T::N_DW];
-#pragma unroll
-	for (int q = 0; q < T::N_DW; ++q) dw[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-	TRC_MARK(1);
-
 	const uint32_t n_tiles = (a.n + 31) / 32;
 	f16x8 xe_n[ES];
 	float cd_n[3];
@@ -969,7 +1004,26 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(1, 
 		cd_n[0] = cd[0]; cd_n[1] = cd[1]; cd_n[2] = cd[2];
 		dl_n = *(const f16x4*)(a.dL_dout + (size_t)ls * a.dL_stride);
 	};
+	// the first tile's inputs are requested ahead of the 40-odd weight fragments, so they arrive under those loads
 	load_inputs(blockIdx.x * 4 + wave);
+	// every weight fragment in registers for the whole kernel (loaded once from global)
+	f16x8 wreg[Lay::N_FWD], breg[T::N_BWD];
+#pragma unroll
+	for (int q = 0; q < Lay::N_FWD; ++q) wreg[q] = a.frags[q * 64 + lane];
+#pragma unroll
+	for (int q = 0; q < T::N_BWD; ++q) breg[q] = a.frags[(Lay::N_FWD + q) * 64 + lane];
+	// The fragments live in the accumulator file (AGPRs can be an MFMA's A operand): left to itself the
+	// register allocator parks them there anyway under VGPR pressure and copies them back with one
+	// v_accvgpr_read per register before each use (~100 VALU per tile); pinned, the MFMAs read them in place.
+#pragma unroll
+	for (int q = 0; q < Lay::N_FWD; ++q) asm volatile("" : "+a"(wreg[q]));
+#pragma unroll
+	for (int q = 0; q < T::N_BWD; ++q) asm volatile("" : "+a"(breg[q]));
+	f32x4 dw[TrainTiles<ES, DH, RH>::N_DW];
+#pragma unroll
+	for (int q = 0; q < TrainTiles<ES, DH, RH>::N_DW; ++q) dw[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+	TRC_MARK(1);
+
 	// every wave runs the same number of iterations (the barriers need all four); tiles past the end
 	// run on zero inputs and zero output gradients, so their dW contribution is exactly zero
 #ifdef NGP_TRAIN_CLOCK
@@ -987,9 +1041,7 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(1, 
 		load_inputs(tile + gridDim.x * 4);  // unconditional (past-the-end tiles read sample 0)
 		TRC_IT(0);
 
-		// ---- phase A: forward ----------------------------------------------------------------
-#pragma unroll
-		for (int s = 0; s < ES; ++s) img_store_std(img + T::I_XE, Lay::S_XE, xe[s], s, lane);
+		// ---- phase A: forward (registers only: runs while other waves still finish phase B) ------
 		f32x16 acc[2];
 		f16x8 hd[DH][4];
 		layer_fwd_reg<2, ES>(acc, xe, wreg, Lay::F_D0);
@@ -1023,16 +1075,22 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(1, 
 			store_out16(a.out, a.out_stride, a.out_layout, a.n, sample, h, ro);
 		}
 		TRC_IT(2);
+		// the previous iteration's phase B has read the images: this barrier frees them. It sits here, not at the
+		// end of the iteration, because nothing above touches LDS.
+		__syncthreads();
+		TRC_IT(3);
 #pragma unroll
-		for (int l = 0; l < DH; ++l) img_store_acc<4>(img + T::I_HD + l * 32 * Lay::S_64, Lay::S_64, hd[l], lane);
+		for (int s = 0; s < ES; ++s) img_store_std(img + T::I_XE, xe[s], s, lane);
+#pragma unroll
+		for (int l = 0; l < DH; ++l) img_store_acc<4>(img + T::I_HD + l * Lay::N_64, hd[l], lane);
 		{
 			f16x8 d1[1] = {dout[0]};
-			img_store_acc<1>(img + T::I_RIN, Lay::S_RIN, d1, lane);
-			img_store_std(img + T::I_RIN, Lay::S_RIN, rin[1], 1, lane);
+			img_store_acc<1>(img + T::I_RIN, d1, lane);
+			img_store_std(img + T::I_RIN, rin[1], 1, lane);
 		}
 #pragma unroll
-		for (int l = 0; l < RH; ++l) img_store_acc<4>(img + T::I_HR + l * 32 * Lay::S_64, Lay::S_64, hr[l], lane);
-		TRC_IT(3);
+		for (int l = 0; l < RH; ++l) img_store_acc<4>(img + T::I_HR + l * Lay::N_64, hr[l], lane);
+		TRC_IT(4);
 
 		// ---- phase A: backward dX chain, every dZ kept in LDS ---------------------------------
 		float dsig;
@@ -1042,35 +1100,35 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(1, 
 			dsig = (float)d[3];
 			dz1[0] = h == 0 ? f16x8{d[0], d[1], d[2], (f16)0.f, 0, 0, 0, 0} : f16x8{};  // extract_rgb (:46-60)
 		}
-		img_store_acc<1>(img + T::I_ZRO, T::S_16, dz1, lane);
+		img_store_acc<1>(img + T::I_ZRO, dz1, lane);
 		f16x8 dz[4];
 		layer_fwd_reg<2, 1>(acc, dz1, breg, Lay::B_RO - Lay::N_FWD);
 		mask_pack<2>(acc, hr[RH - 1], dz);
 #pragma unroll
 		for (int l = RH - 1; l >= 1; --l) {
-			img_store_acc<4>(img + T::I_ZRH + (RH - 1 - l) * 32 * Lay::S_64, Lay::S_64, dz, lane);
+			img_store_acc<4>(img + T::I_ZRH + (RH - 1 - l) * Lay::N_64, dz, lane);
 			layer_fwd_reg<2, 4>(acc, dz, breg, Lay::B_RH - Lay::N_FWD + 8 * (RH - 1 - l));
 			mask_pack<2>(acc, hr[l - 1], dz);
 		}
-		img_store_acc<4>(img + T::I_ZR0, Lay::S_64, dz, lane);
+		img_store_acc<4>(img + T::I_ZR0, dz, lane);
 		f32x16 a1[1];
 		layer_fwd_reg<1, 4>(a1, dz, breg, Lay::B_R0 - Lay::N_FWD);
 		f16x8 dd[1], dsh;
 		pack_tile(a1[0], dd[0], dsh, false);  // dsh: rows 16..31 of dL/d(rgb input) = dL/d(SH encoding)
 		if (h == 0) dd[0][0] = (f16)((float)dd[0][0] + dsig);  // add_density_gradient (:63-74)
 		if (a.dL_dsh && valid) store_dsh(a.dL_dsh, sample, h, dsh);
-		TRC_IT(4);
-		img_store_acc<1>(img + T::I_ZDO, T::S_16, dd, lane);
+		TRC_IT(5);
+		img_store_acc<1>(img + T::I_ZDO, dd, lane);
 		layer_fwd_reg<2, 1>(acc, dd, breg, Lay::B_DO - Lay::N_FWD);
 		mask_pack<2>(acc, hd[DH - 1], dz);
 #pragma unroll
 		for (int l = DH - 1; l >= 1; --l) {
-			img_store_acc<4>(img + T::I_ZDH + (DH - 1 - l) * 32 * Lay::S_64, Lay::S_64, dz, lane);
+			img_store_acc<4>(img + T::I_ZDH + (DH - 1 - l) * Lay::N_64, dz, lane);
 			layer_fwd_reg<2, 4>(acc, dz, breg, Lay::B_DH - Lay::N_FWD + 8 * (DH - 1 - l));
 			mask_pack<2>(acc, hd[l - 1], dz);
 		}
-		img_store_acc<4>(img + T::I_ZD0, Lay::S_64, dz, lane);
-		TRC_IT(5);
+		img_store_acc<4>(img + T::I_ZD0, dz, lane);
+		TRC_IT(6);
 		if (a.dL_denc) {
 			f32x16 ae[Lay::ET];
 			layer_fwd_reg<Lay::ET, 4>(ae, dz, breg, Lay::B_D0 - Lay::N_FWD);
@@ -1088,14 +1146,12 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(1, 
 				}
 			}
 		}
-		TRC_IT(6);
-		__syncthreads();
 		TRC_IT(7);
+		__syncthreads();
+		TRC_IT(8);
 
 		// ---- phase B: this wave's quarter of dW over the four images ---------------------------
 		train_phase_b<ES, DH, RH>(dw, img_all, wave, lane);
-		TRC_IT(8);
-		__syncthreads();
 		TRC_IT(9);
 #ifdef NGP_TRAIN_CLOCK
 		++trc_it;
@@ -1199,12 +1255,12 @@ struct MlpLayout {
 	static constexpr int B_0 = B_H + HT * HS * (NH - 1);
 	static constexpr int ET = (ES + 1) / 2;
 	static constexpr int N_ALL = B_0 + ET * HS;
-	static constexpr int S_XE = 16 * ES + 4;
-	static constexpr int S_W = WD + 4;
+	static constexpr int N_XE = mlp_image::image_halves(16 * ES);
+	static constexpr int N_W = mlp_image::image_halves(WD);
 	static constexpr int I_XE = 0;
-	static constexpr int I_H = I_XE + 32 * S_XE;
-	static constexpr int I_DZ = I_H + NH * 32 * S_W;
-	static constexpr int IMG_HALVES = I_DZ + 32 * S_W;
+	static constexpr int I_H = I_XE + N_XE;
+	static constexpr int I_DZ = I_H + NH * N_W;
+	static constexpr int IMG_HALVES = I_DZ + N_W;
 	static constexpr int W_O = 0;
 	static constexpr int W_H = HS;
 	static constexpr int W_0 = W_H + HS * HS * (NH - 1);
@@ -1238,7 +1294,7 @@ __global__ void __launch_bounds__(256, 1) k_mlp(const MlpArgs a) {
 		for (int s = 0; s < ES; ++s) {
 			xe[s] = *(const f16x8*)(a.enc + (size_t)ls * a.enc_stride + 16 * s + 8 * h);
 			if (!valid) xe[s] = f16x8{};
-			if constexpr (TRAIN) img_store_std(img + Lay::I_XE, Lay::S_XE, xe[s], s, lane);
+			if constexpr (TRAIN) img_store_std(img + Lay::I_XE, xe[s], s, lane);
 		}
 		f32x16 acc[HT];
 		f16x8 hh[NH][2 * HT];
@@ -1258,7 +1314,7 @@ __global__ void __launch_bounds__(256, 1) k_mlp(const MlpArgs a) {
 		}
 		if constexpr (TRAIN) {
 #pragma unroll
-			for (int l = 0; l < NH; ++l) img_store_acc<HS>(img + Lay::I_H + l * 32 * Lay::S_W, Lay::S_W, hh[l], lane);
+			for (int l = 0; l < NH; ++l) img_store_acc<HS>(img + Lay::I_H + l * Lay::N_W, hh[l], lane);
 			f16* dz_img = img + Lay::I_DZ;
 			f16x8 dzo[1];
 			{
@@ -1271,20 +1327,20 @@ __global__ void __launch_bounds__(256, 1) k_mlp(const MlpArgs a) {
 				}
 				dzo[0] = d;
 			}
-			img_store_acc<1>(dz_img, Lay::S_W, dzo, lane);
-			dw_accum<1, HS>(dw + Lay::W_O, dz_img, Lay::S_W, img + Lay::I_H + (NH - 1) * 32 * Lay::S_W, Lay::S_W, lane);
+			img_store_acc<1>(dz_img, dzo, lane);
+			dw_accum<1, HS>(dw + Lay::W_O, dz_img, img + Lay::I_H + (NH - 1) * Lay::N_W, lane);
 			f16x8 dz[2 * HT];
 			layer_fwd<HT, 1>(acc, dzo, lfrag + Lay::B_O * 64, lane);
 			mask_pack<HT>(acc, hh[NH - 1], dz);
 #pragma unroll
 			for (int l = NH - 1; l >= 1; --l) {
-				img_store_acc<HS>(dz_img, Lay::S_W, dz, lane);
-				dw_accum<HS, HS>(dw + Lay::W_H + HS * HS * (NH - 1 - l), dz_img, Lay::S_W, img + Lay::I_H + (l - 1) * 32 * Lay::S_W, Lay::S_W, lane);
+				img_store_acc<HS>(dz_img, dz, lane);
+				dw_accum<HS, HS>(dw + Lay::W_H + HS * HS * (NH - 1 - l), dz_img, img + Lay::I_H + (l - 1) * Lay::N_W, lane);
 				layer_fwd<HT, HS>(acc, dz, lfrag + (Lay::B_H + HT * HS * (NH - 1 - l)) * 64, lane);
 				mask_pack<HT>(acc, hh[l - 1], dz);
 			}
-			img_store_acc<HS>(dz_img, Lay::S_W, dz, lane);
-			dw_accum<HS, ES>(dw + Lay::W_0, dz_img, Lay::S_W, img + Lay::I_XE, Lay::S_XE, lane);
+			img_store_acc<HS>(dz_img, dz, lane);
+			dw_accum<HS, ES>(dw + Lay::W_0, dz_img, img + Lay::I_XE, lane);
 			if (a.dL_denc) {
 				f32x16 ae[Lay::ET];
 				layer_fwd<Lay::ET, HS>(ae, dz, lfrag + Lay::B_0 * 64, lane);

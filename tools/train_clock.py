@@ -16,8 +16,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-PHASES = ["inputs", "density_fwd", "rgb_fwd_out", "images", "bwd_rgb", "bwd_density", "denc_store", "barrier1", "dW",
-          "barrier2"]
+PHASES = ["inputs", "density_fwd", "rgb_fwd_out", "barrier2", "images", "bwd_rgb", "bwd_density", "denc_store",
+          "barrier1", "dW"]
 
 
 def main():
