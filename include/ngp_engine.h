@@ -753,9 +753,10 @@ int ngp_nerf_trainer_get_camera_training(const ngp_nerf_trainer* t, ngp_nerf_cam
  * are zero. */
 int ngp_nerf_trainer_camera_extrinsics(const ngp_nerf_trainer* t, uint32_t i, float* out);
 /* set_camera_extrinsics (:2896-2919) with an NGP-space transform: replaces image i's transform in this trainer (the
- * dataset is not modified) and resets that image's optimiser state. Discards a prelaunched sampler. */
+ * dataset is not modified) and resets that image's optimiser state, its exposure optimiser included (:2911-2913).
+ * Discards a prelaunched sampler. */
 int ngp_nerf_trainer_set_camera_extrinsics(ngp_nerf_trainer* t, uint32_t i, const float* xform);
-/* reset_camera_extrinsics (:2921-2933): every camera's optimiser state to zero, cameras rebuilt. */
+/* reset_camera_extrinsics (:2921-2933): every camera's optimiser state to zero (pose and exposure), cameras rebuilt. */
 int ngp_nerf_trainer_reset_camera_extrinsics(ngp_nerf_trainer* t);
 /* Engine extension (inspection): the last step's sampler call on a single-GPU trainer: its rng, ray count and sample
  * budget (the arguments ngp_nerf_generate_training_samples would take, with the trainer's bitfield) and the device
@@ -884,10 +885,66 @@ int ngp_nerf_compute_loss_depth(const ngp_nerf_dataset* ds, const ngp_nerf_confi
 /* Training::depth_supervision_lambda (default 0: off) and depth_loss_type (ELossType, default L1) of the trainer's
  * steps (testbed.h:719, 745). Only the loss pass reads them: nothing is discarded, and with lambda 0 or a dataset
  * without depth the step issues exactly the launches it would have. Works with the error-map CDFs, an environment
- * map, optimize_extrinsics and data-parallel training (the term is per ray). Exposure, sharpness and replacing an
- * image's colours after creation stay unimplemented. */
+ * map, optimize_extrinsics and data-parallel training (the term is per ray). Sharpness and replacing an image's
+ * colours after creation stay unimplemented. */
 int ngp_nerf_trainer_set_depth_supervision(ngp_nerf_trainer* t, float lambda, uint32_t loss_type);
 int ngp_nerf_trainer_get_depth_supervision(const ngp_nerf_trainer* t, float* lambda, uint32_t* loss_type);
+
+/* ---- per-image exposure (Training::optimize_exposure, exposure_l2_reg; cam_exposure) ---------------------------- */
+/* ngp_nerf_compute_loss_depth with per-image exposures (testbed_nerf.cu:1794-1818, 1973-1986). exposure (DEVICE,
+ * [n_images x 3] log2 exposures; NULL: none): the target's premultiplied linear texel is multiplied by 2^exposure per
+ * channel, in both colour-space branches; nothing else changes. exposure_gradient (DEVICE, [n_images x 3], nullable,
+ * ADDED ONTO): for every ray that compacts to at least one sample, also one cut short by the budget,
+ *   loss_scale / n_rays * (-dL/dprediction / uv_pdf [/ srgb_to_linear_derivative(target)]) * 2^exposure * ln 2
+ * summed per image without atomics: the same bytes from run to run, and a second call onto the first's output gives
+ * exactly twice it; an image without such a ray keeps its values. This is the reference's expression, which leaves out
+ * the texel's own value (d target / d exposure = ln 2 * 2^exposure * texel). The per-image sum relies on image_idx
+ * being monotone in the ray id: a gradient with cdfs->cdf_img set is NGP_INVALID, and so is one without exposures.
+ * With exposure NULL this is ngp_nerf_compute_loss_depth, bit for bit, and launches the same kernels; an all-zero
+ * exposure array gives the same bits too. */
+int ngp_nerf_compute_loss_exposure(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
+                                   uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples_compacted,
+                                   const uint32_t* ray_counter, const void* network_output, const uint32_t* ray_indices,
+                                   const float* rays, uint32_t* numsteps, const float* coords_in, float* coords_out,
+                                   void* dloss_doutput, float* loss, uint32_t* compacted_counter, const float* mean_density,
+                                   float loss_scale, float* error_map, uint32_t em_width, uint32_t em_height,
+                                   const ngp_nerf_error_cdfs* cdfs, const float* envmap, uint32_t env_width,
+                                   uint32_t env_height, uint32_t envmap_loss_type, float* envmap_gradient, float* sample_state,
+                                   uint64_t state_capacity, float depth_supervision_lambda, uint32_t depth_loss_type,
+                                   const float* exposure, float* exposure_gradient);
+/* The per-image exposure optimisers (Training::cam_exposure: AdamOptimizer<vec3>, adam_optimizer.h:128-209): n_images
+ * Adam states, beta1 0.9, beta2 0.99, epsilon 1e-8, initial learning rate 1e-3, which every step overwrites. Host
+ * only: no GPU call. */
+typedef struct ngp_exposure_optimizer ngp_exposure_optimizer;
+int ngp_exposure_optimizer_create(uint32_t n_images, ngp_exposure_optimizer** out);
+void ngp_exposure_optimizer_destroy(ngp_exposure_optimizer* o);
+uint32_t ngp_exposure_optimizer_n_images(const ngp_exposure_optimizer* o);
+int ngp_exposure_optimizer_reset(ngp_exposure_optimizer* o);
+int ngp_exposure_optimizer_reset_one(ngp_exposure_optimizer* o, uint32_t i);
+/* One update of every image (testbed_nerf.cu:3831-3858) from the accumulated gradients (host float [n_images x 3]):
+ * gradient * n_images / 128 / n_steps_between + l2_reg * variable, an Adam step with learning rate network_lr, then
+ * the mean of all variables (summed in image order, divided by n_images) subtracted from each. */
+int ngp_exposure_optimizer_step(ngp_exposure_optimizer* o, const float* grad, uint32_t n_steps_between, float l2_reg,
+                                float network_lr);
+int ngp_exposure_optimizer_get(const ngp_exposure_optimizer* o, uint32_t i, ngp_adam_state* out);
+int ngp_exposure_optimizer_set_state(ngp_exposure_optimizer* o, uint32_t i, const ngp_adam_state* state);
+/* Training::optimize_exposure (default 0) and exposure_l2_reg (default 0) (testbed.h:716-785, python_api.cu:620, 634).
+ * With the switch on, every step's loss pass scales the targets by the images' exposures and sums the exposure
+ * gradient per image; every n_steps_between_cam_updates steps (the counter is shared with optimize_extrinsics) the
+ * sums come back, the optimisers step with the network optimiser's learning rate, the mean is removed and the new
+ * exposures are uploaded. Nothing the sampler reads changes: a prelaunched sampler stays. Exposures that are not zero
+ * (after a snapshot or ngp_nerf_trainer_set_camera_exposure) scale the targets with the switch off too; with all of
+ * them zero and the switch off the step issues exactly the launches it would without this call.
+ * sample_focal_plane_proportional_to_error is allowed (the gradient is divided by uv_pdf);
+ * sample_image_proportional_to_error is not (either call fails, state unchanged), and neither is a data-parallel
+ * exchange hook. A negative or non-finite l2_reg: NGP_INVALID. */
+int ngp_nerf_trainer_set_exposure_training(ngp_nerf_trainer* t, int optimize_exposure, float exposure_l2_reg);
+int ngp_nerf_trainer_get_exposure_training(const ngp_nerf_trainer* t, int* optimize_exposure, float* exposure_l2_reg);
+/* cam_exposure[i].variable(): image i's log2 exposure per channel, float[3]. */
+int ngp_nerf_trainer_camera_exposure(const ngp_nerf_trainer* t, uint32_t i, float* out);
+/* Engine extension: sets image i's exposure and resets that image's moments and iteration count. */
+int ngp_nerf_trainer_set_camera_exposure(ngp_nerf_trainer* t, uint32_t i, const float* rgb);
+int ngp_nerf_trainer_exposure_optimizer_state(const ngp_nerf_trainer* t, uint32_t i, ngp_adam_state* out);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

@@ -293,6 +293,22 @@ SIGNATURES = {
     "ngp_nerf_compute_loss_depth": (i32, [P, C.POINTER(NerfConfig), P, u32, u32, Rng, u32, P, P, P, P, P, P, P, P, P, P,
                                           P, f32, P, u32, u32, C.POINTER(NerfErrorCdfs), P, u32, u32, u32, P, P, u64, f32,
                                           u32]),
+    "ngp_nerf_compute_loss_exposure": (i32, [P, C.POINTER(NerfConfig), P, u32, u32, Rng, u32, P, P, P, P, P, P, P, P, P, P,
+                                             P, f32, P, u32, u32, C.POINTER(NerfErrorCdfs), P, u32, u32, u32, P, P, u64, f32,
+                                             u32, P, P]),
+    "ngp_exposure_optimizer_create": (i32, [u32, C.POINTER(P)]),
+    "ngp_exposure_optimizer_destroy": (None, [P]),
+    "ngp_exposure_optimizer_n_images": (u32, [P]),
+    "ngp_exposure_optimizer_reset": (i32, [P]),
+    "ngp_exposure_optimizer_reset_one": (i32, [P, u32]),
+    "ngp_exposure_optimizer_step": (i32, [P, P, u32, f32, f32]),
+    "ngp_exposure_optimizer_get": (i32, [P, u32, C.POINTER(AdamState)]),
+    "ngp_exposure_optimizer_set_state": (i32, [P, u32, C.POINTER(AdamState)]),
+    "ngp_nerf_trainer_set_exposure_training": (i32, [P, C.c_int, f32]),
+    "ngp_nerf_trainer_get_exposure_training": (i32, [P, C.POINTER(C.c_int), C.POINTER(f32)]),
+    "ngp_nerf_trainer_camera_exposure": (i32, [P, u32, P]),
+    "ngp_nerf_trainer_set_camera_exposure": (i32, [P, u32, P]),
+    "ngp_nerf_trainer_exposure_optimizer_state": (i32, [P, u32, C.POINTER(AdamState)]),
     "ngp_nerf_trainer_set_depth_supervision": (i32, [P, f32, u32]),
     "ngp_nerf_trainer_get_depth_supervision": (i32, [P, C.POINTER(f32), C.POINTER(u32)]),
 }

@@ -134,7 +134,30 @@ struct LossArgs {
 	// the depth prefix through the sample ([6][state_cap]). Otherwise nothing of this is read.
 	float depth_lambda;
 	uint32_t depth_loss_type;
+	// per-image exposure (testbed_nerf.cu:1794-1818, 1973-1986): exposure [n_images x 3] log2 exposures,
+	// the target's premultiplied linear texel is scaled by 2^exposure per channel; null: off, and the kernels'
+	// instantiations without it run. exposure_ray_grad (optional, [n_rays x 3]): pass 1 stores every kept ray's
+	// dloss_by_dexposure there, and exposure_gradients (below) sums per image those of the rays that compact to at least
+	// one sample; null: the scale is applied but no gradient is taken.
+	const float* exposure;
+	float* exposure_ray_grad;
 };
+
+// The per-image sum of the loss pass's per-ray exposure gradients, without atomics, by k_cam_image_sum's method
+// (nerf_camera.h): image_idx is monotone in the ray id under a uniform image choice, so an image's kept rays are one
+// contiguous run, found by two binary searches on ray_indices; one block per image adds, in a fixed tree, the rows of
+// the rays whose compacted sample count (numsteps[2 r] after the loss pass) is not zero, and one thread per channel adds
+// the sum onto image_grad. An image without such rays keeps its accumulator as it is.
+struct ExposureGradArgs {
+	uint32_t n_rays_cap;        // rows of ray_grad: an upper bound of *ray_counter known on the host
+	uint32_t n_rays_total, n_images;
+	const uint32_t* ray_counter;
+	const uint32_t* ray_indices;
+	const uint32_t* numsteps;   // [R x 2] after the loss pass: {compacted numsteps, compacted base}
+	const float* ray_grad;      // [n_rays_cap x 3] LossArgs::exposure_ray_grad
+	float* image_grad;          // [n_images x 3], accumulated
+};
+void exposure_gradients(const ExposureGradArgs& a, hipStream_t s);
 
 // The environment map's stand-alone forms (envmap.hip): dirs [n x 3] normalized; texels, weights [n x 4] as
 // envmap_lookup returns them; values [n x 3] fp16 rgb gradients added into acc (envmap_acc_words64 words, zeroed by
@@ -204,6 +227,8 @@ size_t loss_tmp_f32(uint32_t n_rays);    // floats of compute_loss' tmp_f32 (per
 // whether compute_loss runs its depth instantiations, and the floats of tmp_f32 they need (one more per ray)
 bool loss_depth_on(const Dataset& ds, const LossArgs& a);
 size_t loss_tmp_f32_depth(uint32_t n_rays);
+// the floats of the per-ray exposure gradients, which a caller may keep behind those (LossArgs::exposure_ray_grad)
+size_t loss_tmp_f32_exposure(uint32_t n_rays);
 // construct_cdf_2d / construct_cdf_1d (testbed_nerf.cu:2356-2410) over the error map
 void error_map_cdfs(uint32_t n_images, uint32_t w, uint32_t h, const float* data, float* cdf_x_cond_y, float* cdf_y,
                     float* cdf_img, hipStream_t s);

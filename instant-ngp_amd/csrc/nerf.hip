@@ -1116,8 +1116,9 @@ void sample_rays(const Dataset& ds, const ngp_nerf_config& cfg, const SampleArgs
 // around a prefix scan. The error map deposit (:1869-1899, always on in the reference's training) is
 // done in pass 2 after the compaction early-out, as there, and so is the environment map's gradient
 // deposit (:1988-2011; envmap.h), and depth supervision (:1725-1748, 1848-1856, 1912-1956;
-// DESIGN.md §8e) is the kernels' DEPTH instantiation; sharpness / exposure are off in the reference's default
-// training and not implemented.
+// DESIGN.md §8e) is the kernels' DEPTH instantiation, and the per-image exposure (:1794-1818, 1973-1986)
+// pass 1's EXPO instantiation, whose per-ray gradients exposure_gradients sums per image; sharpness is off in the
+// reference's default training and not implemented.
 // A ray owns one DPP row: lanes load and activate 16 samples at once (network output, dt, exp), and
 // the compositing recurrence (T *= 1 - alpha, rgb += alpha T c) runs over the row in sample order
 // with row_newbcast broadcasts, i.e. with the reference's float ops in the reference's order.
@@ -1149,7 +1150,9 @@ __device__ __forceinline__ float sample_depth(const float* c, const Aabb& b, flo
 // ENV: an environment map is bound (LossArgs::envmap): a separate instantiation, as CDF is
 // DEPTH: depth supervision is on (loss_depth_on): the lanes also load their sample's position, and the row recurrence
 // carries depth_ray += weight * distance(pos, ray_o) under rgb's stop rule; the ray's sum goes to depth_ray[i]
-template <bool CDF, bool ENV, bool DEPTH>
+// EXPO: per-image exposures are bound (LossArgs::exposure): lane ch scales the texel by 2^exposure[img][ch] and, with
+// exposure_ray_grad bound, stores the ray's dloss_by_dexposure[ch]
+template <bool CDF, bool ENV, bool DEPTH, bool EXPO>
 __global__ void __launch_bounds__(256) k_loss_pass1(const Camera* __restrict__ cams, const uint32_t* __restrict__ pixels,
                                                     uint32_t n_images, const ngp_nerf_config cfg, LossArgs a,
                                                     uint32_t* __restrict__ craw, LossRay* __restrict__ lr,
@@ -1322,7 +1325,7 @@ __global__ void __launch_bounds__(256) k_loss_pass1(const Camera* __restrict__ c
 		const float ec = envmap_mix(tap, e0[ch], e1[ch], e2[ch], e3[ch]), ea = envmap_mix(tap, e0[3], e1[3], e2[3], e3[3]);
 		bgc = ec + bgc * (1.0f - ea);
 	}
-	const float exposure_scale = expf(0.6931471805599453f * 0.0f);
+	const float exposure_scale = expf(0.6931471805599453f * (EXPO ? a.exposure[3 * (size_t)img + ch] : 0.0f));
 	float target;
 	if (cfg.linear_colors || cfg.color_space_linear) {
 		target = exposure_scale * texc + (1.0f - tex3) * bgc;
@@ -1340,6 +1343,16 @@ __global__ void __launch_bounds__(256) k_loss_pass1(const Camera* __restrict__ c
 	// loss estimate unbiased, the same optimisation with less variance; importance sampling is meant to change the
 	// weighting of the loss instead.
 	if (CDF) lc = lc / (px.img_pdf * px.uv_pdf);
+	// dloss_by_dexposure of channel ch (testbed_nerf.cu:1973-1986): -gradient / uv_pdf, through the sRGB curve at the
+	// target when not training in linear colours, times loss_scale * 2^exposure * ln 2. It lacks the texel's own value
+	// (d target / d exposure = ln 2 * 2^exposure * texel), as there. Which rays count is decided after the compaction
+	// (exposure_gradients).
+	if (EXPO && a.exposure_ray_grad && L < 3) {
+		float dgt = -gc;
+		if (CDF) dgt = dgt / px.uv_pdf;
+		if (!cfg.linear_colors) dgt = dgt / srgb_to_linear_derivative(target);
+		a.exposure_ray_grad[3 * (size_t)i + L] = (a.loss_scale / (float)a.n_rays) * dgt * exposure_scale * 0.6931471805599453f;
+	}
 	const float l1 = row_bcast<1>(lc), l2 = row_bcast<2>(lc), g1 = row_bcast<1>(gc), g2 = row_bcast<2>(gc);
 	const float p1 = row_bcast<1>(pred), p2 = row_bcast<2>(pred);
 	// dL/d(envmap) of channel ch (testbed_nerf.cu:1988-2002): the map's own loss where it differs, times the
@@ -1592,6 +1605,7 @@ __global__ void __launch_bounds__(256) k_loss_pass2(const Camera* __restrict__ c
 size_t loss_tmp_f32(uint32_t n_rays) { return (size_t)n_rays * (sizeof(LossRay) / 4); }
 // depth_ray, one float per ray after the LossRay array: LossRay and the default path's scratch keep their size
 size_t loss_tmp_f32_depth(uint32_t n_rays) { return loss_tmp_f32(n_rays) + n_rays; }
+size_t loss_tmp_f32_exposure(uint32_t n_rays) { return (size_t)n_rays * 3; }
 bool loss_depth_on(const Dataset& ds, const LossArgs& a) { return a.depth_lambda > 0.0f && ds.n_depth > 0 && ds.d_depth != nullptr; }
 
 void compute_loss(const Dataset& ds, const ngp_nerf_config& cfg, const LossArgs& a, uint32_t* tmp, float* tmpf, hipStream_t s) {
@@ -1611,13 +1625,22 @@ void compute_loss(const Dataset& ds, const ngp_nerf_config& cfg, const LossArgs&
 		const uint32_t b1 = NGP_LOSS_XCD ? 8 * div_round_up(a.n_rays, 128) : blocks;
 		NGP_CHECK(!a.envmap || (a.env_w > 0 && a.env_h > 0 && a.rays), "compute_loss: environment map without a resolution or rays");
 		NGP_CHECK(!a.env_acc || a.envmap, "compute_loss: an environment map gradient needs the map");
-		auto pass1 = a.envmap ? (a.cdfs.any() ? k_loss_pass1<true, true, false> : k_loss_pass1<false, true, false>)
-		                      : (a.cdfs.any() ? k_loss_pass1<true, false, false> : k_loss_pass1<false, false, false>);
+		NGP_CHECK(!a.exposure_ray_grad || a.exposure, "compute_loss: an exposure gradient needs the exposures");
+		auto pass1 = a.envmap ? (a.cdfs.any() ? k_loss_pass1<true, true, false, false> : k_loss_pass1<false, true, false, false>)
+		                      : (a.cdfs.any() ? k_loss_pass1<true, false, false, false> : k_loss_pass1<false, false, false, false>);
 		if (depth_on) {
 			NGP_CHECK(a.rays, "compute_loss: depth supervision needs the rays");
 			NGP_CHECK(a.depth_loss_type <= LOSS_RELL2, "compute_loss: unknown depth loss");
-			pass1 = a.envmap ? (a.cdfs.any() ? k_loss_pass1<true, true, true> : k_loss_pass1<false, true, true>)
-			                 : (a.cdfs.any() ? k_loss_pass1<true, false, true> : k_loss_pass1<false, false, true>);
+			pass1 = a.envmap ? (a.cdfs.any() ? k_loss_pass1<true, true, true, false> : k_loss_pass1<false, true, true, false>)
+			                 : (a.cdfs.any() ? k_loss_pass1<true, false, true, false> : k_loss_pass1<false, false, true, false>);
+		}
+		if (a.exposure) {  // the exposure forms of the same eight
+			if (depth_on)
+				pass1 = a.envmap ? (a.cdfs.any() ? k_loss_pass1<true, true, true, true> : k_loss_pass1<false, true, true, true>)
+				                 : (a.cdfs.any() ? k_loss_pass1<true, false, true, true> : k_loss_pass1<false, false, true, true>);
+			else
+				pass1 = a.envmap ? (a.cdfs.any() ? k_loss_pass1<true, true, false, true> : k_loss_pass1<false, true, false, true>)
+				                 : (a.cdfs.any() ? k_loss_pass1<true, false, false, true> : k_loss_pass1<false, false, false, true>);
 		}
 		pass1<<<b1, 256, 0, s>>>(ds.d_cams, ds.d_pixels, ds.n_images, cfg, a, craw, lr, depth_ray);
 		NGP_HIP(hipGetLastError());

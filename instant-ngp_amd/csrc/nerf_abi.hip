@@ -18,7 +18,8 @@ int run_sampler(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* st
 	});
 }
 
-int run_compute_loss(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, LossArgs a) {
+int run_compute_loss(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, LossArgs a, bool exposure_grad,
+                     const float** exposure_ray_grad) {
 	if (!ds || !cfg || !a.ray_counter || !a.network_output || !a.numsteps || !a.coords_in || !a.coords_out || !a.dloss_doutput ||
 	    !a.compacted_counter || !a.mean_density)
 		return NGP_INVALID;
@@ -26,11 +27,18 @@ int run_compute_loss(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, voi
 		if (!a.n_rays_total_for_image_idx) a.n_rays_total_for_image_idx = a.n_rays;
 		if (!a.state) a.state_cap = 0;
 		if (!a.envmap) a.env_acc = nullptr;
+		if (exposure_ray_grad) *exposure_ray_grad = nullptr;
+		NGP_CHECK(!exposure_grad || (a.exposure && a.ray_indices), "compute_loss: an exposure gradient needs the exposures and the ray indices");
 		NGP_CHECK(a.n_rays > 0 || !a.pub_host, "compute_loss: the counters are published by the scan, which needs rays");
 		if (a.n_rays == 0) { NGP_HIP(hipMemsetAsync(a.compacted_counter, 0, 4, S(stream))); return NGP_OK; }
 		static thread_local Buf tmp, tmpf;
 		const size_t nf = loss_depth_on(ds->ds, a) ? loss_tmp_f32_depth(a.n_rays) : loss_tmp_f32(a.n_rays);
-		compute_loss(ds->ds, *cfg, a, tmp.get<uint32_t>(2 * (size_t)a.n_rays), tmpf.get<float>(nf), S(stream));
+		float* f = tmpf.get<float>(nf + (exposure_grad ? loss_tmp_f32_exposure(a.n_rays) : 0));
+		if (exposure_grad) {  // the rays' exposure gradients behind the per-ray scratch, as depth_ray is
+			a.exposure_ray_grad = f + nf;
+			if (exposure_ray_grad) *exposure_ray_grad = a.exposure_ray_grad;
+		}
+		compute_loss(ds->ds, *cfg, a, tmp.get<uint32_t>(2 * (size_t)a.n_rays), f, S(stream));
 	});
 }
 
@@ -289,12 +297,35 @@ int ngp_nerf_compute_loss_depth(const ngp_nerf_dataset* ds, const ngp_nerf_confi
                                 uint32_t env_width, uint32_t env_height, uint32_t envmap_loss_type, float* envmap_gradient,
                                 float* sample_state, uint64_t state_capacity, float depth_supervision_lambda,
                                 uint32_t depth_loss_type) {
+	// the same call without exposures: one set of checks and one setup for both
+	return ngp_nerf_compute_loss_exposure(ds, cfg, stream, n_rays, n_rays_total, rng, max_samples_compacted, ray_counter, network_output,
+	                                      ray_indices, rays, numsteps, coords_in, coords_out, dloss_doutput, loss, compacted_counter,
+	                                      mean_density, loss_scale, error_map, em_width, em_height, cdfs, envmap, env_width, env_height,
+	                                      envmap_loss_type, envmap_gradient, sample_state, state_capacity, depth_supervision_lambda,
+	                                      depth_loss_type, nullptr, nullptr);
+}
+
+int ngp_nerf_compute_loss_exposure(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
+                                   uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples_compacted, const uint32_t* ray_counter,
+                                   const void* network_output, const uint32_t* ray_indices, const float* rays, uint32_t* numsteps,
+                                   const float* coords_in, float* coords_out, void* dloss_doutput, float* loss,
+                                   uint32_t* compacted_counter, const float* mean_density, float loss_scale, float* error_map,
+                                   uint32_t em_width, uint32_t em_height, const ngp_nerf_error_cdfs* cdfs, const float* envmap,
+                                   uint32_t env_width, uint32_t env_height, uint32_t envmap_loss_type, float* envmap_gradient,
+                                   float* sample_state, uint64_t state_capacity, float depth_supervision_lambda,
+                                   uint32_t depth_loss_type, const float* exposure, float* exposure_gradient) {
+	if (!ds) return NGP_INVALID;
 	if (!(depth_supervision_lambda >= 0.0f) || std::isinf(depth_supervision_lambda) || depth_loss_type > LOSS_RELL2) return NGP_INVALID;
 	if (depth_supervision_lambda > 0.0f && !rays) return NGP_INVALID;
 	if (envmap ? (!rays || !envmap_dims_ok(env_width, env_height) || envmap_loss_type > LOSS_RELL2) : envmap_gradient != nullptr)
 		return NGP_INVALID;
 	if (sample_state && state_capacity == 0) return NGP_INVALID;
 	if (error_map && (em_width < 2 || em_height < 2)) return NGP_INVALID;
+	if (exposure && !ray_indices) return NGP_INVALID;
+	// the per-image sum needs the exposures, and an image's rays in one run: no image CDF
+	if (exposure_gradient && (!exposure || (cdfs && cdfs->cdf_img))) return NGP_INVALID;
+	const uint32_t total = n_rays_total ? n_rays_total : n_rays;
+	if (exposure_gradient && (uint64_t)total * ds->ds.n_images > 0xffffffffull) return NGP_INVALID;
 	NERF_TRY({
 		static thread_local Buf acc;
 		LossArgs a = public_loss_args(n_rays, n_rays_total, rng, max_samples_compacted, ray_counter, network_output, ray_indices, rays,
@@ -303,6 +334,7 @@ int ngp_nerf_compute_loss_depth(const ngp_nerf_dataset* ds, const ngp_nerf_confi
 		a.error_map = error_map; a.em_w = em_width; a.em_h = em_height;
 		a.state = sample_state; a.state_cap = state_capacity;
 		a.depth_lambda = depth_supervision_lambda; a.depth_loss_type = depth_loss_type;
+		a.exposure = exposure;
 		if (envmap) {
 			a.envmap = envmap; a.env_w = env_width; a.env_h = env_height; a.env_loss_type = envmap_loss_type;
 			if (envmap_gradient) {
@@ -311,9 +343,17 @@ int ngp_nerf_compute_loss_depth(const ngp_nerf_dataset* ds, const ngp_nerf_confi
 				NGP_HIP(hipMemsetAsync(a.env_acc, 0, words * 8, S(stream)));
 			}
 		}
-		const int rc = run_compute_loss(ds, cfg, stream, a);
+		const float* ray_grad = nullptr;
+		const int rc = run_compute_loss(ds, cfg, stream, a, exposure_gradient != nullptr, &ray_grad);
 		if (rc != NGP_OK) return rc;  // the error string is set
 		if (a.env_acc) envmap_gradient_f32(env_width, env_height, a.env_acc, envmap_gradient, S(stream));
+		if (ray_grad) {
+			ExposureGradArgs g{};
+			g.n_rays_cap = n_rays; g.n_rays_total = total; g.n_images = ds->ds.n_images;
+			g.ray_counter = ray_counter; g.ray_indices = ray_indices; g.numsteps = numsteps;
+			g.ray_grad = ray_grad; g.image_grad = exposure_gradient;
+			exposure_gradients(g, S(stream));
+		}
 	});
 }
 

@@ -1,11 +1,14 @@
 // nerf_camera.hip — camera pose refinement: the per-image gradient kernels with their C-ABI
-// (ngp_nerf_camera_gradients) and the host-only per-camera optimisers (ngp_pose_optimizer_*, ngp_pose_apply).
+// (ngp_nerf_camera_gradients) and the host-only per-camera optimisers (ngp_pose_optimizer_*, ngp_pose_apply); and the
+// per-image exposure's share of the same machinery: the per-image sum of the loss pass's per-ray exposure gradients
+// (exposure_gradients, nerf.h) and the host-only per-image optimisers (ngp_exposure_optimizer_*).
 #include <cmath>
 #include <cstring>
 #include <memory>
 #include <vector>
 
 #include "../../include/ngp_engine.h"
+#include "nerf.h"
 #include "nerf_camera.h"
 
 using namespace ngp;
@@ -109,6 +112,54 @@ void camera_gradients(const CamGradArgs& a, uint32_t lanes, hipStream_t s) {
 	}
 	NGP_HIP(hipGetLastError());
 	k_cam_image_sum<<<a.n_images, CAM_SUM_THREADS, 0, s>>>(a);
+	NGP_HIP(hipGetLastError());
+}
+
+// The exposure gradient per image (nerf.h): k_cam_image_sum's segment search and summation tree over three floats a
+// ray, counting the rays the loss pass compacted to at least one sample
+__global__ void __launch_bounds__(CAM_SUM_THREADS) k_exposure_image_sum(ExposureGradArgs a) {
+	const uint32_t n_kept = min(*a.ray_counter, a.n_rays_cap);
+	const uint32_t img = blockIdx.x;
+	auto lower = [&](uint32_t target) {
+		uint32_t lo = 0, hi = n_kept;
+		while (lo < hi) {
+			const uint32_t mid = lo + (hi - lo) / 2;
+			if (cam_image_idx(a.ray_indices[mid], a.n_rays_total, a.n_images) < target) lo = mid + 1;
+			else hi = mid;
+		}
+		return lo;
+	};
+	const uint32_t lo = lower(img), hi = img + 1 == a.n_images ? n_kept : lower(img + 1);
+	float g[3] = {0.f, 0.f, 0.f};
+	uint32_t counted = 0;
+	for (uint32_t r = lo + threadIdx.x; r < hi; r += CAM_SUM_THREADS) {
+		if (a.numsteps[2 * (size_t)r] == 0) continue;  // cut to no sample by the compacted budget, or without samples
+		const float* row = a.ray_grad + 3 * (size_t)r;
+		for (int k = 0; k < 3; ++k) g[k] += row[k];
+		++counted;
+	}
+	for (int off = 32; off > 0; off >>= 1) {
+		for (int k = 0; k < 3; ++k) g[k] += __shfl_xor(g[k], off);
+		counted += __shfl_xor(counted, off);
+	}
+	__shared__ float part[CAM_SUM_THREADS / 64][3];
+	__shared__ uint32_t part_n[CAM_SUM_THREADS / 64];
+	if ((threadIdx.x & 63) == 0) {
+		for (int k = 0; k < 3; ++k) part[threadIdx.x >> 6][k] = g[k];
+		part_n[threadIdx.x >> 6] = counted;
+	}
+	__syncthreads();
+	if (threadIdx.x < 3) {
+		float s = 0.f;
+		uint32_t n = 0;
+		for (uint32_t w = 0; w < CAM_SUM_THREADS / 64; ++w) { s += part[w][threadIdx.x]; n += part_n[w]; }
+		if (n) a.image_grad[3 * (size_t)img + threadIdx.x] += s;  // no counted ray: the accumulator keeps its bits
+	}
+}
+
+void exposure_gradients(const ExposureGradArgs& a, hipStream_t s) {
+	if (a.n_rays_cap == 0 || a.n_images == 0) return;
+	k_exposure_image_sum<<<a.n_images, CAM_SUM_THREADS, 0, s>>>(a);
 	NGP_HIP(hipGetLastError());
 }
 
@@ -222,6 +273,10 @@ struct ngp_pose_optimizer {
 	std::vector<pose::AdamState> pos, rot;
 };
 
+struct ngp_exposure_optimizer {
+	std::vector<pose::AdamState> v;
+};
+
 static void to_c(const pose::AdamState& s, ngp_adam_state* o) {
 	o->iter = s.iter;
 	memcpy(o->first_moment, s.first_moment, 12);
@@ -302,6 +357,64 @@ int ngp_pose_optimizer_set_state(ngp_pose_optimizer* o, uint32_t i, const ngp_ad
 	if (!o || i >= o->pos.size()) return invalid("invalid argument: pose optimizer: image index");
 	if (pos) from_c(*pos, &o->pos[i]);
 	if (rot) from_c(*rot, &o->rot[i]);
+	return NGP_OK;
+}
+
+// ---- per-image exposure optimisers (testbed_nerf.cu:3831-3858) ----------------------------------------------------
+int ngp_exposure_optimizer_create(uint32_t n_images, ngp_exposure_optimizer** out) {
+	if (!out || n_images == 0) return invalid("invalid argument: exposure optimizer: n_images > 0 and an out pointer");
+	auto o = new ngp_exposure_optimizer();
+	o->v.resize(n_images);
+	for (auto& s : o->v) s.learning_rate = 1e-3f;  // testbed_nerf.cu:3036; overwritten before every step
+	*out = o;
+	return NGP_OK;
+}
+void ngp_exposure_optimizer_destroy(ngp_exposure_optimizer* o) { delete o; }
+uint32_t ngp_exposure_optimizer_n_images(const ngp_exposure_optimizer* o) { return o ? (uint32_t)o->v.size() : 0; }
+
+static void exposure_reset_state(pose::AdamState& s) {  // reset_state keeps the hyperparameters
+	pose::AdamState z;
+	z.learning_rate = s.learning_rate; z.epsilon = s.epsilon; z.beta1 = s.beta1; z.beta2 = s.beta2;
+	s = z;
+}
+int ngp_exposure_optimizer_reset(ngp_exposure_optimizer* o) {
+	if (!o) return invalid("invalid argument: exposure optimizer");
+	for (auto& s : o->v) exposure_reset_state(s);
+	return NGP_OK;
+}
+int ngp_exposure_optimizer_reset_one(ngp_exposure_optimizer* o, uint32_t i) {
+	if (!o || i >= o->v.size()) return invalid("invalid argument: exposure optimizer: image index");
+	exposure_reset_state(o->v[i]);
+	return NGP_OK;
+}
+
+int ngp_exposure_optimizer_step(ngp_exposure_optimizer* o, const float* grad, uint32_t n_steps_between, float l2_reg, float network_lr) {
+	if (!o || !grad || n_steps_between == 0 || !(l2_reg >= 0.0f)) return invalid("invalid argument: exposure optimizer step");
+	const uint32_t n = (uint32_t)o->v.size();
+	const float scale = (float)n / 128.0f / (float)n_steps_between;  // per_camera_loss_scale (testbed_nerf.cu:3784)
+	float mean[3] = {0.f, 0.f, 0.f};
+	for (uint32_t i = 0; i < n; ++i) {
+		pose::AdamState& e = o->v[i];
+		float g[3];
+		for (int k = 0; k < 3; ++k) g[k] = grad[3 * i + k] * scale + e.variable[k] * l2_reg;
+		e.learning_rate = network_lr;
+		pose::adam_step_position(e, g);
+		for (int k = 0; k < 3; ++k) mean[k] += e.variable[k];
+	}
+	for (int k = 0; k < 3; ++k) mean[k] /= (float)n;
+	for (auto& e : o->v)  // renormalise: only the exposures' differences are identifiable
+		for (int k = 0; k < 3; ++k) e.variable[k] -= mean[k];
+	return NGP_OK;
+}
+
+int ngp_exposure_optimizer_get(const ngp_exposure_optimizer* o, uint32_t i, ngp_adam_state* out) {
+	if (!o || !out || i >= o->v.size()) return invalid("invalid argument: exposure optimizer: image index");
+	to_c(o->v[i], out);
+	return NGP_OK;
+}
+int ngp_exposure_optimizer_set_state(ngp_exposure_optimizer* o, uint32_t i, const ngp_adam_state* state) {
+	if (!o || !state || i >= o->v.size()) return invalid("invalid argument: exposure optimizer: image index");
+	from_c(*state, &o->v[i]);
 	return NGP_OK;
 }
 

@@ -131,7 +131,10 @@ inline bool error_cdfs_arg(const ngp_nerf_error_cdfs* c, ErrorCdfs* out) {
 // The loss pass (compute_loss, nerf.h) and the sampler (sample_rays) behind the C-ABI's null checks, with their
 // scratch buffers; the caller fills the arguments by field name. n_rays_total_for_image_idx 0 means n_rays.
 // cams (optional): the device cameras to trace instead of the dataset's.
-int run_compute_loss(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, LossArgs a);
+// exposure_grad: also take the rays' exposure gradients (a.exposure bound), kept behind the per-ray scratch: the pointer
+// comes back in *exposure_ray_grad for exposure_gradients, and holds until the thread's next loss pass.
+int run_compute_loss(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, LossArgs a, bool exposure_grad = false,
+                     const float** exposure_ray_grad = nullptr);
 int run_sampler(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, SampleArgs a, const Camera* cams);
 
 }  // namespace nerf
@@ -197,6 +200,7 @@ struct ngp_nerf_trainer {
 		if (d_cams) (void)hipFree(d_cams);
 		if (d_raw) (void)hipFree(d_raw);
 		ngp_pose_optimizer_destroy(pose);
+		ngp_exposure_optimizer_destroy(expo);
 	}
 	// data parallelism: rank r traces global rays [R r / N, R (r+1) / N), compacts to B / N,
 	// evaluates 1/N of the density-grid samples; the exchange steps go through `allreduce`
@@ -253,6 +257,18 @@ struct ngp_nerf_trainer {
 	uint32_t n_steps_since_cam_update = 0;
 	Buf cam_grad, cam_ray_grad, dinput;  // [2][n_images x 3] accumulators {pos, rot}; per-ray workspace; dL/dinput [B x 7]
 	const float* graph_dinput = nullptr;  // the gradient pointer the training graph was captured with
+	// Per-image exposure (Training::optimize_exposure, exposure_l2_reg, cam_exposure; testbed_nerf.cu:3831-3858): the
+	// optimisers' variables are mirrored in expo_dev [n_images x 3] once an exposure is not zero or the switch is on
+	// (expo_bound), and the loss pass then runs its exposure form; with the switch on it also takes the gradient, summed
+	// per image into expo_grad, which starts from zero after every update. The update shares n_steps_since_cam_update
+	// with pose refinement. The sampler reads none of this.
+	bool optimize_exposure = false;
+	float exposure_l2_reg = 0.0f;
+	ngp_exposure_optimizer* expo = nullptr;
+	Buf expo_dev, expo_grad;
+	bool expo_bound = false;
+	std::vector<float> expo_host;  // the upload's source: written only after the stream that read it was waited for
+	void upload_exposures(hipStream_t s);
 	// the last step's sampler call, for ngp_nerf_trainer_last_samples
 	ngp_rng last_rng{0, 0};
 	uint32_t last_n_rays = 0, last_max_samples = 0;

@@ -233,6 +233,21 @@ int ngp_nerf_save_snapshot(ngp_nerf_trainer* t, void* stream, const char* path, 
 			nerf["cam_pos_offset"] = pos;
 			nerf["cam_rot_offset"] = rot;
 		}
+		// engine extension (the reference does not save cam_exposure): the per-image exposure optimisers in the same
+		// form, once one of them has left its initial state; a trainer that never used them writes the bytes it wrote
+		// before they existed
+		{
+			Value ex = Value::array();
+			bool used = false;
+			for (uint32_t i = 0; i < t->cams.size(); ++i) {
+				ngp_adam_state e;
+				check_rc(ngp_nerf_trainer_exposure_optimizer_state(t, i, &e));
+				used = used || e.iter != 0;
+				for (int k = 0; k < 3; ++k) used = used || e.variable[k] != 0.f || e.first_moment[k] != 0.f || e.second_moment[k] != 0.f;
+				ex.arr.push_back(adam_to_value(e));
+			}
+			if (used) nerf["cam_exposure"] = ex;
+		}
 		snap["training_step"] = Value::uint(t->training_step);
 		snap["loss"] = Value::real(t->loss_scalar);
 		snap["aabb"]["min"] = vec3(t->cfg.aabb_min);
@@ -321,9 +336,19 @@ int ngp_nerf_load_snapshot(ngp_nerf_trainer* t, void* stream, const char* path) 
 					const ngp_adam_state st = adam_from_value(rot->arr[i]);
 					check_rc(ngp_pose_optimizer_set_state(t->pose, i, nullptr, &st));
 				}
+			// the exposures likewise (engine extension; key absent: zeros)
+			const Value* ex = nerf.find("cam_exposure");
+			check_rc(ngp_exposure_optimizer_reset(t->expo));
+			if (ex && ex->type == Value::Array && ex->arr.size() == n)
+				for (uint32_t i = 0; i < n; ++i) {
+					const ngp_adam_state st = adam_from_value(ex->arr[i]);
+					check_rc(ngp_exposure_optimizer_set_state(t->expo, i, &st));
+				}
 			t->n_steps_since_cam_update = 0;
 			NGP_HIP(hipDeviceSynchronize());
 			t->rebuild_cameras(s);
+			t->upload_exposures(s);
+			NGP_HIP(hipStreamSynchronize(s));
 		}
 		// the environment map, where the snapshot has one (a snapshot without it leaves this trainer's as it is)
 		if (const Value* em = snap.find("envmap")) {

@@ -92,6 +92,7 @@ int ngp_nerf_trainer_create(ngp_model* model, ngp_trainer* trainer, const ngp_ne
 		NGP_HIP(hipMalloc((void**)&t->d_raw, (size_t)d.n_images * 12 * sizeof(float)));
 		NGP_HIP(hipMemcpy(t->d_raw, d.xforms.data(), (size_t)d.n_images * 12 * sizeof(float), hipMemcpyHostToDevice));
 		if (ngp_pose_optimizer_create(d.n_images, &t->pose) != NGP_OK) throw Error(ngp_last_error());
+		if (ngp_exposure_optimizer_create(d.n_images, &t->expo) != NGP_OK) throw Error(ngp_last_error());
 		*out = t.release();
 	});
 }
@@ -152,11 +153,19 @@ static void cameras_quiesce(ngp_nerf_trainer* t) {
 static const char* const ERROR_SAMPLING_VS_EXTRINSICS =
 	"optimize_extrinsics cannot be combined with sample_focal_plane_proportional_to_error / "
 	"sample_image_proportional_to_error: turn one of them off first";
+// The exposure gradient's per-image sum relies on the same contiguous runs; it does divide by uv_pdf, so drawing the
+// position in the image from the error map is allowed
+static const char* const IMAGE_SAMPLING_VS_EXPOSURE =
+	"optimize_exposure cannot be combined with sample_image_proportional_to_error: turn one of them off first";
+static const char* const EXPOSURE_VS_DATA_PARALLEL =
+	"exposure optimisation is single-GPU: the per-image gradient sums of a data-parallel trainer would need their own "
+	"all-reduce";
 
 int ngp_nerf_trainer_set_error_sampling(ngp_nerf_trainer* t, int focal_plane, int image) {
 	if (!t) return NGP_INVALID;
 	NERF_TRY({
 		NGP_CHECK(!(focal_plane || image) || !t->cam.optimize_extrinsics, ERROR_SAMPLING_VS_EXTRINSICS);
+		NGP_CHECK(!image || !t->optimize_exposure, IMAGE_SAMPLING_VS_EXPOSURE);
 		t->drain();  // a prelaunched sampler drew its pixels under the old switches
 		t->sample_focal_plane_by_error = focal_plane != 0;
 		t->sample_image_by_error = image != 0;
@@ -299,6 +308,79 @@ int ngp_nerf_trainer_set_camera_training(ngp_nerf_trainer* t, const ngp_nerf_cam
 	});
 }
 
+// ---- per-image exposure ------------------------------------------------------------------------------------------
+// The optimisers' variables to the device array the loss pass reads, on `s`; binds the array once a variable is not
+// zero (with the switch off and every exposure zero the loss pass runs without it)
+void ngp_nerf_trainer::upload_exposures(hipStream_t s) {
+	const uint32_t n = (uint32_t)cams.size();
+	expo_host.resize((size_t)3 * n);
+	bool any = false;
+	for (uint32_t i = 0; i < n; ++i) {
+		ngp_adam_state e;
+		check_rc(ngp_exposure_optimizer_get(expo, i, &e));
+		for (int k = 0; k < 3; ++k) { expo_host[(size_t)3 * i + k] = e.variable[k]; any = any || e.variable[k] != 0.0f; }
+	}
+	expo_bound = any || optimize_exposure;
+	if (!expo_bound) return;
+	NGP_HIP(hipMemcpyAsync(expo_dev.get<float>((size_t)3 * n), expo_host.data(), expo_host.size() * sizeof(float), hipMemcpyHostToDevice, s));
+}
+// the exposures are about to change outside a step: no loss pass may still read the old ones (the sampler reads none,
+// so a prelaunched one stays)
+static void exposures_changed(ngp_nerf_trainer* t) {
+	NGP_HIP(hipDeviceSynchronize());
+	t->upload_exposures(nullptr);
+	NGP_HIP(hipDeviceSynchronize());
+}
+
+int ngp_nerf_trainer_set_exposure_training(ngp_nerf_trainer* t, int optimize_exposure, float exposure_l2_reg) {
+	if (!t || !(exposure_l2_reg >= 0.0f) || std::isinf(exposure_l2_reg)) return NGP_INVALID;
+	NERF_TRY({
+		NGP_CHECK(!optimize_exposure || !t->dp(), EXPOSURE_VS_DATA_PARALLEL);
+		NGP_CHECK(!optimize_exposure || !t->sample_image_by_error, IMAGE_SAMPLING_VS_EXPOSURE);
+		const bool on = optimize_exposure != 0;
+		t->exposure_l2_reg = exposure_l2_reg;
+		if (on == t->optimize_exposure) return NGP_OK;
+		t->optimize_exposure = on;
+		exposures_changed(t);  // binds (or, with every exposure zero, unbinds) the device array
+		if (on) {
+			// a window of its own unless pose refinement's is running: the sums start from zero either way
+			if (!t->cam.optimize_extrinsics) t->n_steps_since_cam_update = 0;
+			const size_t n = (size_t)3 * t->cams.size();
+			NGP_HIP(hipMemset(t->expo_grad.get<float>(n), 0, n * sizeof(float)));
+		}
+	});
+}
+int ngp_nerf_trainer_get_exposure_training(const ngp_nerf_trainer* t, int* optimize_exposure, float* exposure_l2_reg) {
+	if (!t) return NGP_INVALID;
+	if (optimize_exposure) *optimize_exposure = t->optimize_exposure ? 1 : 0;
+	if (exposure_l2_reg) *exposure_l2_reg = t->exposure_l2_reg;
+	return NGP_OK;
+}
+int ngp_nerf_trainer_camera_exposure(const ngp_nerf_trainer* t, uint32_t i, float* out) {
+	if (!t || !out || i >= t->cams.size()) return NGP_INVALID;
+	ngp_adam_state e;
+	const int rc = ngp_exposure_optimizer_get(t->expo, i, &e);
+	if (rc == NGP_OK) memcpy(out, e.variable, 12);
+	return rc;
+}
+int ngp_nerf_trainer_set_camera_exposure(ngp_nerf_trainer* t, uint32_t i, const float* rgb) {
+	if (!t || !rgb || i >= t->cams.size()) return NGP_INVALID;
+	for (int k = 0; k < 3; ++k)
+		if (!std::isfinite(rgb[k])) return NGP_INVALID;
+	NERF_TRY({
+		check_rc(ngp_exposure_optimizer_reset_one(t->expo, i));
+		ngp_adam_state e;
+		check_rc(ngp_exposure_optimizer_get(t->expo, i, &e));
+		memcpy(e.variable, rgb, 12);
+		check_rc(ngp_exposure_optimizer_set_state(t->expo, i, &e));
+		exposures_changed(t);
+	});
+}
+int ngp_nerf_trainer_exposure_optimizer_state(const ngp_nerf_trainer* t, uint32_t i, ngp_adam_state* out) {
+	if (!t || !out || i >= t->cams.size()) return NGP_INVALID;
+	return ngp_exposure_optimizer_get(t->expo, i, out);
+}
+
 int ngp_nerf_trainer_camera_extrinsics(const ngp_nerf_trainer* t, uint32_t i, float* out) {
 	if (!t || !out || i >= t->cams.size()) return NGP_INVALID;
 	NERF_TRY(t->refined_xform(i, out));
@@ -310,7 +392,9 @@ int ngp_nerf_trainer_set_camera_extrinsics(ngp_nerf_trainer* t, uint32_t i, cons
 		cameras_quiesce(t);
 		memcpy(&t->xforms[(size_t)12 * i], xform, 48);
 		check_rc(ngp_pose_optimizer_reset_one(t->pose, i));
+		check_rc(ngp_exposure_optimizer_reset_one(t->expo, i));  // cam_exposure[frame_idx].reset_state() (:2913)
 		t->rebuild_cameras(nullptr);
+		exposures_changed(t);
 	});
 }
 
@@ -319,8 +403,10 @@ int ngp_nerf_trainer_reset_camera_extrinsics(ngp_nerf_trainer* t) {
 	NERF_TRY({
 		cameras_quiesce(t);
 		check_rc(ngp_pose_optimizer_reset(t->pose));
+		check_rc(ngp_exposure_optimizer_reset(t->expo));  // :2930-2932
 		t->n_steps_since_cam_update = 0;
 		t->rebuild_cameras(nullptr);
+		exposures_changed(t);
 	});
 }
 
@@ -345,6 +431,10 @@ int ngp_nerf_trainer_set_data_parallel(ngp_nerf_trainer* t, uint32_t rank, uint3
 	if (!t || world == 0 || rank >= world || (world > 1 && !allreduce)) return NGP_INVALID;
 	if (allreduce && t->cam.optimize_extrinsics) {
 		nerf_set_error("camera pose refinement is single-GPU: turn optimize_extrinsics off before setting an exchange hook");
+		return NGP_ERROR;
+	}
+	if (allreduce && t->optimize_exposure) {
+		nerf_set_error("exposure optimisation is single-GPU: turn optimize_exposure off before setting an exchange hook");
 		return NGP_ERROR;
 	}
 	if (allreduce && t->env.train) {
@@ -716,6 +806,9 @@ struct Step {
 	bool cam = false;           // camera pose refinement: the training pass also writes dL/dinput
 	float* dinput = nullptr;    // [Bl x 7]
 	bool cam_updated = false;   // this step ended with a pose update (step_camera_update)
+	bool expo = false;          // optimize_exposure: the loss pass also takes the rays' exposure gradients
+	const float* expo_ray_grad = nullptr;  // ... kept here for step_exposure_gradients
+	bool expo_due = false;      // an exposure-only update is due at the end of this step (step_exposure_update)
 	bool em_closed = false;     // this step closed an error map window: the CDFs were rebuilt (error_map_step_done)
 };
 
@@ -753,6 +846,7 @@ static void step_plan(ngp_nerf_trainer* t, Step& c) {
 	c.early_pub = t->early() && sp.Rl > 0;
 	c.can_pipeline = t->pipeline && (!c.dp || t->dp_capturable);
 	c.cam = t->cam.optimize_extrinsics != 0;
+	c.expo = t->optimize_exposure && sp.Rl > 0;
 	t->last_rng = c.rng; t->last_n_rays = sp.R; t->last_max_samples = sp.max_inference;
 	t->last_ray_indices = sp.ray_indices; t->last_rays = sp.rays; t->last_counters = sp.ctr;
 	c.dinput = c.cam ? t->dinput.get<float>((size_t)sp.Bl * 7) : nullptr;
@@ -775,7 +869,7 @@ static void step_sample_and_infer(ngp_nerf_trainer* t, hipStream_t s, const Step
 
 // Loss and compaction, rollover, and the step's counters to the host. The counters are final here (the training
 // pass does not touch them): published before the training pass, the host can size the next step while it runs.
-static void step_loss_and_publish(ngp_nerf_trainer* t, hipStream_t s, const Step& c) {
+static void step_loss_and_publish(ngp_nerf_trainer* t, hipStream_t s, Step& c) {
 	const SamplePlan& sp = c.sp;
 	const uint32_t R = sp.R, Rl = sp.Rl, Bl = sp.Bl;
 	uint32_t* ctr = sp.ctr;
@@ -812,7 +906,9 @@ static void step_loss_and_publish(ngp_nerf_trainer* t, hipStream_t s, const Step
 		a.pub_host = c.early_pub ? t->host_ctr : nullptr; a.pub_seq = pub_seq; a.cdfs = t->sampling_cdfs();
 		a.envmap = env.bound() ? (const float*)env.params.p : nullptr; a.env_w = env.w; a.env_h = env.h;
 		a.env_loss_type = t->envmap_loss_type(); a.env_acc = env_acc;
-		check_rc(run_compute_loss(t->data, &t->cfg, s, a));
+		// per-image exposures (bound once one is not zero, or with optimize_exposure, which also takes their gradient)
+		a.exposure = t->expo_bound ? (const float*)t->expo_dev.p : nullptr;
+		check_rc(run_compute_loss(t->data, &t->cfg, s, a, c.expo, &c.expo_ray_grad));
 	}
 	if (!c.dp) {
 		// single GPU: the rollover launch (fill_rollover_and_rescale + fill_rollover) also publishes the counters
@@ -837,6 +933,26 @@ static void step_loss_and_publish(ngp_nerf_trainer* t, hipStream_t s, const Step
 		k_dp_publish<<<1, 64, 0, s>>>(d, ctr, t->host_ctr, ++t->publish_seq);
 	}
 	NGP_HIP(hipGetLastError());
+}
+
+// optimize_exposure, device part (testbed_nerf.cu:3641-3644, 1973-1986): the rays' exposure gradients summed per image
+// into the trainer's accumulators, which start from zero after every update. Before the sample buffers are released:
+// the sum reads the ray indices and the compacted sample counts.
+static void step_exposure_gradients(ngp_nerf_trainer* t, hipStream_t s, const Step& c) {
+	if (!t->optimize_exposure) return;
+	ProfScope ps("nerf_exposure_gradients", s);
+	const uint32_t n_images = t->data->ds.n_images;
+	float* acc = t->expo_grad.get<float>((size_t)3 * n_images);
+	// a window's first step clears the sums, also when it has no ray of its own (the counter advances all the same)
+	if (t->n_steps_since_cam_update == 0) NGP_HIP(hipMemsetAsync(acc, 0, (size_t)3 * n_images * sizeof(float), s));
+	if (!c.expo) return;
+	NGP_CHECK(c.expo_ray_grad, "nerf: the loss pass took no exposure gradient");
+	const SamplePlan& sp = c.sp;
+	ExposureGradArgs a{};
+	a.n_rays_cap = sp.Rl; a.n_rays_total = sp.R; a.n_images = n_images;
+	a.ray_counter = sp.ctr; a.ray_indices = sp.ray_indices; a.numsteps = sp.numsteps;
+	a.ray_grad = c.expo_ray_grad; a.image_grad = acc;
+	exposure_gradients(a, s);
 }
 
 // The sample buffers and counters are free for the next step's sampler (early(): nothing to release, that sampler
@@ -917,18 +1033,40 @@ static void step_camera_gradients(ngp_nerf_trainer* t, hipStream_t s, const Step
 
 // Camera pose refinement, host part (testbed_nerf.cu:3754-3809): every n_steps_between_cam_updates steps the sums come
 // back, every camera's optimisers step and the cameras are rebuilt and uploaded before any later sampler is launched.
+// optimize_exposure shares the counter and the update (:3831-3858): its sums come back, every image's optimiser steps
+// with the network optimiser's learning rate, the mean is removed and the exposures are uploaded on the step's stream,
+// where the next loss pass reads them. The sampler reads none of it: an exposure-only update keeps the prelaunch, and
+// its round trip is put off until the next sampler is under way (step_exposure_update); with pose refinement on as
+// well, which has to wait for the stream before the sampler anyway, both sums come back behind one synchronisation.
+static void exposure_update_host(ngp_nerf_trainer* t, hipStream_t s, const std::vector<float>& g, uint32_t between) {
+	check_rc(ngp_exposure_optimizer_step(t->expo, g.data(), between, t->exposure_l2_reg, ngp_trainer_learning_rate(t->trainer)));
+	t->upload_exposures(s);
+}
 static void step_camera_update(ngp_nerf_trainer* t, hipStream_t s, Step& c) {
-	if (!c.cam) return;
-	if (++t->n_steps_since_cam_update < std::max(t->cam.n_steps_between_cam_updates, 1u)) return;
-	const uint32_t n_images = t->data->ds.n_images;
-	std::vector<float> g((size_t)6 * n_images);
-	NGP_HIP(hipMemcpyAsync(g.data(), t->cam_grad.p, g.size() * sizeof(float), hipMemcpyDeviceToHost, s));
-	NGP_HIP(hipStreamSynchronize(s));
-	check_rc(ngp_pose_optimizer_step(t->pose, g.data(), g.data() + (size_t)3 * n_images, std::max(t->cam.n_steps_between_cam_updates, 1u),
-	                                 t->cam.extrinsic_learning_rate, t->cam.extrinsic_l2_reg, ngp_trainer_learning_rate(t->trainer)));
-	t->rebuild_cameras(s);
+	const bool expo = t->optimize_exposure;  // also on a step without rays, as the counter is
+	if (!c.cam && !expo) return;
+	const uint32_t between = std::max(t->cam.n_steps_between_cam_updates, 1u);
+	if (++t->n_steps_since_cam_update < between) return;
 	t->n_steps_since_cam_update = 0;
+	if (!c.cam) { c.expo_due = true; return; }
+	const uint32_t n_images = t->data->ds.n_images;
+	std::vector<float> g((size_t)6 * n_images), ge(expo ? (size_t)3 * n_images : 0);
+	NGP_HIP(hipMemcpyAsync(g.data(), t->cam_grad.p, g.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+	if (expo) NGP_HIP(hipMemcpyAsync(ge.data(), t->expo_grad.get<float>(ge.size()), ge.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+	NGP_HIP(hipStreamSynchronize(s));
+	check_rc(ngp_pose_optimizer_step(t->pose, g.data(), g.data() + (size_t)3 * n_images, between, t->cam.extrinsic_learning_rate,
+	                                 t->cam.extrinsic_l2_reg, ngp_trainer_learning_rate(t->trainer)));
+	t->rebuild_cameras(s);
 	c.cam_updated = true;
+	if (expo) exposure_update_host(t, s, ge, between);
+}
+// the exposure-only update's round trip, after the next step's sampler (and density-grid samples) have been launched
+static void step_exposure_update(ngp_nerf_trainer* t, hipStream_t s, const Step& c) {
+	if (!c.expo_due) return;
+	std::vector<float> g((size_t)3 * t->data->ds.n_images);
+	NGP_HIP(hipMemcpyAsync(g.data(), t->expo_grad.get<float>(g.size()), g.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+	NGP_HIP(hipStreamSynchronize(s));
+	exposure_update_host(t, s, g, std::max(t->cam.n_steps_between_cam_updates, 1u));
 }
 
 // NerfCounters::update_after_training (testbed_nerf.cu:3583-3609): the host reads the step's counters and adapts
@@ -1011,6 +1149,7 @@ int ngp_nerf_train_step(ngp_nerf_trainer* t, void* stream, int get_loss, ngp_ner
 		step_plan(t, c);
 		step_sample_and_infer(t, s, c);
 		step_loss_and_publish(t, s, c);
+		step_exposure_gradients(t, s, c);
 		step_release_samples(t, s, c);
 		step_train_pass(t, s, c);
 		step_envmap_update(t, s, c);
@@ -1021,6 +1160,7 @@ int ngp_nerf_train_step(ngp_nerf_trainer* t, void* stream, int get_loss, ngp_ner
 		c.em_closed = error_map_step_done(t, s);
 		step_prelaunch_sampler(t, c);
 		step_pregenerate_grid_samples(t, c);
+		step_exposure_update(t, s, c);
 		if (st) {
 			st->step = t->training_step;
 			st->rays_per_batch = t->rays_per_batch;

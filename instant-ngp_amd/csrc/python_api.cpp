@@ -452,6 +452,18 @@ PYBIND11_MODULE(pyngp, m) {
 			     std::memcpy(out.mutable_data(), d.data(), d.size() * sizeof(float));
 			     return std::move(out);
 		     }, py::arg("frame_idx"), "Engine extension: the stored depth image [H, W] of a training view; None without one.")
+		// per-image exposure (python_api.cu:620, 634)
+		.def_property("optimize_exposure", [](NerfTrainingView& v) { return v.t->optimize_exposure(); },
+		              [](NerfTrainingView& v, bool x) { v.t->set_exposure_training(x, v.t->exposure_l2_reg()); })
+		.def_property("exposure_l2_reg", [](NerfTrainingView& v) { return v.t->exposure_l2_reg(); },
+		              [](NerfTrainingView& v, float x) { v.t->set_exposure_training(v.t->optimize_exposure(), x); })
+		.def("get_camera_exposure",
+		     [](NerfTrainingView& v, int frame_idx) {
+			     py::array_t<float> a(3);
+			     v.t->get_camera_exposure(frame_idx, a.mutable_data());
+			     return a;
+		     },
+		     py::arg("frame_idx"), "Engine extension: a training image's learned log2 exposure per channel.")
 		// error-driven sampling (python_api.cu:624-625); not reproducible from run to run while on
 		.def_property("sample_focal_plane_proportional_to_error", [](NerfTrainingView& v) { return v.t->sample_focal_plane_by_error(); },
 		              [](NerfTrainingView& v, bool x) { v.t->set_error_sampling(x, v.t->sample_image_by_error()); })

@@ -386,6 +386,7 @@ public:
 			push_error_sampling();
 			push_envmap();
 			push_depth_supervision();
+			push_exposure_training();
 		}
 	}
 	uint64_t n_params() const { return m_model ? ngp_model_n_params(m_model) : 0; }
@@ -748,6 +749,7 @@ public:
 		m_sample_image_by_error = image;
 		try {
 			check_error_sampling_vs_extrinsics();
+			check_image_sampling_vs_exposure();
 			push_error_sampling();
 		} catch (...) {
 			m_sample_focal_plane_by_error = was_f;
@@ -776,6 +778,36 @@ public:
 		if (m_nerf_trainer)
 			check(ngp_nerf_trainer_set_depth_supervision(m_nerf_trainer, m_depth_lambda, m_depth_loss_type),
 			      "ngp_nerf_trainer_set_depth_supervision");
+	}
+	// ---- per-image exposure (nerf.training.optimize_exposure / exposure_l2_reg, python_api.cu:620, 634): kept here until
+	// there is a trainer, pushed to a live one; the exposures themselves belong to the trainer (reset_network zeroes them)
+	bool optimize_exposure() const { return m_optimize_exposure; }
+	float exposure_l2_reg() const { return m_exposure_l2_reg; }
+	void set_exposure_training(bool optimize, float l2_reg) {
+		if (!(l2_reg >= 0.f) || std::isinf(l2_reg)) throw std::runtime_error("exposure_l2_reg: a finite value >= 0");
+		const bool was = m_optimize_exposure;
+		const float was_reg = m_exposure_l2_reg;
+		m_optimize_exposure = optimize;
+		m_exposure_l2_reg = l2_reg;
+		try {
+			check_image_sampling_vs_exposure();
+			push_exposure_training();
+		} catch (...) {
+			m_optimize_exposure = was;
+			m_exposure_l2_reg = was_reg;
+			throw;
+		}
+	}
+	void push_exposure_training() {
+		if (m_nerf_trainer)
+			check(ngp_nerf_trainer_set_exposure_training(m_nerf_trainer, m_optimize_exposure ? 1 : 0, m_exposure_l2_reg),
+			      "ngp_nerf_trainer_set_exposure_training");
+	}
+	// cam_exposure[i].variable(): zeros before there is a trainer, and for a frame out of range
+	void get_camera_exposure(int frame_idx, float out[3]) const {
+		out[0] = out[1] = out[2] = 0.f;
+		if (frame_idx < 0 || (size_t)frame_idx >= m_nerf_images.size() || !m_nerf_trainer) return;
+		check(ngp_nerf_trainer_camera_exposure(m_nerf_trainer, (uint32_t)frame_idx, out), "ngp_nerf_trainer_camera_exposure");
 	}
 	// dtype 0 uint16, 1 float32; pixels null: zeros (or, with a negative scale, no depth)
 	void set_image_depth(uint32_t frame_idx, const void* pixels, int dtype, float depth_scale) {
@@ -861,6 +893,11 @@ public:
 		if (m_cam_training.optimize_extrinsics && (m_sample_focal_plane_by_error || m_sample_image_by_error))
 			throw std::runtime_error("optimize_extrinsics cannot be combined with sample_focal_plane_proportional_to_error / "
 			                         "sample_image_proportional_to_error: turn one of them off first");
+	}
+	void check_image_sampling_vs_exposure() const {
+		if (m_optimize_exposure && m_sample_image_by_error)
+			throw std::runtime_error("optimize_exposure cannot be combined with sample_image_proportional_to_error: turn one of "
+			                         "them off first");
 	}
 	// Training::transforms[i].start: the trainer's refined transform, or the dataset's before there is a trainer
 	void training_view_xform(uint32_t i, float out[12]) const {
@@ -1033,6 +1070,8 @@ private:
 	ngp_nerf_camera_training m_cam_training{0, 16, 1e-4f, 1e-3f};  // testbed.h:716-785 defaults
 	bool m_sample_focal_plane_by_error = false, m_sample_image_by_error = false;  // testbed.h:733-734
 	bool m_train_envmap = false;            // Training::train_envmap
+	bool m_optimize_exposure = false;       // Training::optimize_exposure
+	float m_exposure_l2_reg = 0.f;          // Training::exposure_l2_reg
 	float m_depth_lambda = 0.f;             // Training::depth_supervision_lambda (testbed.h:719)
 	uint32_t m_depth_loss_type = 1;         // Training::depth_loss_type: L1 (testbed.h:745)
 	uint32_t m_envmap_res[2] = {0, 0};      // NerfDataset::envmap_resolution, or create_envmap's; 0: no map

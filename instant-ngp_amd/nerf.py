@@ -229,7 +229,8 @@ def training_pixels(ds, cfg, n_rays, rng, cdfs=None, ray_offset=0, n_rays_total=
 
 def compute_loss(ds, cfg, n_rays, rng, max_compacted, samples, network_output, mean_density, loss_scale=128.0,
                  n_rays_total=None, stream=None, error_map=None, keep_state=False, state_capacity=None, cdfs=None,
-                 envmap=None, envmap_gradient=None, envmap_loss=None, depth_lambda=0.0, depth_loss="L1", depth_entry=None):
+                 envmap=None, envmap_gradient=None, envmap_loss=None, depth_lambda=0.0, depth_loss="L1", depth_entry=None,
+                 exposure=None, exposure_gradient=None, exposure_entry=None):
     """compute_loss_kernel_train_nerf (testbed_nerf.cu:1660-2012). `samples` is the dict returned by
     generate_training_samples (its numsteps is rewritten to the compacted {n, base}). error_map: a
     float32 device tensor [n_images, h, w] the compacted rays' losses are added into (:1869-1899).
@@ -245,7 +246,12 @@ def compute_loss(ds, cfg, n_rays, rng, max_compacted, samples, network_output, m
     depth_lambda, depth_loss: depth supervision (testbed_nerf.cu:1848-1856, 1952-1956) against the dataset's depth images
     (NerfDataset.set_depth) with the loss of that name or number. With depth_lambda > 0 (or depth_entry=True) the call
     goes through ngp_nerf_compute_loss_depth, which takes error_map, cdfs, envmap and keep_state in any combination
-    (the kept state then has six planes); with depth_lambda 0 that entry point gives the others' bits."""
+    (the kept state then has six planes); with depth_lambda 0 that entry point gives the others' bits.
+    exposure: a contiguous float32 device tensor [n_images, 3], the images' log2 exposures per channel: the target's
+    texel is scaled by 2^exposure (testbed_nerf.cu:1794-1818). exposure_gradient: a tensor of the same shape the
+    per-image sums of the rays' dloss_by_dexposure (:1973-1986) are ADDED onto, without atomics (the same bits in every
+    run). With exposure given (or exposure_entry=True) the call goes through ngp_nerf_compute_loss_exposure, which takes
+    everything the depth entry point takes; with exposure None it gives that entry point's bits."""
     dev = network_output.device
     # the kernel reads one output row per sample; samples never exceed the sampler's coords buffer
     if network_output.shape[0] < samples["coords"].shape[0]:
@@ -265,7 +271,15 @@ def compute_loss(ds, cfg, n_rays, rng, max_compacted, samples, network_output, m
         raise ValueError("error_map: a contiguous float32 tensor [n_images, h, w]")
     if envmap is None and envmap_gradient is not None:
         raise ValueError("envmap_gradient: needs envmap")
-    if (depth_lambda > 0) if depth_entry is None else depth_entry:
+    if exposure is None and exposure_gradient is not None:
+        raise ValueError("exposure_gradient: needs exposure")
+    for t in (exposure, exposure_gradient):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (len(ds), 3) or not t.is_contiguous() or t.device != dev):
+            raise ValueError("exposure / exposure_gradient: contiguous float32 device tensors [n_images, 3]")
+    through_exposure = exposure is not None if exposure_entry is None else bool(exposure_entry)
+    if exposure is not None and not through_exposure:
+        raise ValueError("exposure: only ngp_nerf_compute_loss_exposure takes it (exposure_entry=False)")
+    if through_exposure or ((depth_lambda > 0) if depth_entry is None else depth_entry):
         for t in (envmap, envmap_gradient):
             if t is not None and (t.dtype != torch.float32 or t.dim() != 3 or t.shape[2] != 4 or not t.is_contiguous()
                                   or t.shape != envmap.shape or t.device != dev):
@@ -277,8 +291,12 @@ def compute_loss(ds, cfg, n_rays, rng, max_compacted, samples, network_output, m
         cap = (samples["coords"].shape[0] if state_capacity is None else int(state_capacity)) if keep_state else 0
         state = torch.empty((6, cap), dtype=torch.float32, device=dev) if keep_state else None
         dl = LOSS[depth_loss] if isinstance(depth_loss, str) else int(depth_loss)
-        check(lib().ngp_nerf_compute_loss_depth(*args, *em, C.byref(e) if e is not None else None, *env, _ptr(state), cap,
-                                                float(depth_lambda), dl))
+        if through_exposure:
+            check(lib().ngp_nerf_compute_loss_exposure(*args, *em, C.byref(e) if e is not None else None, *env, _ptr(state),
+                                                       cap, float(depth_lambda), dl, _ptr(exposure), _ptr(exposure_gradient)))
+        else:
+            check(lib().ngp_nerf_compute_loss_depth(*args, *em, C.byref(e) if e is not None else None, *env, _ptr(state), cap,
+                                                    float(depth_lambda), dl))
         torch.cuda.synchronize(dev)  # the kernels read `keep` and `state`
     elif envmap is not None:
         if error_map is not None or keep_state or cdfs is not None:
@@ -502,6 +520,44 @@ class PoseOptimizer:
             self.handle = None
 
 
+class ExposureOptimizer:
+    """n_images AdamOptimizer<vec3> (Training::cam_exposure) with the update rule of Testbed::train_nerf
+    (testbed_nerf.cu:3831-3858), the mean subtraction included. Host only: no GPU call."""
+
+    def __init__(self, n_images):
+        h = C.c_void_p()
+        check(lib().ngp_exposure_optimizer_create(int(n_images), C.byref(h)))
+        self.handle, self.n_images = h, int(n_images)
+
+    def step(self, grad, n_steps_between=16, l2_reg=0.0, network_lr=1e-2):
+        g = np.ascontiguousarray(np.asarray(grad, np.float32).reshape(self.n_images, 3))
+        check(lib().ngp_exposure_optimizer_step(self.handle, g.ctypes.data, int(n_steps_between), float(l2_reg), float(network_lr)))
+
+    def get(self, i):
+        e = AdamState()
+        check(lib().ngp_exposure_optimizer_get(self.handle, int(i), C.byref(e)))
+        return _adam_dict(e)
+
+    def set_state(self, i, state):
+        st = _adam_struct(state)
+        check(lib().ngp_exposure_optimizer_set_state(self.handle, int(i), C.byref(st)))
+
+    def reset(self):
+        check(lib().ngp_exposure_optimizer_reset(self.handle))
+
+    def reset_one(self, i):
+        check(lib().ngp_exposure_optimizer_reset_one(self.handle, int(i)))
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h:
+            try:
+                lib().ngp_exposure_optimizer_destroy(h)
+            except Exception:
+                pass
+            self.handle = None
+
+
 # ---- Testbed-level training -------------------------------------------------------------------
 class NerfTraining:
     """Testbed::train for NeRF: density-grid update + one training step per call (testbed.cu:4285-4370)."""
@@ -640,6 +696,38 @@ class NerfTraining:
 
     def reset_camera_extrinsics(self):
         check(lib().ngp_nerf_trainer_reset_camera_extrinsics(self.handle))
+
+    # ---- per-image exposure (nerf.training.optimize_exposure / exposure_l2_reg, python_api.cu:620, 634) ----
+    def set_exposure_training(self, optimize=None, l2_reg=None):
+        """Training::optimize_exposure (default off) and exposure_l2_reg (0); an argument not named keeps its value. One
+        log2 exposure per image and channel is learned with the scene, updated every n_steps_between_cam_updates steps
+        with the mean removed. Single GPU; cannot be combined with sample_image_proportional_to_error."""
+        cur = self.exposure_training()
+        o = cur["optimize_exposure"] if optimize is None else bool(optimize)
+        r = cur["exposure_l2_reg"] if l2_reg is None else float(l2_reg)
+        check(lib().ngp_nerf_trainer_set_exposure_training(self.handle, int(o), r))
+
+    def exposure_training(self):
+        o, r = C.c_int(), C.c_float()
+        check(lib().ngp_nerf_trainer_get_exposure_training(self.handle, C.byref(o), C.byref(r)))
+        return {"optimize_exposure": bool(o.value), "exposure_l2_reg": r.value}
+
+    def camera_exposure(self, i):
+        """Image i's log2 exposure per channel (cam_exposure[i].variable())."""
+        out = np.zeros(3, np.float32)
+        check(lib().ngp_nerf_trainer_camera_exposure(self.handle, int(i), out.ctypes.data))
+        return out
+
+    def set_camera_exposure(self, i, rgb):
+        """Set image i's exposure and reset its optimiser's moments (an engine extension)."""
+        v = np.ascontiguousarray(np.broadcast_to(np.asarray(rgb, np.float32), (3,)))
+        check(lib().ngp_nerf_trainer_set_camera_exposure(self.handle, int(i), v.ctypes.data))
+
+    def exposure_optimizer_state(self, i):
+        """cam_exposure[i] as a dict with the reference's member names."""
+        e = AdamState()
+        check(lib().ngp_nerf_trainer_exposure_optimizer_state(self.handle, int(i), C.byref(e)))
+        return _adam_dict(e)
 
     # ---- error-driven sampling (nerf.training.sample_*_proportional_to_error, python_api.cu:624-625) ----
     def set_error_sampling(self, focal_plane=None, image=None):

@@ -56,10 +56,12 @@ _BOXES = [  # min, max, colour
 ]
 
 
-def render(c2w, width, height, camera_angle_x=LEGO_CAMERA_ANGLE_X, device="cpu", return_depth=False):
+def render(c2w, width, height, camera_angle_x=LEGO_CAMERA_ANGLE_X, device="cpu", return_depth=False, exposure=None):
     """RGBA8 [H, W, 4] of the procedural scene from Blender pose c2w. return_depth: also the scene's z-depth per pixel,
     float32 [H, W] in Blender units (distance along the camera's forward axis, what a depth image stores; 0 where the
-    ray misses): NerfDataset.set_depth(i, depth, scale=0.33) puts it into the engine's units."""
+    ray misses): NerfDataset.set_depth(i, depth, scale=0.33) puts it into the engine's units. exposure: the image's log2
+    exposure (a number, or one per channel): the pixels' linear colours are multiplied by 2^exposure and clipped to 1
+    before they are stored as sRGB bytes, as a camera's auto-exposure would; None: the image as it is."""
     f = 0.5 * width / math.tan(0.5 * camera_angle_x)
     j, i = torch.meshgrid(torch.arange(height, device=device, dtype=torch.float32),
                           torch.arange(width, device=device, dtype=torch.float32), indexing="ij")
@@ -100,6 +102,11 @@ def render(c2w, width, height, camera_angle_x=LEGO_CAMERA_ANGLE_X, device="cpu",
     shade = 0.35 + 0.65 * (nrm * light).sum(-1).clamp(min=0)
     alpha = torch.isfinite(best)
     rgb = (col * shade[..., None]).clamp(0, 1)
+    if exposure is not None:
+        e = torch.as_tensor(exposure, dtype=torch.float32, device=device)
+        lin = torch.where(rgb <= 0.04045, rgb / 12.92, ((rgb + 0.055) / 1.055) ** 2.4)
+        lin = (lin * torch.exp2(e)).clamp(0, 1)
+        rgb = torch.where(lin < 0.0031308, 12.92 * lin, 1.055 * lin ** (1 / 2.4) - 0.055).clamp(0, 1)
     out = torch.cat([rgb, alpha[..., None].float()], -1) * alpha[..., None]
     rgba8 = (out * 255 + 0.5).clamp(0, 255).to(torch.uint8).cpu().numpy()
     if not return_depth:
