@@ -885,8 +885,8 @@ int ngp_nerf_compute_loss_depth(const ngp_nerf_dataset* ds, const ngp_nerf_confi
 /* Training::depth_supervision_lambda (default 0: off) and depth_loss_type (ELossType, default L1) of the trainer's
  * steps (testbed.h:719, 745). Only the loss pass reads them: nothing is discarded, and with lambda 0 or a dataset
  * without depth the step issues exactly the launches it would have. Works with the error-map CDFs, an environment
- * map, optimize_extrinsics and data-parallel training (the term is per ray). Sharpness and replacing an image's
- * colours after creation stay unimplemented. */
+ * map, optimize_extrinsics and data-parallel training (the term is per ray). Sharpness stays unimplemented; an
+ * image's colours are replaced with ngp_nerf_dataset_set_image. */
 int ngp_nerf_trainer_set_depth_supervision(ngp_nerf_trainer* t, float lambda, uint32_t loss_type);
 int ngp_nerf_trainer_get_depth_supervision(const ngp_nerf_trainer* t, float* lambda, uint32_t* loss_type);
 
@@ -945,6 +945,34 @@ int ngp_nerf_trainer_camera_exposure(const ngp_nerf_trainer* t, uint32_t i, floa
 /* Engine extension: sets image i's exposure and resets that image's moments and iteration count. */
 int ngp_nerf_trainer_set_camera_exposure(ngp_nerf_trainer* t, uint32_t i, const float* rgb);
 int ngp_nerf_trainer_exposure_optimizer_state(const ngp_nerf_trainer* t, uint32_t i, ngp_adam_state* out);
+
+/* ---- HDR training images (EImageDataType: image_data_type per image, read_rgba) ------------------- */
+/* The reference's values (common.h:123-128). BYTE: RGBA8, sRGB with straight alpha, 4 bytes a texel, what
+ * ngp_nerf_dataset_create takes. HALF: four fp16, 8 bytes. FLOAT: four fp32, 16 bytes. Half and Float texels are
+ * linear, premultiplied RGBA in image order, and the loss pass uses them as they are (no sRGB decode, no alpha
+ * multiply, so radiance above 1 survives); the sampler drops a ray whose texel's red is < 0, which for Byte is the
+ * 0x00FF00FF texel. */
+#define NGP_IMAGE_BYTE 1
+#define NGP_IMAGE_HALF 2
+#define NGP_IMAGE_FLOAT 3
+/* ngp_nerf_dataset_create with a type per image: pixels_host[i] is HOST memory [height][width] texels of
+ * image_types[i]. With every type BYTE this is ngp_nerf_dataset_create (the same bytes on the device, the same
+ * kernels). ngp_nerf_generate_training_samples* and ngp_nerf_compute_loss* read the types from the dataset; with a
+ * Half or Float image in it they launch their TEX instantiations, for which each ray's texel type is a run-time
+ * value. NULL arguments, n_images 0 or a type other than the three: NGP_INVALID before any HIP call. */
+int ngp_nerf_dataset_create_typed(uint32_t n_images, const ngp_nerf_image* images, const void* const* pixels_host,
+                                  const uint32_t* image_types, ngp_nerf_dataset** out);
+/* NerfDataset::set_training_image's colour part (nerf_loader.cu:907-1005): replaces image `image`'s texels by HOST
+ * pixels [height][width] of image_type, at the image's existing resolution, which the call cannot change (the caller
+ * passes it for checking: a width or height other than the image's is NGP_INVALID and leaves the image alone). The
+ * type may change. Waits for the device first, as ngp_nerf_dataset_set_depth does, and a trainer of this dataset
+ * discards the sampler it launched ahead (its mask decisions may have changed) before its next step. NULL arguments,
+ * an image index out of range or an unknown type: NGP_INVALID before any HIP call. */
+int ngp_nerf_dataset_set_image(ngp_nerf_dataset* ds, uint32_t image, const void* pixels_host, uint32_t image_type,
+                               uint32_t width, uint32_t height);
+/* Copies image `image`'s texels as stored to HOST memory and reports their type (image_type nullable; out_host
+ * nullable: only the type; capacity in bytes, at least width * height * the type's texel size, else NGP_INVALID). */
+int ngp_nerf_dataset_image(const ngp_nerf_dataset* ds, uint32_t image, void* out_host, uint64_t capacity, uint32_t* image_type);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

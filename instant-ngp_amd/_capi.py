@@ -290,6 +290,9 @@ SIGNATURES = {
     "ngp_nerf_renderer_set_envmap": (i32, [P, P, u32, u32]),
     "ngp_nerf_dataset_set_depth": (i32, [P, u32, P, i32, f32]),
     "ngp_nerf_dataset_depth": (i32, [P, u32, P, u64, C.POINTER(i32)]),
+    "ngp_nerf_dataset_create_typed": (i32, [u32, C.POINTER(NerfImage), C.POINTER(P), C.POINTER(u32), C.POINTER(P)]),
+    "ngp_nerf_dataset_set_image": (i32, [P, u32, P, u32, u32, u32]),
+    "ngp_nerf_dataset_image": (i32, [P, u32, P, u64, C.POINTER(u32)]),
     "ngp_nerf_compute_loss_depth": (i32, [P, C.POINTER(NerfConfig), P, u32, u32, Rng, u32, P, P, P, P, P, P, P, P, P, P,
                                           P, f32, P, u32, u32, C.POINTER(NerfErrorCdfs), P, u32, u32, u32, P, P, u64, f32,
                                           u32]),

@@ -41,6 +41,17 @@ struct Camera {          // per image, device side
 
 struct Rng { uint64_t state, inc; };  // tcnn::pcg32 state
 
+// EImageDataType (common.h:123-128) with the reference's values: Byte is RGBA8 sRGB with straight alpha (4 bytes a
+// texel), Half four fp16 and Float four fp32 (8 and 16 bytes), both linear, premultiplied RGBA
+enum ImageType : uint32_t { IMAGE_BYTE = NGP_IMAGE_BYTE, IMAGE_HALF = NGP_IMAGE_HALF, IMAGE_FLOAT = NGP_IMAGE_FLOAT };
+inline bool image_type_ok(uint32_t t) { return t >= IMAGE_BYTE && t <= IMAGE_FLOAT; }
+inline size_t image_texel_bytes(uint32_t t) { return t == IMAGE_FLOAT ? 16 : t == IMAGE_HALF ? 8 : 4; }
+// One image's texels as the kernels' TEX instantiations find them: [height][width] texels of `type` on the device
+struct ImageRef {
+	const void* data;
+	uint32_t type, pad;
+};
+
 // Host: effective camera matrix = get_xform_given_rolling_shutter(start == end, t = 0)
 // (common_device.cuh:401-408): rotation goes through glm quat_cast / slerp / normalize / mat3_cast.
 void effective_camera_matrix(const float xform[12], float out[12]);
@@ -57,6 +68,17 @@ struct Dataset {
 	std::vector<float*> depth;
 	float** d_depth = nullptr;
 	uint32_t n_depth = 0;  // images with depth
+	// Image types (NerfDataset::pixelmemory / image_data_type per image, nerf_loader.cu:907-1005). A Byte image's texels
+	// are its slot of d_pixels, which every image keeps (Camera::pixel_offset stays valid whatever the image's type
+	// becomes); a Half or Float image's are an allocation of its own, hdr[i]. d_images [n_images] {pointer, type} exists
+	// once an image has been Half or Float; while one is (n_hdr > 0) the sampler and the loss pass run their TEX
+	// instantiations, which read it. With n_hdr == 0 nothing of this is read.
+	std::vector<uint32_t> types;  // ImageType per image
+	std::vector<void*> hdr;       // per image: the Half / Float texels, or null
+	ImageRef* d_images = nullptr;
+	uint32_t n_hdr = 0;
+	uint64_t image_epoch = 0;     // bumped whenever an image's texels change: a trainer discards its prelaunched sampler
+	bool tex() const { return n_hdr > 0 && d_images != nullptr; }
 	~Dataset();
 };
 

@@ -251,9 +251,19 @@ struct RaySetup {
 	float startt, cone;
 };
 
+// read_rgba's Half and Float branches (common_device.cuh:905-912): the texel as it is stored, one 8-byte load and four
+// conversions, or one 16-byte load
+__device__ __forceinline__ f32x4 read_hdr_texel(const ImageRef& im, uint64_t idx) {
+	if (im.type == IMAGE_FLOAT) return ((const f32x4*)im.data)[idx];
+	const f16x4 h = ((const f16x4*)im.data)[idx];
+	return f32x4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
+}
+
 // CDF: the ray's pixel comes from the error map's CDFs `e` (a separate instantiation: the uniform one carries none of it)
-template <bool CDF>
-__device__ RaySetup setup_ray(const Camera* cams, const uint32_t* pixels, uint32_t n_images, const ngp_nerf_config& cfg,
+// TEX: the dataset holds a Half or Float image (Dataset::tex): `pixels` is then the image table, ImageRef [n_images],
+// and the texel is read by its image's type; otherwise it is the packed RGBA8 buffer
+template <bool CDF, bool TEX>
+__device__ RaySetup setup_ray(const Camera* cams, const void* pixels, uint32_t n_images, const ngp_nerf_config& cfg,
                               uint32_t ig, uint32_t n_rays_div, Rng rng, const Cone& cone, const ErrorCdfs& e) {
 	RaySetup r;
 	r.valid = false;
@@ -261,8 +271,18 @@ __device__ RaySetup setup_ray(const Camera* cams, const uint32_t* pixels, uint32
 	const TrainPixel px = training_pixel<CDF>(cams, n_images, cfg.snap_to_pixel_centers != 0, e, ig, n_rays_div, rng);
 	const Camera& cam = cams[px.img];
 	const float u = px.u, v = px.v;
-	const uint32_t raw = pixels[cam.pixel_offset + pixel_index(u, v, cam.width, cam.height)];
-	if (raw == 0x00FF00FFu) return r;  // masked (read_rgba returns -1)
+	if (TEX) {  // a texel whose red is < 0 is masked (testbed_nerf.cu:1430-1435); a Byte one decodes to that at 0x00FF00FF
+		const ImageRef im = ((const ImageRef*)pixels)[px.img];
+		const uint64_t idx = pixel_index(u, v, cam.width, cam.height);
+		if (im.type == IMAGE_BYTE) {
+			if (((const uint32_t*)im.data)[idx] == 0x00FF00FFu) return r;
+		} else if (read_hdr_texel(im, idx)[0] < 0.0f) {
+			return r;
+		}
+	} else {
+		const uint32_t raw = ((const uint32_t*)pixels)[cam.pixel_offset + pixel_index(u, v, cam.width, cam.height)];
+		if (raw == 0x00FF00FFu) return r;  // masked (read_rgba returns -1)
+	}
 	(void)pcg_float(rng);              // motionblur_time
 	// uv_to_ray (common_device.cuh:443-510): pinhole, then the lens undistortion
 	float dx = (u - cam.principal[0]) * (float)cam.width / cam.focal[0];
@@ -623,15 +643,15 @@ extern "C" __attribute__((visibility("default"))) int ngp_debug_math_check(int w
 
 // generate_training_samples_nerf pass 1: count the occupied steps of ray i (lane L of its group), keep their t;
 // returns the count (uniform over the group).
-template <bool CONE0, bool CDF>
-__device__ __forceinline__ uint32_t count_ray(const Camera* __restrict__ cams, const uint32_t* __restrict__ pixels, uint32_t n_images,
+template <bool CONE0, bool CDF, bool TEX>
+__device__ __forceinline__ uint32_t count_ray(const Camera* __restrict__ cams, const void* __restrict__ pixels, uint32_t n_images,
                                               const ngp_nerf_config& cfg, const SampleArgs& a, uint32_t* __restrict__ nsteps,
                                               float* __restrict__ tbuf, RayGeo* __restrict__ geo, const Cone& cone, uint32_t i,
                                               uint32_t L) {
 	constexpr uint32_t RGk = sampler_rg<CONE0>();
 	if (!CONE0 && NGP_SAMPLER_PRIO) __builtin_amdgcn_s_setprio(NGP_SAMPLER_PRIO);
 	SAMPLER_STAT(const unsigned long long ck0 = sampler_clock();)
-	const RaySetup r = setup_ray<CDF>(cams, pixels, n_images, cfg, i + a.ray_offset, a.n_rays_total_for_image_idx, a.rng, cone, a.cdfs);
+	const RaySetup r = setup_ray<CDF, TEX>(cams, pixels, n_images, cfg, i + a.ray_offset, a.n_rays_total_for_image_idx, a.rng, cone, a.cdfs);
 	SAMPLER_STAT(const unsigned long long ck1 = sampler_clock(); unsigned long long ck2 = ck1, ck_g = 0, ck_o = 0, ck_q = 0;)
 	uint32_t j = 0;
 	if (r.valid) {
@@ -823,8 +843,8 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 // The count pass, and per wave the sum of its rays' counts and the number of its rays with samples (wsum[2 w],
 // wsum[2 w + 1]): the sampler's prefix sums over rays become a scan over waves (k_sample_bscan, ~2 K values at
 // the Lego stand-in's ~32 K rays) plus an in-wave prefix in k_sample_write, instead of a scan over the rays.
-template <bool CONE0, bool CDF>
-__global__ void __launch_bounds__(256) k_sample_count(const Camera* __restrict__ cams, const uint32_t* __restrict__ pixels,
+template <bool CONE0, bool CDF, bool TEX>
+__global__ void __launch_bounds__(256) k_sample_count(const Camera* __restrict__ cams, const void* __restrict__ pixels,
                                                       uint32_t n_images, const ngp_nerf_config cfg, SampleArgs a,
                                                       uint32_t* __restrict__ nsteps, float* __restrict__ tbuf,
                                                       RayGeo* __restrict__ geo, const Cone cone, uint32_t* __restrict__ wsum) {
@@ -833,7 +853,7 @@ __global__ void __launch_bounds__(256) k_sample_count(const Camera* __restrict__
 	const uint32_t i = gid / RGk, L = gid % RGk;
 	const bool live = i < a.n_rays;  // whole rows
 	uint32_t j = 0;
-	if (live) j = count_ray<CONE0, CDF>(cams, pixels, n_images, cfg, a, nsteps, tbuf, geo, cone, i, L);
+	if (live) j = count_ray<CONE0, CDF, TEX>(cams, pixels, n_images, cfg, a, nsteps, tbuf, geo, cone, i, L);
 	const bool head = live && L == 0;
 	const uint32_t sum = wave_sum(head ? j : 0u);
 	const uint32_t nz = (uint32_t)__popcll(__ballot(head && j > 0));
@@ -1094,9 +1114,15 @@ void sample_rays(const Dataset& ds, const ngp_nerf_config& cfg, const SampleArgs
 	{
 		ProfScope ps("sample_count", s);
 		// pixels from the error map's CDFs: the count pass's other instantiation (the write pass copies what it stored)
-		auto count = cone0 ? (a.cdfs.any() ? k_sample_count<true, true> : k_sample_count<true, false>)
-		                   : (a.cdfs.any() ? k_sample_count<false, true> : k_sample_count<false, false>);
-		count<<<cone0 ? blocks0 : blocks, NGP_SAMPLER_BLOCK, 0, s>>>(cams, ds.d_pixels, ds.n_images, cfg, a, nsteps, tbuf, geo, cone, wsum);
+		auto count = cone0 ? (a.cdfs.any() ? k_sample_count<true, true, false> : k_sample_count<true, false, false>)
+		                   : (a.cdfs.any() ? k_sample_count<false, true, false> : k_sample_count<false, false, false>);
+		// a Half or Float image in the dataset: the TEX forms of the same four, reading the image table
+		const bool tex = ds.tex();
+		if (tex)
+			count = cone0 ? (a.cdfs.any() ? k_sample_count<true, true, true> : k_sample_count<true, false, true>)
+			              : (a.cdfs.any() ? k_sample_count<false, true, true> : k_sample_count<false, false, true>);
+		const void* pixels = tex ? (const void*)ds.d_images : (const void*)ds.d_pixels;
+		count<<<cone0 ? blocks0 : blocks, NGP_SAMPLER_BLOCK, 0, s>>>(cams, pixels, ds.n_images, cfg, a, nsteps, tbuf, geo, cone, wsum);
 		NGP_HIP(hipGetLastError());
 	}
 	NGP_CHECK(nw == (cone0 ? blocks0 : blocks) * (NGP_SAMPLER_BLOCK / 64) && 64 % rgk == 0, "sampler: count waves");
@@ -1152,8 +1178,10 @@ __device__ __forceinline__ float sample_depth(const float* c, const Aabb& b, flo
 // carries depth_ray += weight * distance(pos, ray_o) under rgb's stop rule; the ray's sum goes to depth_ray[i]
 // EXPO: per-image exposures are bound (LossArgs::exposure): lane ch scales the texel by 2^exposure[img][ch] and, with
 // exposure_ray_grad bound, stores the ray's dloss_by_dexposure[ch]
-template <bool CDF, bool ENV, bool DEPTH, bool EXPO>
-__global__ void __launch_bounds__(256) k_loss_pass1(const Camera* __restrict__ cams, const uint32_t* __restrict__ pixels,
+// TEX: the dataset holds a Half or Float image (Dataset::tex): `pixels` is the image table, and a Half or Float texel
+// is the target as it stands, linear and premultiplied: no sRGB decode, no alpha multiply (read_rgba)
+template <bool CDF, bool ENV, bool DEPTH, bool EXPO, bool TEX>
+__global__ void __launch_bounds__(256) k_loss_pass1(const Camera* __restrict__ cams, const void* __restrict__ pixels,
                                                     uint32_t n_images, const ngp_nerf_config cfg, LossArgs a,
                                                     uint32_t* __restrict__ craw, LossRay* __restrict__ lr,
                                                     float* __restrict__ depth_ray) {
@@ -1192,8 +1220,18 @@ __global__ void __launch_bounds__(256) k_loss_pass1(const Camera* __restrict__ c
 	float bg[3] = {cfg.background_color[0], cfg.background_color[1], cfg.background_color[2]};
 	if (cfg.random_bg_color) { bg[0] = pcg_float(rng); bg[1] = pcg_float(rng); bg[2] = pcg_float(rng); }
 	float bgc = srgb_to_linear(ch == 0 ? bg[0] : ch == 1 ? bg[1] : bg[2]);
-	// read_rgba, Byte images (common_device.cuh:885-904)
-	const uint32_t raw = pixels[cam.pixel_offset + pixel_index(u, v, cam.width, cam.height)];
+	// read_rgba (common_device.cuh:885-913): Byte images, or with TEX the image's own type
+	uint32_t raw = 0, tex_type = IMAGE_BYTE;
+	f32x4 hdr = {0.f, 0.f, 0.f, 0.f};
+	if (TEX) {
+		const ImageRef im = ((const ImageRef*)pixels)[img];
+		const uint64_t idx = pixel_index(u, v, cam.width, cam.height);
+		tex_type = im.type;
+		if (tex_type == IMAGE_BYTE) raw = ((const uint32_t*)im.data)[idx];
+		else hdr = read_hdr_texel(im, idx);
+	} else {
+		raw = ((const uint32_t*)pixels)[cam.pixel_offset + pixel_index(u, v, cam.width, cam.height)];
+	}
 	// the environment map's four texels in the ray's direction, loaded here for the same reason
 	EnvmapTap tap;
 	f32x4 e0, e1, e2, e3;
@@ -1315,7 +1353,8 @@ __global__ void __launch_bounds__(256) k_loss_pass1(const Camera* __restrict__ c
 	}
 	// channel ch of the target, the background and the loss (every lane of the row holds rr, rg, rb, t, cn)
 	float texc, tex3;
-	if (raw == 0x00FF00FFu) { texc = tex3 = -1.0f; }
+	if (TEX && tex_type != IMAGE_BYTE) { texc = ch == 0 ? hdr[0] : ch == 1 ? hdr[1] : hdr[2]; tex3 = hdr[3]; }
+	else if (raw == 0x00FF00FFu) { texc = tex3 = -1.0f; }
 	else {
 		const float alpha = (float)(raw >> 24) * (1.0f / 255.0f);
 		texc = srgb_to_linear((float)((raw >> (8 * ch)) & 0xff) * (1.0f / 255.0f)) * alpha;
@@ -1606,6 +1645,17 @@ size_t loss_tmp_f32(uint32_t n_rays) { return (size_t)n_rays * (sizeof(LossRay) 
 // depth_ray, one float per ray after the LossRay array: LossRay and the default path's scratch keep their size
 size_t loss_tmp_f32_depth(uint32_t n_rays) { return loss_tmp_f32(n_rays) + n_rays; }
 size_t loss_tmp_f32_exposure(uint32_t n_rays) { return (size_t)n_rays * 3; }
+// k_loss_pass1's TEX instantiations by their four other switches
+using LossPass1 = void (*)(const Camera*, const void*, uint32_t, const ngp_nerf_config, LossArgs, uint32_t*, LossRay*, float*);
+static LossPass1 loss_pass1_tex(bool cdf, bool env, bool depth, bool expo) {
+#define NGP_P1(E, D, V) k_loss_pass1<false, V, D, E, true>, k_loss_pass1<true, V, D, E, true>
+	static const LossPass1 k[16] = {NGP_P1(false, false, false), NGP_P1(false, false, true), NGP_P1(false, true, false),
+	                                NGP_P1(false, true, true),   NGP_P1(true, false, false), NGP_P1(true, false, true),
+	                                NGP_P1(true, true, false),   NGP_P1(true, true, true)};
+#undef NGP_P1
+	return k[(cdf ? 1 : 0) | (env ? 2 : 0) | (depth ? 4 : 0) | (expo ? 8 : 0)];
+}
+
 bool loss_depth_on(const Dataset& ds, const LossArgs& a) { return a.depth_lambda > 0.0f && ds.n_depth > 0 && ds.d_depth != nullptr; }
 
 void compute_loss(const Dataset& ds, const ngp_nerf_config& cfg, const LossArgs& a, uint32_t* tmp, float* tmpf, hipStream_t s) {
@@ -1626,23 +1676,28 @@ void compute_loss(const Dataset& ds, const ngp_nerf_config& cfg, const LossArgs&
 		NGP_CHECK(!a.envmap || (a.env_w > 0 && a.env_h > 0 && a.rays), "compute_loss: environment map without a resolution or rays");
 		NGP_CHECK(!a.env_acc || a.envmap, "compute_loss: an environment map gradient needs the map");
 		NGP_CHECK(!a.exposure_ray_grad || a.exposure, "compute_loss: an exposure gradient needs the exposures");
-		auto pass1 = a.envmap ? (a.cdfs.any() ? k_loss_pass1<true, true, false, false> : k_loss_pass1<false, true, false, false>)
-		                      : (a.cdfs.any() ? k_loss_pass1<true, false, false, false> : k_loss_pass1<false, false, false, false>);
+		auto pass1 = a.envmap ? (a.cdfs.any() ? k_loss_pass1<true, true, false, false, false> : k_loss_pass1<false, true, false, false, false>)
+		                      : (a.cdfs.any() ? k_loss_pass1<true, false, false, false, false> : k_loss_pass1<false, false, false, false, false>);
 		if (depth_on) {
 			NGP_CHECK(a.rays, "compute_loss: depth supervision needs the rays");
 			NGP_CHECK(a.depth_loss_type <= LOSS_RELL2, "compute_loss: unknown depth loss");
-			pass1 = a.envmap ? (a.cdfs.any() ? k_loss_pass1<true, true, true, false> : k_loss_pass1<false, true, true, false>)
-			                 : (a.cdfs.any() ? k_loss_pass1<true, false, true, false> : k_loss_pass1<false, false, true, false>);
+			pass1 = a.envmap ? (a.cdfs.any() ? k_loss_pass1<true, true, true, false, false> : k_loss_pass1<false, true, true, false, false>)
+			                 : (a.cdfs.any() ? k_loss_pass1<true, false, true, false, false> : k_loss_pass1<false, false, true, false, false>);
 		}
 		if (a.exposure) {  // the exposure forms of the same eight
 			if (depth_on)
-				pass1 = a.envmap ? (a.cdfs.any() ? k_loss_pass1<true, true, true, true> : k_loss_pass1<false, true, true, true>)
-				                 : (a.cdfs.any() ? k_loss_pass1<true, false, true, true> : k_loss_pass1<false, false, true, true>);
+				pass1 = a.envmap ? (a.cdfs.any() ? k_loss_pass1<true, true, true, true, false> : k_loss_pass1<false, true, true, true, false>)
+				                 : (a.cdfs.any() ? k_loss_pass1<true, false, true, true, false> : k_loss_pass1<false, false, true, true, false>);
 			else
-				pass1 = a.envmap ? (a.cdfs.any() ? k_loss_pass1<true, true, false, true> : k_loss_pass1<false, true, false, true>)
-				                 : (a.cdfs.any() ? k_loss_pass1<true, false, false, true> : k_loss_pass1<false, false, false, true>);
+				pass1 = a.envmap ? (a.cdfs.any() ? k_loss_pass1<true, true, false, true, false> : k_loss_pass1<false, true, false, true, false>)
+				                 : (a.cdfs.any() ? k_loss_pass1<true, false, false, true, false> : k_loss_pass1<false, false, false, true, false>);
 		}
-		pass1<<<b1, 256, 0, s>>>(ds.d_cams, ds.d_pixels, ds.n_images, cfg, a, craw, lr, depth_ray);
+		// a Half or Float image in the dataset: the TEX form of whichever of the sixteen was chosen, reading the image
+		// table instead of the packed buffer. A Byte-only dataset keeps the choice made above.
+		const bool tex = ds.tex();
+		if (tex) pass1 = loss_pass1_tex(a.cdfs.any(), a.envmap != nullptr, depth_on, a.exposure != nullptr);
+		const void* pixels = tex ? (const void*)ds.d_images : (const void*)ds.d_pixels;
+		pass1<<<b1, 256, 0, s>>>(ds.d_cams, pixels, ds.n_images, cfg, a, craw, lr, depth_ray);
 		NGP_HIP(hipGetLastError());
 	}
 	{
@@ -2639,6 +2694,8 @@ void effective_camera_matrix(const float xf[12], float out[12]) {
 
 Dataset::~Dataset() {
 	for (float* d : depth) if (d) (void)hipFree(d);
+	for (void* d : hdr) if (d) (void)hipFree(d);
+	if (d_images) (void)hipFree(d_images);
 	if (d_depth) (void)hipFree(d_depth);
 	if (d_cams) (void)hipFree(d_cams);
 	if (d_pixels) (void)hipFree(d_pixels);

@@ -61,6 +61,81 @@ static LossArgs public_loss_args(uint32_t n_rays, uint32_t n_rays_total, ngp_rng
 	return a;
 }
 
+// The dataset's image table after an image's type or pointer changed: {pointer, type} per image, a Byte image's pointer
+// being its slot of the packed buffer. Allocated once an image is Half or Float.
+static void upload_image_table(Dataset& ds) {
+	if (!ds.d_images && ds.n_hdr == 0) return;
+	std::vector<ImageRef> refs(ds.n_images);
+	for (uint32_t i = 0; i < ds.n_images; ++i) {
+		const bool byte = ds.types[i] == IMAGE_BYTE;
+		refs[i] = ImageRef{byte ? (const void*)(ds.d_pixels + ds.cams[i].pixel_offset) : (const void*)ds.hdr[i], ds.types[i], 0u};
+	}
+	if (!ds.d_images) NGP_HIP(hipMalloc(&ds.d_images, ds.n_images * sizeof(ImageRef)));
+	NGP_HIP(hipMemcpy(ds.d_images, refs.data(), ds.n_images * sizeof(ImageRef), hipMemcpyHostToDevice));
+}
+
+// Image i's texels from host memory, as `type`: into its slot of the packed buffer, or into an allocation of its own
+static void store_image(Dataset& ds, uint32_t i, const void* host, uint32_t type) {
+	const size_t n = (size_t)ds.cams[i].width * ds.cams[i].height, bytes = n * image_texel_bytes(type);
+	if (type == IMAGE_BYTE) {
+		NGP_HIP(hipMemcpy(ds.d_pixels + ds.cams[i].pixel_offset, host, bytes, hipMemcpyHostToDevice));
+		if (ds.hdr[i]) { NGP_HIP(hipFree(ds.hdr[i])); ds.hdr[i] = nullptr; --ds.n_hdr; }
+	} else {
+		void* p = nullptr;
+		NGP_HIP(hipMalloc(&p, bytes));
+		if (hipMemcpy(p, host, bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(p); throw Error("nerf dataset: image upload failed"); }
+		if (ds.hdr[i]) NGP_HIP(hipFree(ds.hdr[i]));
+		else ++ds.n_hdr;
+		ds.hdr[i] = p;
+	}
+	ds.types[i] = type;
+}
+
+// ngp_nerf_dataset_create and _create_typed (types null: every image Byte)
+static int ngp_nerf_dataset_create_typed_impl(uint32_t n_images, const ngp_nerf_image* images, const void* const* pixels,
+                                              const uint32_t* types, ngp_nerf_dataset** out) {
+	if (!out || !images || !pixels || n_images == 0) return NGP_INVALID;
+	NERF_TRY({
+		auto d = std::make_unique<ngp_nerf_dataset>();
+		d->ds.n_images = n_images;
+		uint64_t total = 0;
+		std::vector<Camera> cams(n_images);
+		for (uint32_t i = 0; i < n_images; ++i) {
+			const ngp_nerf_image& im = images[i];
+			Camera& c = cams[i];
+			c.width = im.width; c.height = im.height;
+			c.focal[0] = im.focal_length[0]; c.focal[1] = im.focal_length[1];
+			c.principal[0] = im.principal_point[0]; c.principal[1] = im.principal_point[1];
+			NGP_CHECK(im.lens_mode <= LENS_OPENCV_FISHEYE, "nerf dataset: unsupported lens mode");
+			c.lens_mode = im.lens_mode;
+			for (int k = 0; k < 4; ++k) c.lens[k] = im.lens_params[k];
+			effective_camera_matrix(im.xform, c.m);
+			c.pixel_offset = total;
+			total += (uint64_t)im.width * im.height;
+		}
+		NGP_HIP(hipMalloc(&d->ds.d_pixels, total * 4 + 12 * 4 * n_images));
+		d->ds.cams = cams;
+		d->ds.types.assign(n_images, IMAGE_BYTE);
+		d->ds.hdr.assign(n_images, nullptr);
+		for (uint32_t i = 0; i < n_images; ++i) {
+			NGP_CHECK(pixels[i] != nullptr, "nerf dataset: an image without pixels");
+			const uint32_t type = types ? types[i] : (uint32_t)IMAGE_BYTE;
+			// a Half or Float image's slot of the packed buffer is never read; zeroed, so that its bytes are defined
+			if (type != IMAGE_BYTE) NGP_HIP(hipMemset(d->ds.d_pixels + cams[i].pixel_offset, 0, (size_t)images[i].width * images[i].height * 4));
+			store_image(d->ds, i, pixels[i], type);
+		}
+		upload_image_table(d->ds);
+		// raw (start) transforms after the pixels, for mark_untrained_density_grid
+		std::vector<float> raw(12 * n_images);
+		for (uint32_t i = 0; i < n_images; ++i) memcpy(&raw[12 * i], images[i].xform, 48);
+		NGP_HIP(hipMemcpy(d->ds.d_pixels + total, raw.data(), raw.size() * 4, hipMemcpyHostToDevice));
+		d->ds.xforms = raw;
+		NGP_HIP(hipMalloc(&d->ds.d_cams, n_images * sizeof(Camera)));
+		NGP_HIP(hipMemcpy(d->ds.d_cams, cams.data(), n_images * sizeof(Camera), hipMemcpyHostToDevice));
+		*out = d.release();
+	});
+}
+
 struct ngp_nerf_renderer {
 	Buf pay0, pay1, payh, rgba0, rgba1, rgbah, coords, out, frame, counters;
 	const float* envmap = nullptr;        // ngp_nerf_renderer_set_envmap (the caller's device memory)
@@ -96,39 +171,41 @@ int ngp_nerf_default_config(float aabb_scale, ngp_nerf_config* o) {
 }
 
 int ngp_nerf_dataset_create(uint32_t n_images, const ngp_nerf_image* images, const void* const* rgba8, ngp_nerf_dataset** out) {
-	if (!out || !images || !rgba8 || n_images == 0) return NGP_INVALID;
+	return ngp_nerf_dataset_create_typed_impl(n_images, images, rgba8, nullptr, out);
+}
+
+int ngp_nerf_dataset_create_typed(uint32_t n_images, const ngp_nerf_image* images, const void* const* pixels_host,
+                                  const uint32_t* image_types, ngp_nerf_dataset** out) {
+	if (!image_types || !pixels_host) return NGP_INVALID;
+	for (uint32_t i = 0; i < n_images; ++i)
+		if (!image_type_ok(image_types[i]) || !pixels_host[i]) return NGP_INVALID;
+	return ngp_nerf_dataset_create_typed_impl(n_images, images, pixels_host, image_types, out);
+}
+
+int ngp_nerf_dataset_set_image(ngp_nerf_dataset* d, uint32_t image, const void* pixels_host, uint32_t image_type, uint32_t width,
+                               uint32_t height) {
+	if (!d || !pixels_host || image >= d->ds.n_images || !image_type_ok(image_type)) return NGP_INVALID;
+	if (width != d->ds.cams[image].width || height != d->ds.cams[image].height) return NGP_INVALID;  // resizing is not built
 	NERF_TRY({
-		auto d = std::make_unique<ngp_nerf_dataset>();
-		d->ds.n_images = n_images;
-		uint64_t total = 0;
-		std::vector<Camera> cams(n_images);
-		for (uint32_t i = 0; i < n_images; ++i) {
-			const ngp_nerf_image& im = images[i];
-			Camera& c = cams[i];
-			c.width = im.width; c.height = im.height;
-			c.focal[0] = im.focal_length[0]; c.focal[1] = im.focal_length[1];
-			c.principal[0] = im.principal_point[0]; c.principal[1] = im.principal_point[1];
-			NGP_CHECK(im.lens_mode <= LENS_OPENCV_FISHEYE, "nerf dataset: unsupported lens mode");
-			c.lens_mode = im.lens_mode;
-			for (int k = 0; k < 4; ++k) c.lens[k] = im.lens_params[k];
-			effective_camera_matrix(im.xform, c.m);
-			c.pixel_offset = total;
-			total += (uint64_t)im.width * im.height;
-		}
-		NGP_HIP(hipMalloc(&d->ds.d_pixels, total * 4 + 12 * 4 * n_images));
-		for (uint32_t i = 0; i < n_images; ++i)
-			NGP_HIP(hipMemcpy(d->ds.d_pixels + cams[i].pixel_offset, rgba8[i], (size_t)images[i].width * images[i].height * 4,
-			                  hipMemcpyHostToDevice));
-		// raw (start) transforms after the pixels, for mark_untrained_density_grid
-		std::vector<float> raw(12 * n_images);
-		for (uint32_t i = 0; i < n_images; ++i) memcpy(&raw[12 * i], images[i].xform, 48);
-		NGP_HIP(hipMemcpy(d->ds.d_pixels + total, raw.data(), raw.size() * 4, hipMemcpyHostToDevice));
-		d->ds.xforms = raw;
-		NGP_HIP(hipMalloc(&d->ds.d_cams, n_images * sizeof(Camera)));
-		NGP_HIP(hipMemcpy(d->ds.d_cams, cams.data(), n_images * sizeof(Camera), hipMemcpyHostToDevice));
-		d->ds.cams = cams;
-		*out = d.release();
+		Dataset& ds = d->ds;
+		NGP_HIP(hipDeviceSynchronize());  // no sampler or loss pass may still be reading the image or the table
+		const bool table_changes = image_type != IMAGE_BYTE || ds.types[image] != IMAGE_BYTE;
+		store_image(ds, image, pixels_host, image_type);
+		if (table_changes) upload_image_table(ds);  // Byte over Byte rewrites the packed buffer in place
+		++ds.image_epoch;
 	});
+}
+
+int ngp_nerf_dataset_image(const ngp_nerf_dataset* d, uint32_t image, void* out_host, uint64_t cap, uint32_t* image_type) {
+	if (!d || image >= d->ds.n_images) return NGP_INVALID;
+	const Dataset& ds = d->ds;
+	const uint32_t type = ds.types[image];
+	const size_t bytes = (size_t)ds.cams[image].width * ds.cams[image].height * image_texel_bytes(type);
+	if (out_host && cap < bytes) return NGP_INVALID;
+	if (image_type) *image_type = type;
+	if (!out_host) return NGP_OK;
+	const void* src = type == IMAGE_BYTE ? (const void*)(ds.d_pixels + ds.cams[image].pixel_offset) : (const void*)ds.hdr[image];
+	NERF_TRY(NGP_HIP(hipMemcpy(out_host, src, bytes, hipMemcpyDeviceToHost)));
 }
 
 void ngp_nerf_dataset_destroy(ngp_nerf_dataset* d) { delete d; }

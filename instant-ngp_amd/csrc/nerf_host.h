@@ -172,6 +172,9 @@ struct ngp_nerf_trainer {
 	bool pipeline = true;                // ngp_nerf_trainer_set_pipeline
 	bool prelaunched = false;
 	uint32_t pre_R = 0, pre_max_inference = 0;
+	// Dataset::image_epoch the last step saw: ngp_nerf_dataset_set_image may have changed which texels are masked, so
+	// the next step discards a sampler launched before it. (The captured training pass holds no dataset pointer.)
+	uint64_t data_epoch = 0;
 	hipStream_t sample_stream = nullptr;
 	// prelaunched sampler -> this step's inference (the consumer is usually already waiting: by value), and the step's
 	// release of the sample buffers -> the next sampler (long done when the host launches that sampler: by event; the

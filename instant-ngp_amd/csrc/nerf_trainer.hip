@@ -1142,6 +1142,10 @@ int ngp_nerf_train_step(ngp_nerf_trainer* t, void* stream, int get_loss, ngp_ner
 	NERF_TRY({
 		hipStream_t s = step_stream(t, stream);
 		Step c;
+		if (t->data_epoch != t->data->ds.image_epoch) {  // an image was replaced (ngp_nerf_dataset_set_image)
+			t->drain();
+			t->data_epoch = t->data->ds.image_epoch;
+		}
 		c.pre = t->prelaunched;
 		c.get_loss = get_loss != 0;
 		t->prelaunched = false;

@@ -53,14 +53,20 @@ void load_training_data(Testbed& tb, const std::string& path) {
 		py::list images = d.attr("images"), pixels = d.attr("rgba8");
 		py::object ctypes = py::module_::import("ctypes");
 		std::vector<ngp_nerf_image> meta(py::len(images));
-		std::vector<py::array_t<uint8_t, py::array::c_style | py::array::forcecast>> keep;
+		// an EXR frame's pixels come as float16 (Half), every other frame's as RGBA8
+		std::vector<py::array> keep;
 		std::vector<const void*> ptrs;
+		std::vector<uint32_t> types;
 		for (size_t i = 0; i < meta.size(); ++i) {
 			py::object im = images[i];
 			if (ctypes.attr("sizeof")(im).cast<size_t>() != sizeof(ngp_nerf_image))
 				throw std::runtime_error("load_training_data: NerfImage layout differs from ngp_nerf_image");
 			std::memcpy(&meta[i], (const void*)ctypes.attr("addressof")(im).cast<uintptr_t>(), sizeof(ngp_nerf_image));
-			keep.emplace_back(pixels[i]);
+			py::array px = py::array::ensure(pixels[i]);
+			const bool half = px && px.dtype().kind() == 'f' && px.dtype().itemsize() == 2;
+			if (half) keep.emplace_back(py::array::ensure(px, py::array::c_style));
+			else keep.emplace_back(py::array_t<uint8_t, py::array::c_style | py::array::forcecast>(pixels[i]));
+			types.push_back(half ? NGP_IMAGE_HALF : NGP_IMAGE_BYTE);
 			if (keep.back().ndim() != 3 || (uint32_t)keep.back().shape(0) != meta[i].height ||
 			    (uint32_t)keep.back().shape(1) != meta[i].width || keep.back().shape(2) != 4)
 				throw std::runtime_error("load_training_data: image buffer shape does not match its metadata");
@@ -96,7 +102,7 @@ void load_training_data(Testbed& tb, const std::string& path) {
 			}
 		}
 		py::gil_scoped_release nogil;
-		tb.load_nerf(meta, ptrs, aabb_scale, scale, offset);
+		tb.load_nerf(meta, ptrs, aabb_scale, scale, offset, &types);
 		if (has_envmap) tb.set_dataset_envmap((uint32_t)envmap.shape(1), (uint32_t)envmap.shape(0), envmap.data());
 		for (size_t i = 0; i < meta.size(); ++i)
 			if (has_depth[i]) tb.set_image_depth((uint32_t)i, depth[i].data(), 0, depth_scale[i]);
@@ -443,6 +449,27 @@ PYBIND11_MODULE(pyngp, m) {
 		     py::arg("frame_idx"), py::arg("img") = py::none(), py::arg("depth_img") = py::none(), py::arg("depth_scale") = 1.0f,
 		     "The depth part of Testbed.nerf.training.set_image: depth_img [H, W] (uint16 or float32) times depth_scale "
 		     "becomes the image's depth; None: zeros (with a negative depth_scale: no depth). img must be None.")
+		.def("set_image_pixels",
+		     [](NerfTrainingView& v, int frame_idx, py::array img) {
+			     if (frame_idx < 0) throw std::runtime_error("set_image_pixels: no such training view");
+			     if (!img.dtype().is(py::dtype::of<float>()) || img.ndim() != 3 || img.shape(2) != 4)
+				     throw std::runtime_error("set_image_pixels: img is a float32 [H, W, 4] array");
+			     py::array_t<float, py::array::c_style | py::array::forcecast> f(img);
+			     v.t->set_image_pixels((uint32_t)frame_idx, f.data(), (uint32_t)f.shape(1), (uint32_t)f.shape(0));
+		     },
+		     py::arg("frame_idx"), py::arg("img"),
+		     "Engine extension: replaces a training view's colours by a float32 [H, W, 4] image (linear, premultiplied RGBA, "
+		     "stored as it is) of the view's resolution.")
+		.def("image", [](NerfTrainingView& v, int frame_idx) -> py::object {
+			     if (frame_idx < 0) throw std::runtime_error("image: no such training view");
+			     uint32_t type = 0;
+			     const std::vector<uint8_t> d = v.t->image_pixels((uint32_t)frame_idx, &type);
+			     const ngp_nerf_image& im = v.t->nerf_images().at((size_t)frame_idx);
+			     const char* dt = type == NGP_IMAGE_FLOAT ? "float32" : type == NGP_IMAGE_HALF ? "float16" : "uint8";
+			     py::array out(py::dtype(dt), std::vector<py::ssize_t>{(py::ssize_t)im.height, (py::ssize_t)im.width, 4});
+			     std::memcpy(out.mutable_data(), d.data(), d.size());
+			     return std::move(out);
+		     }, py::arg("frame_idx"), "Engine extension: a training view's texels as stored: [H, W, 4] uint8, float16 or float32.")
 		.def("depth_image", [](NerfTrainingView& v, int frame_idx) -> py::object {
 			     if (frame_idx < 0) throw std::runtime_error("depth_image: no such training view");
 			     const std::vector<float> d = v.t->image_depth((uint32_t)frame_idx);
@@ -522,6 +549,7 @@ PYBIND11_MODULE(pyngp, m) {
 	py::class_<NerfDatasetView>(m, "NerfDataset")
 		.def_property_readonly("n_images", [](NerfDatasetView& v) { return v.t->n_training_views(); })
 		.def_property_readonly("aabb_scale", [](NerfDatasetView& v) { return v.t->aabb_scale(); })
+		.def_property_readonly("is_hdr", [](NerfDatasetView& v) { return v.t->nerf_is_hdr(); })
 		.def_property_readonly("metadata", [](NerfDatasetView& v) {
 			py::list out;
 			for (const ngp_nerf_image& im : v.t->nerf_images()) {

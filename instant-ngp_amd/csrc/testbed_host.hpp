@@ -247,20 +247,30 @@ public:
 	std::string network_config() const { return m_network_config.dump(); }
 
 	// ---- training data ------------------------------------------------------------------------------
-	// Testbed::load_nerf + load_nerf_post (testbed_nerf.cu:3093-3109): decoded images (RGBA8 sRGB) with their
-	// metadata after nerf_matrix_to_ngp, and the dataset's aabb_scale
+	// Testbed::load_nerf + load_nerf_post (testbed_nerf.cu:3093-3109): decoded images (RGBA8 sRGB, or with `types` an
+	// NGP_IMAGE_* type per image: EXR frames come as Half) with their metadata after nerf_matrix_to_ngp, and the
+	// dataset's aabb_scale
 	void load_nerf(const std::vector<ngp_nerf_image>& images, const std::vector<const void*>& rgba8, float aabb_scale,
-	               float dataset_scale = 1.0f, const float* dataset_offset = nullptr) {
+	               float dataset_scale = 1.0f, const float* dataset_offset = nullptr, const std::vector<uint32_t>* types = nullptr) {
 		set_mode(ETestbedMode::Nerf);
 		if (images.empty() || images.size() != rgba8.size()) throw std::runtime_error("load_nerf: one RGBA8 buffer per image");
+		if (types && types->size() != images.size()) throw std::runtime_error("load_nerf: one image type per image");
 		free_network();
 		free_data();
-		check(ngp_nerf_dataset_create((uint32_t)images.size(), images.data(), rgba8.data(), &m_nerf_dataset), "ngp_nerf_dataset_create");
+		bool hdr = false;
+		if (types) for (uint32_t t : *types) hdr = hdr || t != NGP_IMAGE_BYTE;
+		if (hdr)
+			check(ngp_nerf_dataset_create_typed((uint32_t)images.size(), images.data(), rgba8.data(), types->data(), &m_nerf_dataset),
+			      "ngp_nerf_dataset_create_typed");
+		else
+			check(ngp_nerf_dataset_create((uint32_t)images.size(), images.data(), rgba8.data(), &m_nerf_dataset), "ngp_nerf_dataset_create");
+		m_nerf_is_hdr = hdr;  // NerfDataset::is_hdr: set by the loader, not changed by set_image_pixels (nerf_loader.cu:553)
 		m_nerf_images = images;
 		m_aabb_scale = aabb_scale;
 		m_dataset_scale = dataset_scale;  // NerfDataset::scale (nerf_loader.cu:388): Depth renders in its units
 		for (int d = 0; d < 3; ++d) m_dataset_offset[d] = dataset_offset ? dataset_offset[d] : 0.5f;  // NerfDataset::offset
 		check(ngp_nerf_default_config(aabb_scale, &m_nerf_cfg), "ngp_nerf_default_config");
+		if (m_nerf_is_hdr) m_nerf_cfg.rgb_activation = 3;  // load_nerf_post (testbed_nerf.cu:3027): Exponential for an HDR dataset
 		m_training_data_available = true;
 		set_camera_to_training_view(0);
 	}
@@ -815,6 +825,25 @@ public:
 		if (frame_idx >= m_nerf_images.size()) throw std::runtime_error("set_image: no such training view");
 		check(ngp_nerf_dataset_set_depth(m_nerf_dataset, frame_idx, pixels, dtype, depth_scale), "ngp_nerf_dataset_set_depth");
 	}
+	bool nerf_is_hdr() const { return m_nerf_is_hdr; }
+	// Engine extension: a training view's colours replaced by a float32 RGBA image [height][width][4] (linear,
+	// premultiplied; stored as Float) at the view's resolution
+	void set_image_pixels(uint32_t frame_idx, const float* rgba, uint32_t width, uint32_t height) {
+		if (!m_nerf_dataset) throw std::runtime_error("set_image_pixels: no NeRF training data loaded");
+		if (frame_idx >= m_nerf_images.size()) throw std::runtime_error("set_image_pixels: no such training view");
+		if (width != m_nerf_images[frame_idx].width || height != m_nerf_images[frame_idx].height)
+			throw std::runtime_error("set_image_pixels: the image has the wrong resolution (resizing a training view is not supported)");
+		check(ngp_nerf_dataset_set_image(m_nerf_dataset, frame_idx, rgba, NGP_IMAGE_FLOAT, width, height), "ngp_nerf_dataset_set_image");
+	}
+	// a training view's texels as stored, and their NGP_IMAGE_* type
+	std::vector<uint8_t> image_pixels(uint32_t frame_idx, uint32_t* type) const {
+		if (!m_nerf_dataset || frame_idx >= m_nerf_images.size()) throw std::runtime_error("image: no such training view");
+		check(ngp_nerf_dataset_image(m_nerf_dataset, frame_idx, nullptr, 0, type), "ngp_nerf_dataset_image");
+		const size_t texel = *type == NGP_IMAGE_FLOAT ? 16 : *type == NGP_IMAGE_HALF ? 8 : 4;
+		std::vector<uint8_t> out((size_t)m_nerf_images[frame_idx].width * m_nerf_images[frame_idx].height * texel);
+		check(ngp_nerf_dataset_image(m_nerf_dataset, frame_idx, out.data(), out.size(), type), "ngp_nerf_dataset_image");
+		return out;
+	}
 	// the stored depth image of a training view (empty: none)
 	std::vector<float> image_depth(uint32_t frame_idx) const {
 		if (!m_nerf_dataset || frame_idx >= m_nerf_images.size()) throw std::runtime_error("depth: no such training view");
@@ -1066,6 +1095,7 @@ private:
 	ngp_trainer* m_trainer = nullptr;
 	// NeRF
 	ngp_nerf_dataset* m_nerf_dataset = nullptr;
+	bool m_nerf_is_hdr = false;
 	ngp_nerf_trainer* m_nerf_trainer = nullptr;
 	ngp_nerf_camera_training m_cam_training{0, 16, 1e-4f, 1e-3f};  // testbed.h:716-785 defaults
 	bool m_sample_focal_plane_by_error = false, m_sample_image_by_error = false;  // testbed.h:733-734

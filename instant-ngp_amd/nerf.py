@@ -83,25 +83,73 @@ def make_image(width, height, xform12, focal=None, camera_angle_x=None, principa
     return im
 
 
-class NerfDataset:
-    """Training images (RGBA8 sRGB, EImageDataType::Byte) + cameras on the device."""
+IMAGE_BYTE, IMAGE_HALF, IMAGE_FLOAT = 1, 2, 3  # EImageDataType (NGP_IMAGE_*)
+_IMAGE_TYPE = {np.dtype(np.uint8): IMAGE_BYTE, np.dtype(np.float16): IMAGE_HALF, np.dtype(np.float32): IMAGE_FLOAT}
+_IMAGE_DTYPE = {IMAGE_BYTE: np.uint8, IMAGE_HALF: np.float16, IMAGE_FLOAT: np.float32}
 
-    def __init__(self, images, rgba8):
-        if len(images) != len(rgba8) or not images:
-            raise ValueError("need one RGBA8 array per image")
+
+def _image_array(im, px):
+    """px as a contiguous [h, w, 4] array of one of the three texel types, and that type."""
+    px = np.asarray(px)
+    if px.dtype not in _IMAGE_TYPE:
+        raise ValueError(f"training image: uint8, float16 or float32, not {px.dtype}")
+    if px.shape != (im.height, im.width, 4):
+        raise ValueError(f"image buffer shape {px.shape} != {(im.height, im.width, 4)}")
+    return np.ascontiguousarray(px), _IMAGE_TYPE[px.dtype]
+
+
+class NerfDataset:
+    """Training images + cameras on the device. Each image is a [h, w, 4] array: uint8 is RGBA8 sRGB with straight alpha
+    (EImageDataType::Byte), float16 and float32 are linear premultiplied RGBA (Half, Float) which the loss pass uses as
+    they are; the three may be mixed. A red < 0 in a Half or Float texel masks the pixel, as 0x00FF00FF does in a Byte
+    one."""
+
+    def __init__(self, images, pixels):
+        if len(images) != len(pixels) or not images:
+            raise ValueError("need one RGBA array per image")
         arr = (NerfImage * len(images))(*images)
         self.images = list(images)
-        bufs = []
-        for im, px in zip(images, rgba8):
-            px = np.ascontiguousarray(px, dtype=np.uint8)
-            if px.shape != (im.height, im.width, 4):
-                raise ValueError(f"image buffer shape {px.shape} != {(im.height, im.width, 4)}")
+        if all(np.asarray(px).dtype not in (np.float16, np.float32) for px in pixels):
+            pixels = [np.ascontiguousarray(px, dtype=np.uint8) for px in pixels]  # as before: anything castable to bytes
+        bufs, types = [], []
+        for im, px in zip(images, pixels):
+            px, t = _image_array(im, px)
             bufs.append(px)
-        self._host = bufs
+            types.append(t)
         ptrs = (C.c_void_p * len(bufs))(*[b.ctypes.data for b in bufs])
         h = C.c_void_p()
-        check(lib().ngp_nerf_dataset_create(len(images), arr, ptrs, C.byref(h)))
+        if all(t == IMAGE_BYTE for t in types):
+            check(lib().ngp_nerf_dataset_create(len(images), arr, ptrs, C.byref(h)))
+        else:
+            check(lib().ngp_nerf_dataset_create_typed(len(images), arr, ptrs, (C.c_uint32 * len(types))(*types), C.byref(h)))
         self.handle = h
+        self.image_types = types
+
+    @property
+    def is_hdr(self):
+        """NerfDataset::is_hdr: an image is Half or Float."""
+        return any(t != IMAGE_BYTE for t in self.image_types)
+
+    def set_image(self, i, array):
+        """Replaces image i's colours (NerfDataset::set_training_image's colour part) by a uint8, float16 or float32
+        [h, w, 4] array at the image's resolution; the type may change. Waits for the device; a trainer of this dataset
+        discards the sampler it launched ahead."""
+        if not 0 <= int(i) < len(self.images):
+            raise IndexError(f"image {i} of {len(self.images)}")
+        im = self.images[i]
+        px, t = _image_array(im, array)
+        check(lib().ngp_nerf_dataset_set_image(self.handle, int(i), px.ctypes.data, t, im.width, im.height))
+        self.image_types[i] = t
+
+    def image(self, i):
+        """Image i's texels as stored: [h, w, 4] uint8, float16 or float32."""
+        if not 0 <= int(i) < len(self.images):
+            raise IndexError(f"image {i} of {len(self.images)}")
+        im, t = self.images[i], C.c_uint32(0)
+        check(lib().ngp_nerf_dataset_image(self.handle, int(i), None, 0, C.byref(t)))
+        out = np.zeros((im.height, im.width, 4), _IMAGE_DTYPE[t.value])
+        check(lib().ngp_nerf_dataset_image(self.handle, int(i), out.ctypes.data, out.nbytes, C.byref(t)))
+        return out
 
     def __len__(self):
         return len(self.images)

@@ -2,14 +2,18 @@
 
 Host-side restatement of the reference loader `load_nerf` (src/nerf_loader.cu:260-726) for the
 formats the training path consumes: the original NeRF/instant-ngp `transforms.json` (one or more
-files), 8-bit images (PNG/JPEG/BMP... decoded to RGBA8 sRGB, EImageDataType::Byte), perspective and
+files), 8-bit images (PNG/JPEG/BMP... decoded to RGBA8 sRGB, EImageDataType::Byte), `.exr` frames (HDR: linear
+premultiplied RGBA stored as fp16, EImageDataType::Half, with `fix_premult`; nerf_loader.cu:429-430, 549-553; the two kinds
+may be mixed, and the `.alpha.` companion, the dynamic masks and `white_transparent` / `black_transparent` apply to
+the 8-bit frames only, as in the reference), perspective and
 OpenCV / OpenCV-fisheye lenses, per-frame intrinsics overrides, `scale` / `offset` / `aabb` /
 `aabb_scale`, the sharpness filter, `n_frames`, `white_transparent` / `black_transparent`,
 `<file>.alpha.<ext>` alpha images, `dynamic_mask_<name>.png` masks, the `envmap` image, and depth supervision:
 `integer_depth_scale`, `enable_depth_loading` and per-frame `depth_path` 16-bit images (nerf_loader.cu:404-422, 471,
-609-621, 711). Not handled (the loader raises): EXR/HDR images, per-pixel ray files, rolling shutter, FTheta /
+609-621, 711). Not handled (the loader raises): per-pixel ray files, rolling shutter, FTheta /
 LatLong / equirectangular lenses, Mitsuba scenes — none of the in-scope datasets use them.
-Image decoding is PIL's (the reference uses stb_image); the pixels then travel to the device
+Image decoding is PIL's (the reference uses stb_image) or, for EXR, the package's reader (exr.py; the reference uses
+tinyexr); the pixels then travel to the device
 unchanged, as `set_training_image` does with `convert_rgba32` (nerf_loader.cu:49-71).
 """
 import json
@@ -124,6 +128,46 @@ def _decode(path):
         return np.array(im.convert("RGBA"), dtype=np.uint8)
 
 
+def _decode_8bit(base, fr, p, white, black):
+    """An 8-bit frame as RGBA8 [h, w, 4]: the image, its `.alpha.` companion and dynamic mask if present, then
+    convert_rgba32."""
+    px = _decode(p)
+    h, w = px.shape[:2]
+    ap = _resolve(base, f"{fr['file_path']}.alpha.{os.path.splitext(p)[1]}")
+    if os.path.exists(ap):
+        a = _decode(ap)
+        if a.shape[:2] != (h, w):
+            raise ValueError(f"Alpha image {ap} has wrong resolution.")
+        px[..., 3] = (255.0 * _srgb_to_linear(a[..., 0].astype(np.float32) / 255.0)).astype(np.uint8)
+    mp = os.path.join(os.path.dirname(p), f"dynamic_mask_{os.path.splitext(os.path.basename(p))[0]}.png")
+    mask_color = 0
+    if os.path.exists(mp):
+        m = _decode(mp)
+        if m.shape[:2] != (h, w):
+            raise ValueError(f"Dynamic mask {mp} has wrong resolution.")
+        mask_color = MASK_COLOR
+        px.view(np.uint32)[..., 0][np.any(m[..., :3] != 0, axis=-1)] = MASK_COLOR
+    # convert_rgba32 (nerf_loader.cu:49-71)
+    if white:
+        px[..., 3][np.all(px[..., :3] == 255, axis=-1)] = 0
+    if black:
+        px[..., 3][np.all(px[..., :3] == 0, axis=-1)] = 0
+    if mask_color:
+        px.view(np.uint32)[..., 0][px.view(np.uint32)[..., 0] == mask_color] = 0x00FF00FF
+    return px
+
+
+def _decode_exr(path, fix_premult):
+    """load_exr_to_gpu (tinyexr_wrapper.cu:41-55, interleave_and_cast_kernel): float16 [h, w, 4], rgb = half(float(rgb) *
+    (alpha if fix_premult else 1)), alpha = half(alpha)."""
+    from .exr import read_exr
+    px = np.asarray(read_exr(path), np.float32)
+    if fix_premult:
+        px = np.concatenate([px[..., :3] * px[..., 3:4], px[..., 3:4]], axis=-1)
+    with np.errstate(over="ignore"):  # beyond fp16's range: infinity, as the device conversion gives
+        return np.ascontiguousarray(px.astype(np.float16))
+
+
 def _decode_depth(path):
     """load_stbi_16(path, 1 channel): a single-channel 16-bit image as uint16 [h, w] (8-bit files widen as stb does,
     v * 257)."""
@@ -154,7 +198,8 @@ def _load_envmap(path):
 
 
 class LoadedNerf:
-    """Result of load_nerf: cameras + RGBA8 pixels (host) and the dataset-level settings."""
+    """Result of load_nerf: cameras + pixels (host) and the dataset-level settings. rgba8 holds one array per image:
+    uint8 RGBA8 for an 8-bit frame, float16 linear premultiplied RGBA for an EXR frame."""
 
     def __init__(self):
         self.images, self.rgba8, self.paths = [], [], []
@@ -165,6 +210,16 @@ class LoadedNerf:
         # file, enable_depth_loading false or no integer_depth_scale), and per image the scale the dataset multiplies
         # them by: integer_depth_scale * scale (nerf_loader.cu:711)
         self.depth, self.depth_scale = [], []
+
+    @property
+    def image_types(self):
+        """EImageDataType per image: 1 Byte, 2 Half."""
+        return [2 if px.dtype == np.float16 else 1 for px in self.rgba8]
+
+    @property
+    def is_hdr(self):
+        """NerfDataset::is_hdr: a frame was an EXR file (the Testbed then trains with the exponential rgb activation)."""
+        return any(px.dtype == np.float16 for px in self.rgba8)
 
     @property
     def envmap_resolution(self):
@@ -198,6 +253,7 @@ def load_nerf(jsonpaths, max_images=None):
     jsons = [_load_json(p) for p in jsonpaths]
     per_json_frames = []
     enable_depth_loading = True
+    fix_premult = False
     for path, j in zip(jsonpaths, jsons):
         base = os.path.dirname(path)
         if not isinstance(j.get("frames"), list):
@@ -246,6 +302,8 @@ def load_nerf(jsonpaths, max_images=None):
             res.envmap = _load_envmap(_resolve(base, j["envmap"]))
         if "enable_depth_loading" in j:   # like the reference's flag, it carries over to the files after this one
             enable_depth_loading = bool(j["enable_depth_loading"])
+        if "fix_premult" in j:   # carries over likewise (nerf_loader.cu:402, 429-430)
+            fix_premult = bool(j["fix_premult"])
         integer_depth_scale = np.float32(j["integer_depth_scale"]) if "integer_depth_scale" in j else np.float32(-1.0)
         lens0 = {"mode": LENS_PERSPECTIVE, "params": [0.0] * 4, "principal": [0.5, 0.5]}
         _read_lens(j, lens0)
@@ -256,30 +314,10 @@ def load_nerf(jsonpaths, max_images=None):
             if not os.path.exists(p):
                 raise FileNotFoundError(f"Could not find image file '{p}'.")
             if p.lower().endswith(".exr"):
-                raise NotImplementedError("EXR (HDR) training images are not supported")
-            px = _decode(p)
+                px = _decode_exr(p, fix_premult)
+            else:
+                px = _decode_8bit(base, fr, p, white, black)
             h, w = px.shape[:2]
-            ap = _resolve(base, f"{fr['file_path']}.alpha.{os.path.splitext(p)[1]}")
-            if os.path.exists(ap):
-                a = _decode(ap)
-                if a.shape[:2] != (h, w):
-                    raise ValueError(f"Alpha image {ap} has wrong resolution.")
-                px[..., 3] = (255.0 * _srgb_to_linear(a[..., 0].astype(np.float32) / 255.0)).astype(np.uint8)
-            mp = os.path.join(os.path.dirname(p), f"dynamic_mask_{os.path.splitext(os.path.basename(p))[0]}.png")
-            mask_color = 0
-            if os.path.exists(mp):
-                m = _decode(mp)
-                if m.shape[:2] != (h, w):
-                    raise ValueError(f"Dynamic mask {mp} has wrong resolution.")
-                mask_color = MASK_COLOR
-                px.view(np.uint32)[..., 0][np.any(m[..., :3] != 0, axis=-1)] = MASK_COLOR
-            # convert_rgba32 (nerf_loader.cu:49-71)
-            if white:
-                px[..., 3][np.all(px[..., :3] == 255, axis=-1)] = 0
-            if black:
-                px[..., 3][np.all(px[..., :3] == 0, axis=-1)] = 0
-            if mask_color:
-                px.view(np.uint32)[..., 0][px.view(np.uint32)[..., 0] == mask_color] = 0x00FF00FF
             focal = _read_focal(fr, (w, h)) or _read_focal(j, (w, h))
             if focal is None:
                 raise ValueError("Couldn't read fov.")
