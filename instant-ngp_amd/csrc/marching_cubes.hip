@@ -24,8 +24,7 @@
 #include "../../include/ngp_engine.h"
 #include "common.h"
 #include "marching_cubes.h"
-#include "nerf.h"
-#include "ngp_math.h"
+#include "nerf_device.h"
 #include "profiler.h"
 
 namespace ngp {
@@ -275,7 +274,7 @@ struct SampleArgs {
 };
 
 // Grid point p = aabb_min + (x, y, z) * (aabb_max - aabb_min) / (res - 1) (gen_vertices' vec * scale + offset), through
-// transpose(aabb_to_local), then warped into the model's box as the renderer's inputs are (k_render_inputs, nerf.hip).
+// transpose(aabb_to_local), then warped into the model's box as the renderer's inputs are (k_render_inputs, nerf_render.hip).
 // Rows past the grid's end repeat its last point: the batch is padded to the inference granularity.
 __global__ void __launch_bounds__(256) k_mc_positions(SampleArgs a, uint64_t start, uint32_t n_pad, float* __restrict__ out) {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -297,36 +296,13 @@ __global__ void __launch_bounds__(256) k_mc_positions(SampleArgs a, uint64_t sta
 	}
 }
 
-// network_to_density (testbed_nerf.cu:357-365) with the engine's expf, as the renderer and the density grid update
-__device__ __forceinline__ float density_activation(float v, uint32_t act) {
-	switch (act) {
-		case nerf::ACT_NONE: return v;
-		case nerf::ACT_RELU: return v > 0.0f ? v : 0.0f;
-		case nerf::ACT_LOGISTIC: return 1.0f / (1.0f + ngp_expf_fast(-v));
-		case nerf::ACT_EXP: return ngp_expf_fast(v);
-	}
-	return 0.0f;
-}
-// network_to_rgb (:317-330)
-__device__ __forceinline__ float rgb_activation(float v, uint32_t act) {
-	switch (act) {
-		case nerf::ACT_NONE: return v;
-		case nerf::ACT_RELU: return v > 0.0f ? v : 0.0f;
-		case nerf::ACT_LOGISTIC: return 1.0f / (1.0f + ngp_expf_fast(-v));
-		case nerf::ACT_EXP: return ngp_expf_mid(fminf(fmaxf(v, -10.0f), 10.0f));
-	}
-	return 0.0f;
-}
-__device__ __forceinline__ float linear_to_srgb(float l) {  // common_device.cuh:99-105
-	return l < 0.0031308f ? 12.92f * l : 1.055f * powf(l, 0.41666f) - 0.055f;
-}
-
-// row 0 of the model's fp16 output (SoA: n contiguous halves) -> the grid's float
+// row 0 of the model's fp16 output (SoA: n contiguous halves) -> the grid's float; the density as the renderer and the
+// density grid update activate it (nerf_device.h)
 __global__ void __launch_bounds__(256) k_mc_values(uint32_t n, const f16* __restrict__ row0, int kind, uint32_t act, float* __restrict__ out) {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;
 	const float v = (float)row0[i];
-	out[i] = kind == NGP_MC_NERF ? density_activation(v, act) : kind == NGP_MC_SDF ? -v : v;
+	out[i] = kind == NGP_MC_NERF ? nerf::network_to_density(v, act) : kind == NGP_MC_SDF ? -v : v;
 }
 
 // NerfCoordinate rows at the vertices: warped position, dt 0, direction normalize(-normal) as (d + 1) / 2
@@ -350,7 +326,7 @@ __global__ void __launch_bounds__(256) k_mc_color_inputs(uint32_t n, uint32_t n_
 __global__ void __launch_bounds__(256) k_mc_colors_nerf(uint32_t n, const f16* __restrict__ rgbd, uint32_t act, float* __restrict__ colors) {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;
-	for (int k = 0; k < 3; ++k) colors[3 * (size_t)i + k] = linear_to_srgb(rgb_activation((float)rgbd[4 * (size_t)i + k], act));
+	for (int k = 0; k < 3; ++k) colors[3 * (size_t)i + k] = linear_to_srgb(nerf::network_to_rgb((float)rgbd[4 * (size_t)i + k], act));
 }
 // SDF: 0.5 n + 0.5 of the normalised normal
 __global__ void __launch_bounds__(256) k_mc_colors_normal(uint32_t n, const float* __restrict__ normals, float* __restrict__ colors) {

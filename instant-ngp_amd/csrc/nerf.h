@@ -53,7 +53,8 @@ struct ImageRef {
 };
 
 // Host: effective camera matrix = get_xform_given_rolling_shutter(start == end, t = 0)
-// (common_device.cuh:401-408): rotation goes through glm quat_cast / slerp / normalize / mat3_cast.
+// (common_device.cuh:401-408): rotation goes through glm quat_cast / slerp / normalize / mat3_cast. In nerf_abi.hip, as
+// is ~Dataset: the dataset is created there.
 void effective_camera_matrix(const float xform[12], float out[12]);
 
 struct Dataset {
@@ -191,6 +192,9 @@ void envmap_deposit_values(uint32_t w, uint32_t h, uint32_t n, const float* dirs
                            hipStream_t s);
 void envmap_gradient_f32(uint32_t w, uint32_t h, const unsigned long long* acc, float* grad, hipStream_t s);
 
+// The kernels' entry points, by the file that holds them; each kernel there cites the reference kernel it re-implements.
+
+// ---- nerf_sampler.hip ------------------------------------------------------------------------
 // Every ray's training pixel (nerf_pixel.h): img [n_rays], uv [n_rays x 2] after snapping, pdf [n_rays x 2] =
 // {img_pdf, uv_pdf}. The device form reads the dataset's cameras and device CDFs; the host form makes no GPU call
 // (cams: host cameras of which width and height are read, CDFs and outputs in host memory).
@@ -198,13 +202,23 @@ void training_pixels(const Dataset& ds, const ngp_nerf_config& cfg, uint32_t n_r
                      const ErrorCdfs& cdfs, uint32_t* img, float* uv, float* pdf, hipStream_t s);
 void training_pixels_host(const Camera* cams, uint32_t n_images, const ngp_nerf_config& cfg, uint32_t n_rays, uint32_t ray_offset,
                           uint32_t n_rays_total, Rng rng, const ErrorCdfs& cdfs, uint32_t* img, float* uv, float* pdf);
-
-// The kernels (each cites its reference kernel in nerf.hip).
 // cams (optional): the device cameras to trace instead of the dataset's (a trainer's refined poses)
 void sample_rays(const Dataset& ds, const ngp_nerf_config& cfg, const SampleArgs& a, uint32_t* tmp_u32, float* tmp_f32, hipStream_t s,
                  const Camera* cams = nullptr);
 size_t sample_tmp_u32(uint32_t n_rays);  // u32 of sample_rays' tmp_u32 (counts, count-wave sums and prefixes)
+size_t sample_tmp_f32(uint32_t n_rays);  // floats of sample_rays' tmp_f32 (stored t per step + ray geometry)
+
+// ---- nerf_loss.hip ---------------------------------------------------------------------------
 void compute_loss(const Dataset& ds, const ngp_nerf_config& cfg, const LossArgs& a, uint32_t* tmp_u32, float* tmp_f32, hipStream_t s);
+size_t loss_tmp_f32(uint32_t n_rays);    // floats of compute_loss' tmp_f32 (per-ray pass-1 results)
+// whether compute_loss runs its depth instantiations, and the floats of tmp_f32 they need (one more per ray)
+bool loss_depth_on(const Dataset& ds, const LossArgs& a);
+size_t loss_tmp_f32_depth(uint32_t n_rays);
+// the floats of the per-ray exposure gradients, which a caller may keep behind those (LossArgs::exposure_ray_grad)
+size_t loss_tmp_f32_exposure(uint32_t n_rays);
+// construct_cdf_2d / construct_cdf_1d (testbed_nerf.cu:2356-2410) over the error map
+void error_map_cdfs(uint32_t n_images, uint32_t w, uint32_t h, const float* data, float* cdf_x_cond_y, float* cdf_y,
+                    float* cdf_img, hipStream_t s);
 void fill_rollover_f16(uint32_t n_elements, uint32_t stride, const uint32_t* n_input, f16* data, bool rescale, hipStream_t s);
 void fill_rollover_f32(uint32_t n_elements, uint32_t stride, const uint32_t* n_input, float* data, hipStream_t s);
 void fill_rollover_pair(uint32_t n_elements, const uint32_t* n_input, f16* dloss, uint32_t stride16, float* coords,
@@ -219,6 +233,8 @@ struct StepPublish {
 };
 void fill_rollover_pair_publish(uint32_t n_elements, const uint32_t* n_input, f16* dloss, uint32_t stride16, float* coords,
                                 uint32_t stride32, const StepPublish& pub, hipStream_t s);
+
+// ---- nerf_density_grid.hip -------------------------------------------------------------------
 void grid_generate_samples(uint32_t n, Rng rng, uint32_t step, const ngp_nerf_config& cfg, const float* grid_in,
                            uint32_t n_cascades, float thresh, float* positions, uint32_t* indices, uint32_t* mask, hipStream_t s);
 size_t grid_mask_words(uint32_t n_cascades);  // u32 of grid_generate_samples' cell mask
@@ -244,18 +260,8 @@ void grid_mean_bitfield(const float* grid, uint32_t max_cascade, float* mean_out
 // grid_ema then grid_mean_bitfield in three launches (the density grid update's finalization; n_el >= GRID_N_CELLS)
 void grid_ema_mean_bitfield(uint32_t n_el, float decay, float* grid, const float* tmp, uint32_t max_cascade, float* mean_out,
                             uint8_t* bitfield, hipStream_t s);
-size_t sample_tmp_f32(uint32_t n_rays);  // floats of sample_rays' tmp_f32 (stored t per step + ray geometry)
-size_t loss_tmp_f32(uint32_t n_rays);    // floats of compute_loss' tmp_f32 (per-ray pass-1 results)
-// whether compute_loss runs its depth instantiations, and the floats of tmp_f32 they need (one more per ray)
-bool loss_depth_on(const Dataset& ds, const LossArgs& a);
-size_t loss_tmp_f32_depth(uint32_t n_rays);
-// the floats of the per-ray exposure gradients, which a caller may keep behind those (LossArgs::exposure_ray_grad)
-size_t loss_tmp_f32_exposure(uint32_t n_rays);
-// construct_cdf_2d / construct_cdf_1d (testbed_nerf.cu:2356-2410) over the error map
-void error_map_cdfs(uint32_t n_images, uint32_t w, uint32_t h, const float* data, float* cdf_x_cond_y, float* cdf_y,
-                    float* cdf_img, hipStream_t s);
 
-// ---- rendering (NerfTracer) ------------------------------------------------------------------
+// ---- nerf_render.hip: rendering (NerfTracer) -------------------------------------------------
 struct RenderArgs {
 	uint32_t width, height;
 	float focal[2], screen_center[2];

@@ -1,11 +1,83 @@
-// nerf_abi.hip — the C-ABI that needs no trainer: the NeRF dataset, the default config, stateless wrappers around the
-// kernels of nerf.hip and envmap.hip (sampler, training pixels, loss, environment map, rollover, density grid), and
-// the renderer. run_sampler and run_compute_loss are the wrappers' common part, which the training step
+// nerf_abi.hip — the C-ABI that needs no trainer: the NeRF dataset (with its cameras' effective matrices), the default
+// config, stateless wrappers around the kernels of nerf_sampler.hip, nerf_loss.hip, nerf_density_grid.hip and envmap.hip
+// (sampler, training pixels, loss, environment map, rollover, density grid), the renderer (nerf_render.hip) and
+// ngp_debug_math_check. run_sampler and run_compute_loss are the wrappers' common part, which the training step
 // (nerf_trainer.hip) calls too.
 #include "nerf_host.h"
+#include "ngp_math.h"
 
 namespace ngp {
 namespace nerf {
+
+// ------------------------------------------------------------------------------------------------
+// host: effective camera matrix (glm quat_cast -> slerp(t=0, start == end) -> normalize -> mat3_cast)
+// ------------------------------------------------------------------------------------------------
+void effective_camera_matrix(const float xf[12], float out[12]) {
+	// glm column-major m[c][r] = xf[3c + r]
+	auto M = [&](int c, int r) { return xf[3 * c + r]; };
+	const float fx = M(0, 0) - M(1, 1) - M(2, 2), fy = M(1, 1) - M(0, 0) - M(2, 2), fz = M(2, 2) - M(0, 0) - M(1, 1);
+	const float fw = M(0, 0) + M(1, 1) + M(2, 2);
+	int bi = 0;
+	float big = fw;
+	if (fx > big) { big = fx; bi = 1; }
+	if (fy > big) { big = fy; bi = 2; }
+	if (fz > big) { big = fz; bi = 3; }
+	const float bv = sqrtf(big + 1.0f) * 0.5f, mult = 0.25f / bv;
+	float w, x, y, z;
+	switch (bi) {
+		case 0: w = bv; x = (M(1, 2) - M(2, 1)) * mult; y = (M(2, 0) - M(0, 2)) * mult; z = (M(0, 1) - M(1, 0)) * mult; break;
+		case 1: w = (M(1, 2) - M(2, 1)) * mult; x = bv; y = (M(0, 1) + M(1, 0)) * mult; z = (M(2, 0) + M(0, 2)) * mult; break;
+		case 2: w = (M(2, 0) - M(0, 2)) * mult; x = (M(0, 1) + M(1, 0)) * mult; y = bv; z = (M(1, 2) + M(2, 1)) * mult; break;
+		default: w = (M(0, 1) - M(1, 0)) * mult; x = (M(2, 0) + M(0, 2)) * mult; y = (M(1, 2) + M(2, 1)) * mult; z = bv; break;
+	}
+	// slerp(q, q, 0) takes the linear branch: q * 1 + q * 0 = q; then normalize
+	const float len = sqrtf(w * w + x * x + y * y + z * z);
+	if (len <= 0.f) { w = 1.f; x = y = z = 0.f; }
+	else { const float inv = 1.0f / len; w *= inv; x *= inv; y *= inv; z *= inv; }
+	const float qxx = x * x, qyy = y * y, qzz = z * z, qxz = x * z, qxy = x * y, qyz = y * z, qwx = w * x, qwy = w * y, qwz = w * z;
+	out[0] = 1.f - 2.f * (qyy + qzz); out[1] = 2.f * (qxy + qwz); out[2] = 2.f * (qxz - qwy);
+	out[3] = 2.f * (qxy - qwz); out[4] = 1.f - 2.f * (qxx + qzz); out[5] = 2.f * (qyz + qwx);
+	out[6] = 2.f * (qxz + qwy); out[7] = 2.f * (qyz - qwx); out[8] = 1.f - 2.f * (qxx + qyy);
+	out[9] = xf[9]; out[10] = xf[10]; out[11] = xf[11];
+}
+
+Dataset::~Dataset() {
+	for (float* d : depth) if (d) (void)hipFree(d);
+	for (void* d : hdr) if (d) (void)hipFree(d);
+	if (d_images) (void)hipFree(d_images);
+	if (d_depth) (void)hipFree(d_depth);
+	if (d_cams) (void)hipFree(d_cams);
+	if (d_pixels) (void)hipFree(d_pixels);
+}
+
+// ngp_debug_math_check: the device forms of the shared math against their reference operations, over whole
+// input ranges. which 0: ngp_div_2pf(f) vs the IEEE f / (2 + f) for all 2^23 reduced logf arguments f.
+__global__ void k_check_div_2pf(unsigned long long* bad) {
+	const uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
+	if (m >= (1u << 23)) return;
+	const float f = __uint_as_float(m + 0x3f3504f3u) - 1.0f;
+	const float want = f / (2.0f + f);
+	if (__float_as_uint(ngp_div_2pf(f)) != __float_as_uint(want)) atomicAdd(bad, 1ull);
+}
+extern "C" __attribute__((visibility("default"))) int ngp_debug_math_check(int which, void* stream, uint64_t* mismatches) {
+	if (!mismatches || which != 0) return NGP_INVALID;
+	hipStream_t s = (hipStream_t)stream;
+	unsigned long long* d = nullptr;
+	if (hipMallocAsync((void**)&d, 8, s) != hipSuccess) return NGP_ERROR;
+	int rc = NGP_OK;
+	if (hipMemsetAsync(d, 0, 8, s) != hipSuccess) rc = NGP_ERROR;
+	if (rc == NGP_OK) {
+		k_check_div_2pf<<<(1u << 23) / 256, 256, 0, s>>>(d);
+		if (hipGetLastError() != hipSuccess) rc = NGP_ERROR;
+	}
+	unsigned long long h = 0;
+	if (rc == NGP_OK && hipMemcpyAsync(&h, d, 8, hipMemcpyDeviceToHost, s) != hipSuccess) rc = NGP_ERROR;
+	if (hipStreamSynchronize(s) != hipSuccess) rc = NGP_ERROR;
+	(void)hipFreeAsync(d, s);
+	(void)hipStreamSynchronize(s);
+	*mismatches = h;
+	return rc;
+}
 
 // sample_rays, optionally tracing `cams` instead of the dataset's cameras
 int run_sampler(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, SampleArgs a, const Camera* cams) {

@@ -169,4 +169,12 @@ NGP_MATH_FN float ngp_div_rc(float x, float c, float rc) {
 	return x / c;
 }
 
+/* The sRGB curves (common_device.cuh:75-121), one text for the NeRF loss pass and renderer, the mesh colours
+ * (marching_cubes.hip) and the image trainer (training.hip). */
+NGP_MATH_FN float srgb_to_linear(float s) { return s <= 0.04045f ? s / 12.92f : powf((s + 0.055f) / 1.055f, 2.4f); }
+NGP_MATH_FN float srgb_to_linear_derivative(float s) {
+	return s <= 0.04045f ? 1.0f / 12.92f : 2.4f / 1.055f * powf((s + 0.055f) / 1.055f, 1.4f);
+}
+NGP_MATH_FN float linear_to_srgb(float l) { return l < 0.0031308f ? 12.92f * l : 1.055f * powf(l, 0.41666f) - 0.055f; }
+
 #endif /* NGP_MATH_H */

@@ -1,4 +1,4 @@
-// render_common.h — device helpers shared by the ray tracers (nerf.hip's NerfTracer, sdf_render.hip's SphereTracer):
+// render_common.h — device helpers shared by the ray tracers (nerf_render.hip's NerfTracer, sdf_render.hip's SphereTracer):
 // the vector type, the bounding box tests (bounding_box.cuh) and the scrambled-Sobol pixel jitter (random_val.cuh).
 // Float arithmetic in the reference's operation order (-ffp-contract=off). Include inside a .hip file only.
 #pragma once

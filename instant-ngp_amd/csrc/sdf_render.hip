@@ -43,7 +43,7 @@ struct TraceArgs {  // what the trace kernels share
 // prepare_shadow_rays normalises the (already normalised) sun direction once more for the payload (:253, 274)
 __device__ __forceinline__ V3 shadow_dir(const TraceArgs& t) { return normalize3(t.sun_dir); }
 
-// init_rays_with_payload_kernel_sdf (:508-613) with pixel_to_ray as k_render_init does it (nerf.hip): no slice
+// init_rays_with_payload_kernel_sdf (:508-613) with pixel_to_ray as k_render_init does it (nerf_render.hip): no slice
 // plane, aperture, foveation, envmap, hidden-area mask or octree. Also clears the frame and the depth buffer.
 __global__ void k_sdf_init_rays(FrameArgs a, TraceArgs t, Rays r, float* __restrict__ frame, float* __restrict__ depth) {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;

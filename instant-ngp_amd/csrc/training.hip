@@ -1,6 +1,7 @@
 // training.hip — tcnn losses, image sampling (BASELINE C1) and SDF sampling (BASELINE C5) on gfx950.
 // See training.h for the reference call sites; every kernel cites the code it restates.
 #include "training.h"
+#include "ngp_math.h"
 #include "profiler.h"
 
 #include <cmath>
@@ -68,10 +69,6 @@ void loss_evaluate(uint32_t type, const LossEvalArgs& a, hipStream_t s) {
 // ------------------------------------------------------------------------------------------------
 // Image training data (src/testbed_image.cu:214-285)
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float linear_to_srgb(float x) {  // common_device.cuh:99-105
-	return x < 0.0031308f ? 12.92f * x : 1.055f * powf(x, 0.41666f) - 0.055f;
-}
-
 // generate_random_uniform (element k = draw k of m_rng; tcnn†) + stratify2_kernel (:62-76)
 // + eval_image_kernel_and_snap<float, 3> (:167-212), one thread per sample.
 __global__ void __launch_bounds__(256) k_image_samples(const ImageSampleArgs a, uint32_t log2_n) {

@@ -112,7 +112,7 @@ def test_sampler_with_cdfs(pkg, orc, scene):
 
 # ---- 6. the loss with CDFs --------------------------------------------------------------------------------------
 def numpy_deposit(img, uv, ml, n_img, em_h, em_w):
-    """deposit_error of csrc/nerf.hip (testbed_nerf.cu:1869-1899): weights in float32, sums in float64."""
+    """deposit_error of csrc/nerf_loss.hip (testbed_nerf.cu:1869-1899): weights in float32, sums in float64."""
     rx, ry = F(em_w), F(em_h)
     px = np.minimum(np.maximum(uv[:, 0] * rx - F(0.5), F(0)), rx - F(1.0 + 1e-4)).astype(F)
     py = np.minimum(np.maximum(uv[:, 1] * ry - F(0.5), F(0)), ry - F(1.0 + 1e-4)).astype(F)

@@ -169,7 +169,7 @@ def test_generate_training_samples_cone(pkg, orc, scene, aabb_scale, n_rays, fra
 def test_sampler_and_loss_cone_at_scale(pkg, orc, scene, aabb_scale, cone, n_rays, frac):
     """Fox-scale and larger ray counts (64k rays at aabb_scale 8, 32, 128: 2-4 K count waves and 4 tiles of the
     loss's group scan; 32k and 30001 rays) and user-set cone angles
-    from 2e-5 to 0.02: the sampler's hardware exp/log speculation in empty space (csrc/nerf.hip
+    from 2e-5 to 0.02: the sampler's hardware exp/log speculation in empty space (csrc/nerf_sampler.hip
     step_empty) falls back to the exact path near every integer decision, with margins that scale with
     1 / log(1 + cone), so sample sets, compacted counts and coordinates stay bit-exact with the oracle."""
     ds, ims, pix = scene

@@ -240,7 +240,7 @@ def depth_world(pkg):
 
 # ---- the float32 restatement -------------------------------------------------------------------------------------------
 def _loss32(target, pred, kind):
-    """loss_channel of nerf.hip in float32 arrays: (loss, gradient)."""
+    """loss_channel of nerf_loss.hip in float32 arrays: (loss, gradient)."""
     f = F32
     d = pred - target
     one, ad = f(1.0), np.abs(d)

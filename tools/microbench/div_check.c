@@ -1,6 +1,6 @@
 // Exhaustive checks of the sampler's divisions against the IEEE quotient, for every non-negative
 // finite float t (negative t: both forms are odd in t):
-//  - by MIN_CONE_STEPSIZE (nerf.hip div_min_stepsize): q = t * RN(1/c); q' = fma(fma(-q, c, t), RN(1/c), q);
+//  - by MIN_CONE_STEPSIZE (nerf_device.h div_min_stepsize): q = t * RN(1/c); q' = fma(fma(-q, c, t), RN(1/c), q);
 //    prints the largest failing t below 1 and the smallest failing t above 1;
 //  - by log(1 + cone) (ngp_math.h ngp_div_rc, the stepping space's exponential segment) at the
 //    default cone 1/256: counts mismatches over the range ngp_div_rc refines (2^-100 .. 2^100).
