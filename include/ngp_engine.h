@@ -474,6 +474,7 @@ void ngp_nerf_renderer_destroy(ngp_nerf_renderer* r);
  * backprop_scale 128, composited as normalize(-density'(raw) * gradient), shaded as (0.5 n + 0.5) * alpha),
  * 0 AO (each step's alpha), 3 Positions ((pos - 0.5) / 2 + 0.5, show_accel off), 4 Depth (dot(camera forward,
  * pos - ray origin) * depth_scale): :1189-1208, composited like Shade, no sRGB decoding in the shade step (:2183).
+ * 5 Distortion: see ngp_nerf_renderer_set_distortion_map.
  * depth_scale: 1 / the dataset's scale (render_nerf, testbed_nerf.cu:2822); default 1. */
 int ngp_nerf_renderer_set_mode(ngp_nerf_renderer* r, int render_mode);
 int ngp_nerf_renderer_set_depth_scale(ngp_nerf_renderer* r, float depth_scale);
@@ -626,7 +627,11 @@ int ngp_nerf_trainer_error_map(ngp_nerf_trainer* t, int which, float* out, uint6
  * Engine extension (the reference does not save m_envmap): with an environment map set, a member "envmap" holds
  * width, height, params_binary and ema_params_binary (fp32) and, with the optimizer state, "optimizer" {current_step,
  * ema_valid, ema_binary, first_moments_binary, second_moments_binary, param_steps_binary}. Loading sets the trainer's
- * map from it; a snapshot without the member leaves the trainer's map as it is. */
+ * map from it; a snapshot without the member leaves the trainer's map as it is. Likewise with a lens distortion map
+ * bound: a member "distortion_map" holds width, height and params_binary ([height][width][2] fp32) and, with the
+ * optimizer state, "optimizer" {current_step, ema_valid, ema_binary, ema_params_binary, first_moments_binary,
+ * second_moments_binary, param_steps_binary}. Loading binds the map; a snapshot without the member leaves the
+ * trainer's map as it is. */
 int ngp_nerf_save_snapshot(ngp_nerf_trainer* t, void* stream, const char* path, const char* network_config_json,
                            int include_optimizer_state, int compress);
 int ngp_nerf_load_snapshot(ngp_nerf_trainer* t, void* stream, const char* path);
@@ -851,6 +856,113 @@ int ngp_nerf_trainer_set_envmap_training(ngp_nerf_trainer* t, int loss_type, con
  * value in the pixel's normalized ray direction instead of background_rgba. envmap: DEVICE [height][width][4] fp32,
  * owned by the caller and read by every later ngp_nerf_render; NULL unbinds. */
 int ngp_nerf_renderer_set_envmap(ngp_nerf_renderer* r, const float* envmap, uint32_t width, uint32_t height);
+
+/* ---- lens distortion map (Testbed::m_distortion, Training::optimize_distortion) ----------------------------------- */
+/* A small trainable 2-D map of ray-direction offsets that absorbs what the declared lens model does not explain:
+ * uv_to_ray adds distortion.at_lerp(uv) to dir.xy after the lens (common_device.cuh:443-510), and
+ * compute_cam_gradient_train_nerf splats every ray's image-plane gradient into it (testbed_nerf.cu:2088-2099). A map
+ * is [height][width][2] fp32, texel index x + y * width; width and height in 1..8192.
+ * ngp_nerf_distortion_lookup: the four texels and bilinear weights of n positions uv [n x 2] as Buffer2DView::at_lerp
+ * (common.h:384-400) and deposit_image_gradient (common_device.cuh:124-156) both derive them: xy = (width, height) * uv,
+ * texel (int)xy, weights xy - texel; texels [n x 4] in the order (x, y), (x+1, y), (x, y+1), (x+1, y+1), each clamped
+ * into the map, weights [n x 4] = (1-wx)(1-wy), wx(1-wy), (1-wx)wy, wx wy. Deviation: uv is first folded into [0, 2]
+ * with NaN to 0, so every index is inside the map whatever uv holds. map (nullable) with offsets (nullable, [n x 2]):
+ * also the mixed offset, the four products summed in that order. Device memory. _host: the same function compiled for
+ * the host, host memory, no GPU call; only IEEE add, subtract, multiply, compare and convert are used, so the two agree
+ * bit for bit. */
+int ngp_nerf_distortion_lookup(void* stream, uint32_t width, uint32_t height, uint32_t n, const float* uv, uint32_t* texels,
+                               float* weights, const float* map, float* offsets);
+int ngp_nerf_distortion_lookup_host(uint32_t width, uint32_t height, uint32_t n, const float* uv, uint32_t* texels, float* weights,
+                                    const float* map, float* offsets);
+/* ngp_nerf_generate_training_samples_cdf with a distortion map (DEVICE, nullable) added to every ray's dir.xy at the
+ * ray's (u, v), after the lens; the rng draws and the pixel choice are unchanged. distortion_map NULL: the same
+ * kernels and the same bytes as without it. */
+int ngp_nerf_generate_training_samples_distortion(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream,
+                                                  uint32_t n_rays, uint32_t ray_offset, uint32_t n_rays_total, ngp_rng rng,
+                                                  uint32_t max_samples, const uint8_t* bitfield, uint32_t* ray_indices,
+                                                  float* rays, uint32_t* numsteps, float* coords, uint32_t* counters,
+                                                  const ngp_nerf_error_cdfs* cdfs, const float* distortion_map,
+                                                  uint32_t map_width, uint32_t map_height);
+/* compute_cam_gradient_train_nerf's distortion branch, per ray (testbed_nerf.cu:2088-2099): ngp_nerf_camera_gradients'
+ * arguments and first pass, which additionally writes, for every kept ray, ray_gradients[r] = (inverse(mat3(xform_img))
+ * * (gd - d * dot(gd, d))).xy with d = normalize(ray.d) and gd the ray's summed direction gradient; zeros for a ray
+ * without samples. camera_matrices: DEVICE [n_images x 9], each image's column-major 3x3; the inverse is the general
+ * one (adjugate / determinant), not the transpose. ray_gradients: DEVICE, room for n_rays_total x 2 floats.
+ * pos_gradient / rot_gradient: both given, the per-image sums are added onto them exactly as ngp_nerf_camera_gradients
+ * does (the same bytes); both NULL, the second pass is not launched. */
+int ngp_nerf_distortion_ray_gradients(const ngp_nerf_config* cfg, void* stream, uint32_t n_rays_total, uint32_t n_images,
+                                      const uint32_t* ray_counter, const uint32_t* ray_indices, const float* rays,
+                                      const uint32_t* numsteps, const float* coords, const float* coords_gradient,
+                                      uint32_t gradient_stride, float* pos_gradient, float* rot_gradient,
+                                      const float* camera_matrices, float* ray_gradients);
+/* The map's gradient accumulator: exact and independent of the order of arrival at any magnitude (the reference adds
+ * floats atomically). A finite fp32 contribution is M * 2^(e - 149) with a signed 24-bit integer M and e = max(biased
+ * exponent, 1) - 1; it is added as the 64-bit integer M << (e % 16) into bin e / 16 of its channel, so bin b's unit is
+ * 2^(16 b - 149) and 2^22 contributions to one bin cannot overflow it. Layout: [height][width][3 channels][16 bins]
+ * signed 64-bit words, the channels sum g.x w, sum g.y w and sum w (the reference keeps one weight per gradient
+ * channel; they are equal), then one word counting the rays whose gradient was not finite, which are dropped whole
+ * (deviation: the reference would turn the texel NaN for good). _accumulator_words: the word count of a map (0: invalid size). The
+ * accumulator is the caller's DEVICE memory, zeroed by the caller, and may be read as it is.
+ * ngp_nerf_distortion_deposit (deposit_image_gradient): one thread per kept ray (*ray_counter of them, ids in
+ * ray_indices) recomputes the ray's uv from its id and rng by the uniform training pixel draw, as the loss pass does,
+ * and adds g.x * w_k, g.y * w_k and w_k for the four corners, each product one fp32 multiply, zero products skipped.
+ * ray_gradients [R x 2]; numsteps (nullable, [R x 2]): a ray whose count is 0 deposits nothing (:2044-2048). Calls
+ * accumulate. ngp_nerf_distortion_gradient (safe_divide, :3811-3816): gradient [height][width][2] is WRITTEN with
+ * (float)(S_g / S_w) per channel, S the bins summed in double from the highest down and the quotient rounded to fp32
+ * once, or 0 where S_w == 0. */
+uint64_t ngp_nerf_distortion_accumulator_words(uint32_t width, uint32_t height);
+int ngp_nerf_distortion_deposit(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays_total,
+                                ngp_rng rng, const uint32_t* ray_counter, const uint32_t* ray_indices, const uint32_t* numsteps,
+                                const float* ray_gradients, uint32_t width, uint32_t height, uint64_t* accumulator);
+int ngp_nerf_distortion_gradient(void* stream, uint32_t width, uint32_t height, const uint64_t* accumulator, float* gradient);
+/* The trainer's map (m_distortion.map, a TrainableBuffer<2, 2, float>; testbed.cu:4066-4076): params (nullable: zeros,
+ * TrainableBuffer::initialize_params) are the [height][width][2] initial values in HOST memory. Setting a map resets
+ * its optimizer and discards a prelaunched sampler. A bound map is read by every sampler the trainer launches,
+ * whether optimize_distortion is on or off, as in the reference, which always owns a 32 x 32 zero map; a trainer here
+ * has none until asked, and then issues exactly the launches it would have. _clear also turns the switch off. */
+int ngp_nerf_trainer_set_distortion_map(ngp_nerf_trainer* t, uint32_t width, uint32_t height, const float* params);
+int ngp_nerf_trainer_clear_distortion_map(ngp_nerf_trainer* t);
+enum {
+	NGP_DISTORTION_PARAMS = 0,           /* the raw parameters (the sampler reads these) */
+	NGP_DISTORTION_GRADIENT = 1,         /* the last update's gradient, sum g w / sum w (scaled by 128 * n_steps_between) */
+	NGP_DISTORTION_FIRST_MOMENTS = 2,
+	NGP_DISTORTION_SECOND_MOMENTS = 3,
+	NGP_DISTORTION_PARAM_STEPS = 4,      /* per-parameter Adam step counters: uint32 in the float slots */
+	NGP_DISTORTION_INFERENCE_PARAMS = 5  /* the parameters; the debiased EMA once a step ran under an Ema wrapper (the
+	                                        default chain has none) */
+};
+/* Copies array `which` ([height][width][2]) to HOST memory (out nullable: only the resolution; 0 x 0: no map). */
+int ngp_nerf_trainer_distortion_map(const ngp_nerf_trainer* t, int which, float* out, uint64_t capacity, uint32_t* width,
+                                    uint32_t* height);
+/* The device array (NGP_DISTORTION_PARAMS or NGP_DISTORTION_INFERENCE_PARAMS; NULL without a map), e.g. for
+ * ngp_nerf_renderer_set_distortion_map. Valid until the map is set or cleared. */
+int ngp_nerf_trainer_distortion_map_device(const ngp_nerf_trainer* t, int which, const float** data, uint32_t* width,
+                                           uint32_t* height);
+/* The trainer's accumulator copied to HOST memory as it is (out nullable: only the word count; 0: no map). */
+int ngp_nerf_trainer_distortion_accumulator(const ngp_nerf_trainer* t, uint64_t* out, uint64_t capacity, uint64_t* words);
+/* The network config's "distortion_map" section (testbed.cu:4068-4076): the map's optimizer chain (JSON as
+ * ngp_trainer_create takes it; NULL: the main trainer's) and the resolution of the map that turning
+ * optimize_distortion on creates when none is bound (the reference's default: 32 x 32). */
+int ngp_nerf_trainer_set_distortion_training(ngp_nerf_trainer* t, const char* optimizer_json, uint32_t width, uint32_t height);
+/* Training::optimize_distortion (testbed.h:716-785; default off). On: the training step takes the compacted batch's
+ * input gradient as optimize_extrinsics does, stores every kept ray's image-plane gradient
+ * (ngp_nerf_distortion_ray_gradients with the trainer's current cameras) and deposits it (ngp_nerf_distortion_deposit)
+ * into the trainer's accumulator, which starts from zero after every update; every n_steps_between_cam_updates steps
+ * (the counter shared with poses and exposure) it takes the gradient (ngp_nerf_distortion_gradient) and one step of
+ * the map's optimizer with loss scale 128 * n_steps_between_cam_updates (testbed_nerf.cu:3811-3818) on the step's
+ * stream, and the next step's sampler runs behind that update. Every step of this is bitwise reproducible. Without a
+ * map, turning it on creates a zero map of the configured resolution. Refused, with the state unchanged: together
+ * with either error-sampling switch (uv_pdf is taken as 1), and with a data-parallel exchange hook (the gradient is
+ * not all-reduced), in either order of setting. */
+int ngp_nerf_trainer_set_optimize_distortion(ngp_nerf_trainer* t, int optimize);
+int ngp_nerf_trainer_get_optimize_distortion(const ngp_nerf_trainer* t, int* optimize);
+/* render_nerf through a distortion map (Testbed::Nerf::render_with_lens_distortion; testbed_nerf.cu:2229-2344): every
+ * pixel's ray gets the map's offset at the pixel's uv added to dir.xy after the lens, and render mode 5
+ * (ERenderMode::Distortion, :2331-2344) shows to_rgb(offset * 50) with alpha 1 for every pixel, the offset read at
+ * (x + 0.5, y + 0.5) / resolution, without marching a ray (hsv_to_rgb / to_rgb, common_device.cuh:802-827; without a
+ * map the offset is zero). map: DEVICE [height][width][2] fp32, owned by the caller and read by every later
+ * ngp_nerf_render; NULL unbinds. */
+int ngp_nerf_renderer_set_distortion_map(ngp_nerf_renderer* r, const float* map, uint32_t width, uint32_t height);
 
 /* ---- depth supervision (Training::depth_supervision_lambda, depth_loss_type; NerfDataset depth images) ---------- */
 /* NerfDataset::set_training_image's depth part (nerf_loader.cu:943-960, copy_depth :81-90): image `image` gets an fp32

@@ -314,6 +314,23 @@ SIGNATURES = {
     "ngp_nerf_trainer_exposure_optimizer_state": (i32, [P, u32, C.POINTER(AdamState)]),
     "ngp_nerf_trainer_set_depth_supervision": (i32, [P, f32, u32]),
     "ngp_nerf_trainer_get_depth_supervision": (i32, [P, C.POINTER(f32), C.POINTER(u32)]),
+    "ngp_nerf_distortion_lookup": (i32, [P, u32, u32, u32, P, P, P, P, P]),
+    "ngp_nerf_distortion_lookup_host": (i32, [u32, u32, u32, P, P, P, P, P]),
+    "ngp_nerf_generate_training_samples_distortion": (i32, [P, C.POINTER(NerfConfig), P, u32, u32, u32, Rng, u32, P, P, P, P,
+                                                            P, P, C.POINTER(NerfErrorCdfs), P, u32, u32]),
+    "ngp_nerf_distortion_ray_gradients": (i32, [C.POINTER(NerfConfig), P, u32, u32, P, P, P, P, P, P, u32, P, P, P, P]),
+    "ngp_nerf_distortion_accumulator_words": (u64, [u32, u32]),
+    "ngp_nerf_distortion_deposit": (i32, [P, C.POINTER(NerfConfig), P, u32, Rng, P, P, P, P, u32, u32, P]),
+    "ngp_nerf_distortion_gradient": (i32, [P, u32, u32, P, P]),
+    "ngp_nerf_trainer_set_distortion_map": (i32, [P, u32, u32, P]),
+    "ngp_nerf_trainer_clear_distortion_map": (i32, [P]),
+    "ngp_nerf_trainer_distortion_map": (i32, [P, i32, P, u64, C.POINTER(u32), C.POINTER(u32)]),
+    "ngp_nerf_trainer_distortion_map_device": (i32, [P, i32, C.POINTER(P), C.POINTER(u32), C.POINTER(u32)]),
+    "ngp_nerf_trainer_distortion_accumulator": (i32, [P, P, u64, C.POINTER(u64)]),
+    "ngp_nerf_trainer_set_distortion_training": (i32, [P, C.c_char_p, u32, u32]),
+    "ngp_nerf_trainer_set_optimize_distortion": (i32, [P, i32]),
+    "ngp_nerf_trainer_get_optimize_distortion": (i32, [P, C.POINTER(i32)]),
+    "ngp_nerf_renderer_set_distortion_map": (i32, [P, P, u32, u32]),
 }
 
 

@@ -66,6 +66,10 @@ NERF_BASE = {
         {"n_dims_to_encode": 3, "otype": "SphericalHarmonics", "degree": 4}, {"otype": "Identity"}]},
     "rgb_network": {"otype": "FullyFusedMLP", "activation": "ReLU", "output_activation": "None", "n_neurons": 64,
                     "n_hidden_layers": 2},
+    # the lens distortion map (nerf.training.optimize_distortion): its resolution and its own optimizer
+    "distortion_map": {"resolution": [32, 32], "optimizer": {
+        "otype": "ExponentialDecay", "decay_start": 10000, "decay_interval": 5000, "decay_end": 25000, "decay_base": 0.33,
+        "nested": {"otype": "Adam", "learning_rate": 1e-4, "beta1": 0.9, "beta2": 0.99, "epsilon": 1e-8}}},
 }
 
 # configs/sdf/base.json (L=16, F=2, T=2^19; BASELINE C5 uses T=2^22) and configs/image/base.json.
@@ -102,3 +106,19 @@ def nerf_config(variant="C2"):
     # log member to 2.0, src/testbed.cu:3991, and passes the encoding config on unchanged, :4037)
     cfg["encoding"]["per_level_scale"] = 2.0
     return cfg
+
+
+def distortion_map_config(cfg):
+    """The "distortion_map" section of a network config as Testbed::reset_network reads it (testbed.cu:4066-4076):
+    {"resolution": [w, h], "optimizer": {...}}. The resolution defaults to 32 x 32; the optimizer falls back to the
+    config's main "optimizer" section when the "distortion_map" section, or its optimizer, is absent."""
+    sec = cfg.get("distortion_map") or {}
+    res = sec.get("resolution", [32, 32])
+    if isinstance(res, (int, float)):
+        res = [res, res]
+    if len(res) != 2 or any(int(r) < 1 for r in res):
+        raise ValueError("distortion_map: resolution is [width, height]")
+    opt = sec.get("optimizer", cfg.get("optimizer"))
+    if opt is None:
+        raise ValueError("distortion_map: the config has neither a distortion_map optimizer nor a main optimizer")
+    return {"resolution": [int(res[0]), int(res[1])], "optimizer": json.loads(json.dumps(opt))}

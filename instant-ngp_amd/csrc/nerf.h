@@ -12,6 +12,7 @@
 #include "lens.h"
 
 #include <functional>
+#include <type_traits>
 
 namespace ngp {
 namespace nerf {
@@ -94,6 +95,13 @@ struct ErrorCdfs {
 	bool any() const { return cdf_img != nullptr || cdf_x_cond_y != nullptr; }
 };
 
+// The lens distortion map a sampler or renderer adds to its rays (distortion.h): device floats [h][w][2], the offset
+// of dir.xy at the ray's uv after the lens. data null: none, and the kernels' instantiations without it run.
+struct DistMap {
+	const float* data;
+	uint32_t w, h;
+};
+
 struct SampleArgs {
 	uint32_t n_rays, ray_offset, n_rays_total_for_image_idx;  // image_idx uses the global ray id
 	uint32_t max_samples;
@@ -105,6 +113,11 @@ struct SampleArgs {
 	float* coords;             // [max_samples x 7] NerfCoordinate
 	uint32_t* counters;        // [2]: rays kept, numsteps total (incl. dropped)
 	ErrorCdfs cdfs;            // all null: uniform pixels
+};
+
+// the arguments of the count pass's DIST forms
+struct SampleArgsDist : SampleArgs {
+	DistMap dist;
 };
 
 struct LossArgs {
@@ -192,6 +205,33 @@ void envmap_deposit_values(uint32_t w, uint32_t h, uint32_t n, const float* dirs
                            hipStream_t s);
 void envmap_gradient_f32(uint32_t w, uint32_t h, const unsigned long long* acc, float* grad, hipStream_t s);
 
+// The lens distortion map's stand-alone forms (distortion.hip; distortion.h has the lookup and the accumulator): uv
+// [n x 2]; texels, weights [n x 4] as distortion_lookup returns them; offsets (optional, with map [h][w][2]) [n x 2] the
+// mixed offset. distortion_deposit_rays: one thread per kept ray (at most n_rays_cap, the device counter's value)
+// recomputes the ray's uv by training_pixel<false> from its id and the rng, as loss pass 1 does, and adds ray_grad
+// [R x 2] by the lookup's weights into acc (distortion_acc_words64 words, zeroed by the caller); numsteps (optional,
+// [R x 2]): a ray whose count is 0 deposits nothing, as the reference returns before its deposit. cams: device cameras
+// of which width and height are read. distortion_gradient_f32 turns an accumulator into the fp32 gradient [h][w][2]:
+// per channel the bins summed in double from the highest down, then (float)(sum g / sum w), 0 where no weight came.
+void distortion_lookup_device(uint32_t w, uint32_t h, uint32_t n, const float* uv, uint32_t* texels, float* weights, const float* map,
+                              float* offsets, hipStream_t s);
+void distortion_lookup_host(uint32_t w, uint32_t h, uint32_t n, const float* uv, uint32_t* texels, float* weights, const float* map,
+                            float* offsets);
+struct DistDepositArgs {
+	uint32_t n_rays_cap, n_rays_total, n_images;
+	bool snap;
+	Rng rng;
+	const Camera* cams;
+	const uint32_t* ray_counter;
+	const uint32_t* ray_indices;
+	const uint32_t* numsteps;   // nullable
+	const float* ray_grad;      // [R x 2]
+	uint32_t w, h;
+	unsigned long long* acc;
+};
+void distortion_deposit_rays(const DistDepositArgs& a, hipStream_t s);
+void distortion_gradient_f32(uint32_t w, uint32_t h, const unsigned long long* acc, float* grad, hipStream_t s);
+
 // The kernels' entry points, by the file that holds them; each kernel there cites the reference kernel it re-implements.
 
 // ---- nerf_sampler.hip ------------------------------------------------------------------------
@@ -203,8 +243,9 @@ void training_pixels(const Dataset& ds, const ngp_nerf_config& cfg, uint32_t n_r
 void training_pixels_host(const Camera* cams, uint32_t n_images, const ngp_nerf_config& cfg, uint32_t n_rays, uint32_t ray_offset,
                           uint32_t n_rays_total, Rng rng, const ErrorCdfs& cdfs, uint32_t* img, float* uv, float* pdf);
 // cams (optional): the device cameras to trace instead of the dataset's (a trainer's refined poses)
+// dist (optional, data non-null): the distortion map added to every ray's direction (the count pass's DIST forms)
 void sample_rays(const Dataset& ds, const ngp_nerf_config& cfg, const SampleArgs& a, uint32_t* tmp_u32, float* tmp_f32, hipStream_t s,
-                 const Camera* cams = nullptr);
+                 const Camera* cams = nullptr, const DistMap* dist = nullptr);
 size_t sample_tmp_u32(uint32_t n_rays);  // u32 of sample_rays' tmp_u32 (counts, count-wave sums and prefixes)
 size_t sample_tmp_f32(uint32_t n_rays);  // floats of sample_rays' tmp_f32 (stored t per step + ray geometry)
 
@@ -277,7 +318,7 @@ struct RenderArgs {
 	uint32_t rgb_activation, density_activation;
 	float min_transmittance;
 	float background[4];           // linear rgba
-	uint32_t render_mode;          // ERenderMode (common.h:110-121): 0 AO, 1 Shade, 2 Normals, 3 Positions, 4 Depth, 9 EncodingVis
+	uint32_t render_mode;          // ERenderMode (common.h:110-121): 0 AO, 1 Shade, 2 Normals, 3 Positions, 4 Depth, 5 Distortion, 9 EncodingVis
 	float depth_scale;             // ERenderMode::Depth: 1 / dataset scale (testbed_nerf.cu:2822)
 	int32_t show_accel;            // Testbed::Nerf::show_accel (-1 off): the march's minimum mip, alpha 1, Positions by cell
 	// environment map (testbed_nerf.cu:2315-2319): the frame is pre-filled per pixel with the map's value in the
@@ -285,7 +326,11 @@ struct RenderArgs {
 	const float* envmap;
 	uint32_t env_w, env_h;
 };
-enum : uint32_t { RENDER_AO = 0, RENDER_SHADE = 1, RENDER_NORMALS = 2, RENDER_POSITIONS = 3, RENDER_DEPTH = 4, RENDER_ENCODING_VIS = 9 };
+struct RenderArgsDist : RenderArgs {  // the arguments of the DIST forms of k_render_init and k_render_fill_envmap
+	DistMap dist;
+};
+enum : uint32_t { RENDER_AO = 0, RENDER_SHADE = 1, RENDER_NORMALS = 2, RENDER_POSITIONS = 3, RENDER_DEPTH = 4, RENDER_DISTORTION = 5,
+                  RENDER_ENCODING_VIS = 9 };
 struct RenderWorkspace {
 	void* payload[2]; void* payload_hit;
 	float* rgba[2]; float* rgba_hit;
@@ -299,10 +344,11 @@ size_t render_payload_bytes();
 // spp samples of one view, averaged into out (linear RGBA [H x W x 4]); infer(n, coords, out_rm)
 // evaluates the network on n NerfCoordinates (output RM, row stride n). Normals: grad(n, coords) then
 // overwrites the coordinates' position rows with d(density output)/d(position) (Network::input_gradient,
-// testbed_nerf.cu:2615-2617).
+// testbed_nerf.cu:2615-2617). dist (optional, data non-null): the distortion map added to every pixel's ray direction
+// after the lens (render_with_lens_distortion), and what ERenderMode::Distortion shows (:2331-2344; without one, zero).
 void render_frame(const RenderArgs& a, uint32_t spp, RenderWorkspace& ws,
                   const std::function<void(uint32_t, const float*, f16*)>& infer, float* out, hipStream_t s,
-                  const std::function<void(uint32_t, float*)>& grad = nullptr);
+                  const std::function<void(uint32_t, float*)>& grad = nullptr, const DistMap* dist = nullptr);
 
 }  // namespace nerf
 }  // namespace ngp

@@ -5,6 +5,7 @@
 // (nerf_trainer.hip) calls too.
 #include "nerf_host.h"
 #include "ngp_math.h"
+#include "distortion.h"
 
 namespace ngp {
 namespace nerf {
@@ -80,13 +81,15 @@ extern "C" __attribute__((visibility("default"))) int ngp_debug_math_check(int w
 }
 
 // sample_rays, optionally tracing `cams` instead of the dataset's cameras
-int run_sampler(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, SampleArgs a, const Camera* cams) {
+int run_sampler(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, SampleArgs a, const Camera* cams,
+                const DistMap* dist) {
 	if (!ds || !cfg || !a.bitfield || !a.ray_indices || !a.rays || !a.numsteps || !a.coords || !a.counters) return NGP_INVALID;
 	NERF_TRY({
 		if (!a.n_rays_total_for_image_idx) a.n_rays_total_for_image_idx = a.n_rays;
 		static thread_local Buf tmp, tmpf;
 		if (a.n_rays == 0) { NGP_HIP(hipMemsetAsync(a.counters, 0, 8, S(stream))); return NGP_OK; }
-		sample_rays(ds->ds, *cfg, a, tmp.get<uint32_t>(sample_tmp_u32(a.n_rays)), tmpf.get<float>(sample_tmp_f32(a.n_rays)), S(stream), cams);
+		sample_rays(ds->ds, *cfg, a, tmp.get<uint32_t>(sample_tmp_u32(a.n_rays)), tmpf.get<float>(sample_tmp_f32(a.n_rays)), S(stream), cams,
+		            dist);
 	});
 }
 
@@ -210,6 +213,7 @@ static int ngp_nerf_dataset_create_typed_impl(uint32_t n_images, const ngp_nerf_
 
 struct ngp_nerf_renderer {
 	Buf pay0, pay1, payh, rgba0, rgba1, rgbah, coords, out, frame, counters;
+	DistMap dist{nullptr, 0, 0};          // ngp_nerf_renderer_set_distortion_map (the caller's device memory)
 	const float* envmap = nullptr;        // ngp_nerf_renderer_set_envmap (the caller's device memory)
 	uint32_t env_w = 0, env_h = 0;
 	uint32_t* host_counters = nullptr;
@@ -338,6 +342,21 @@ int ngp_nerf_generate_training_samples_cdf(const ngp_nerf_dataset* ds, const ngp
 	a.max_samples = max_samples; a.rng = Rng{rng.state, rng.inc}; a.bitfield = bitfield;
 	a.ray_indices = ray_indices; a.rays = rays; a.numsteps = numsteps; a.coords = coords; a.counters = counters;
 	return run_sampler(ds, cfg, stream, a, nullptr);
+}
+
+int ngp_nerf_generate_training_samples_distortion(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
+                                                  uint32_t ray_offset, uint32_t n_rays_total, ngp_rng rng, uint32_t max_samples,
+                                                  const uint8_t* bitfield, uint32_t* ray_indices, float* rays, uint32_t* numsteps,
+                                                  float* coords, uint32_t* counters, const ngp_nerf_error_cdfs* cdfs,
+                                                  const float* distortion_map, uint32_t map_width, uint32_t map_height) {
+	SampleArgs a{};
+	if (!error_cdfs_arg(cdfs, &a.cdfs)) return NGP_INVALID;
+	if (distortion_map && !distortion_dims_ok(map_width, map_height)) return NGP_INVALID;
+	a.n_rays = n_rays; a.ray_offset = ray_offset; a.n_rays_total_for_image_idx = n_rays_total;
+	a.max_samples = max_samples; a.rng = Rng{rng.state, rng.inc}; a.bitfield = bitfield;
+	a.ray_indices = ray_indices; a.rays = rays; a.numsteps = numsteps; a.coords = coords; a.counters = counters;
+	const DistMap dm{distortion_map, map_width, map_height};
+	return run_sampler(ds, cfg, stream, a, nullptr, distortion_map ? &dm : nullptr);
 }
 
 int ngp_nerf_training_pixels(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays, uint32_t ray_offset,
@@ -530,6 +549,46 @@ int ngp_envmap_deposit(void* stream, uint32_t width, uint32_t height, uint32_t n
 	});
 }
 
+// ---- lens distortion map: the stand-alone forms (distortion.h, distortion.hip) ----------------------------------------
+int ngp_nerf_distortion_lookup(void* stream, uint32_t width, uint32_t height, uint32_t n, const float* uv, uint32_t* texels,
+                               float* weights, const float* map, float* offsets) {
+	if (!distortion_dims_ok(width, height) || (n && (!uv || !texels || !weights)) || (offsets && !map)) return NGP_INVALID;
+	NERF_TRY({ distortion_lookup_device(width, height, n, uv, texels, weights, map, offsets, S(stream)); });
+}
+
+int ngp_nerf_distortion_lookup_host(uint32_t width, uint32_t height, uint32_t n, const float* uv, uint32_t* texels, float* weights,
+                                    const float* map, float* offsets) {
+	if (!distortion_dims_ok(width, height) || (n && (!uv || !texels || !weights)) || (offsets && !map)) return NGP_INVALID;
+	distortion_lookup_host(width, height, n, uv, texels, weights, map, offsets);
+	return NGP_OK;
+}
+
+uint64_t ngp_nerf_distortion_accumulator_words(uint32_t width, uint32_t height) {
+	return distortion_dims_ok(width, height) ? (uint64_t)distortion_acc_words64(width, height) : 0;
+}
+
+int ngp_nerf_distortion_deposit(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays_total, ngp_rng rng,
+                                const uint32_t* ray_counter, const uint32_t* ray_indices, const uint32_t* numsteps,
+                                const float* ray_gradients, uint32_t width, uint32_t height, uint64_t* accumulator) {
+	if (!ds || !cfg || !ray_counter || !ray_indices || !ray_gradients || !accumulator || n_rays_total == 0 ||
+	    !distortion_dims_ok(width, height) || (uint64_t)n_rays_total * ds->ds.n_images > 0xffffffffull)
+		return NGP_INVALID;
+	NERF_TRY({
+		DistDepositArgs a{};
+		// kept rays are distinct ids below n_rays_total: at most that many rows
+		a.n_rays_cap = n_rays_total; a.n_rays_total = n_rays_total; a.n_images = ds->ds.n_images;
+		a.snap = cfg->snap_to_pixel_centers != 0; a.rng = Rng{rng.state, rng.inc}; a.cams = ds->ds.d_cams;
+		a.ray_counter = ray_counter; a.ray_indices = ray_indices; a.numsteps = numsteps; a.ray_grad = ray_gradients;
+		a.w = width; a.h = height; a.acc = (unsigned long long*)accumulator;
+		distortion_deposit_rays(a, S(stream));
+	});
+}
+
+int ngp_nerf_distortion_gradient(void* stream, uint32_t width, uint32_t height, const uint64_t* accumulator, float* gradient) {
+	if (!distortion_dims_ok(width, height) || !accumulator || !gradient) return NGP_INVALID;
+	NERF_TRY({ distortion_gradient_f32(width, height, (const unsigned long long*)accumulator, gradient, S(stream)); });
+}
+
 int ngp_envmap_optimizer_step(void* stream, const char* optimizer_json, uint32_t step, float loss_scale, uint32_t n, float* params,
                               const float* gradient, float* first_moments, float* second_moments, uint32_t* param_steps, float* ema,
                               float* ema_params) {
@@ -592,7 +651,7 @@ int ngp_nerf_renderer_create(ngp_nerf_renderer** out) {
 }
 void ngp_nerf_renderer_destroy(ngp_nerf_renderer* r) { delete r; }
 int ngp_nerf_renderer_set_mode(ngp_nerf_renderer* r, int render_mode) {
-	if (!r || render_mode < (int)RENDER_AO || (render_mode > (int)RENDER_DEPTH && render_mode != (int)RENDER_ENCODING_VIS))
+	if (!r || render_mode < (int)RENDER_AO || (render_mode > (int)RENDER_DISTORTION && render_mode != (int)RENDER_ENCODING_VIS))
 		return NGP_INVALID;
 	r->render_mode = (uint32_t)render_mode;
 	return NGP_OK;
@@ -612,6 +671,12 @@ int ngp_nerf_renderer_set_envmap(ngp_nerf_renderer* r, const float* envmap, uint
 	r->envmap = envmap;
 	r->env_w = envmap ? width : 0;
 	r->env_h = envmap ? height : 0;
+	return NGP_OK;
+}
+
+int ngp_nerf_renderer_set_distortion_map(ngp_nerf_renderer* r, const float* map, uint32_t width, uint32_t height) {
+	if (!r || (map && !distortion_dims_ok(width, height))) return NGP_INVALID;
+	r->dist = DistMap{map, map ? width : 0, map ? height : 0};
 	return NGP_OK;
 }
 
@@ -670,7 +735,7 @@ int ngp_nerf_render(ngp_nerf_renderer* r, ngp_model* model, const ngp_nerf_confi
 		auto grad = [&](uint32_t n, float* coords) {
 			check_rc(ngp_input_gradient(model, s, 3, n, coords, 7, coords, 7, 128.0f));
 		};
-		render_frame(a, spp, ws, infer, out_rgba, s, grad);
+		render_frame(a, spp, ws, infer, out_rgba, s, grad, &r->dist);
 	});
 }
 

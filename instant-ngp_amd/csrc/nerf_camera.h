@@ -2,6 +2,8 @@
 // (compute_cam_gradient_train_nerf, testbed_nerf.cu:2014-2123, restated without float atomics) and the host side
 // (per-camera Adam states, adam_optimizer.h:128-309; update_transforms, testbed_nerf.cu:2980-3024).
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace ngp {
@@ -33,6 +35,20 @@ struct CamGradArgs {
 	float* pos_grad;            // [n_images x 3], accumulated
 	float* rot_grad;            // [n_images x 3], accumulated
 };
+// The distortion map's share of pass 1 (compute_cam_gradient_train_nerf's distortion branch, testbed_nerf.cu:2088-2099):
+// k_cam_ray_grad's DIST forms take these behind their arguments (CamGradArgsDist) and lane 0, which holds the ray's summed gd and
+// d = normalize(ray.d), also stores (inverse(mat3(xform_img)) * (gd - d * dot(gd, d))).xy, the image-plane gradient, into
+// dist_grad [n_rays_cap x 2] (zeros for a ray without samples). inverse is the general 3x3 inverse by the adjugate
+// (glm::inverse), not the transpose. mats: image i's column-major 3x3 at mats + i * mat_stride floats (a Camera's m, or
+// packed matrices). The six pose floats are computed by the same text as without DIST.
+struct CamDistArgs {
+	const float* mats;
+	uint32_t mat_stride;
+	float* dist_grad;
+};
+struct CamGradArgsDist : CamGradArgs {
+	CamDistArgs dist;
+};
 // lanes per ray of pass 1: 1, 8, 16 or 64 (camera pose refinement, has the measurement behind the choice;
 // a build with -DNGP_CAM_GRAD_LANES=n repeats it)
 #ifndef NGP_CAM_GRAD_LANES
@@ -43,6 +59,9 @@ constexpr uint32_t CAM_SUM_THREADS = 256;
 
 // Both passes on `s`. lanes (per ray, pass 1): 1, 8, 16 or 64.
 void camera_gradients(const CamGradArgs& a, uint32_t lanes, hipStream_t s);
+// Pass 1's DIST form; pass 2 only with image_sums (optimize_extrinsics on): with the distortion map alone no per-image
+// sum is wanted and k_cam_image_sum is not launched
+void camera_gradients_distortion(const CamGradArgs& a, const CamDistArgs& d, uint32_t lanes, bool image_sums, hipStream_t s);
 
 }  // namespace nerf
 

@@ -24,8 +24,12 @@ __device__ __forceinline__ uint32_t cam_image_idx(uint32_t ray_idx, uint32_t n_r
 	return ((ray_idx * n_images) / n_rays_total) % n_images;
 }
 
-template <uint32_t L>
-__global__ void __launch_bounds__(256) k_cam_ray_grad(CamGradArgs a) {
+template <bool DIST> using CamGradArgsK = std::conditional_t<DIST, CamGradArgsDist, CamGradArgs>;
+__device__ __forceinline__ CamDistArgs dist_of(const CamGradArgs&) { return CamDistArgs{}; }
+__device__ __forceinline__ CamDistArgs dist_of(const CamGradArgsDist& a) { return a.dist; }
+
+template <uint32_t L, bool DIST>
+__global__ void __launch_bounds__(256) k_cam_ray_grad(CamGradArgsK<DIST> a) {
 	const uint32_t n_kept = min(*a.ray_counter, a.n_rays_cap);
 	const uint32_t lane = threadIdx.x % L;
 	const float diag[3] = {a.aabb_max[0] - a.aabb_min[0], a.aabb_max[1] - a.aabb_min[1], a.aabb_max[2] - a.aabb_min[2]};
@@ -62,9 +66,29 @@ __global__ void __launch_bounds__(256) k_cam_ray_grad(CamGradArgs a) {
 			out[3] = d[1] * g[5] - d[2] * g[4];
 			out[4] = d[2] * g[3] - d[0] * g[5];
 			out[5] = d[0] * g[4] - d[1] * g[3];
+			if (DIST) {
+				const CamDistArgs dm = dist_of(a);
+				float* dg = dm.dist_grad + 2 * (size_t)i;
+				if (n == 0) {
+					dg[0] = dg[1] = 0.f;
+				} else {
+					const float dt = g[3] * d[0] + g[4] * d[1] + g[5] * d[2];
+					const float ox = g[3] - d[0] * dt, oy = g[4] - d[1] * dt, oz = g[5] - d[2] * dt;
+					const float* m = dm.mats + (size_t)dm.mat_stride * cam_image_idx(a.ray_indices[i], a.n_rays_total, a.n_images);
+					// the first two rows of inverse(mat3(m)) via the adjugate (glm::inverse), as k_mark_untrained takes it
+					const float a00 = m[0], a01 = m[1], a02 = m[2], a10 = m[3], a11 = m[4], a12 = m[5], a20 = m[6], a21 = m[7], a22 = m[8];
+					const float det = a00 * (a11 * a22 - a21 * a12) - a10 * (a01 * a22 - a21 * a02) + a20 * (a01 * a12 - a11 * a02);
+					const float id = 1.0f / det;
+					const float I0 = (a11 * a22 - a21 * a12) * id, I3 = -(a10 * a22 - a20 * a12) * id, I6 = (a10 * a21 - a20 * a11) * id;
+					const float I1 = -(a01 * a22 - a21 * a02) * id, I4 = (a00 * a22 - a20 * a02) * id, I7 = -(a00 * a21 - a20 * a01) * id;
+					dg[0] = I0 * ox + I3 * oy + I6 * oz;
+					dg[1] = I1 * ox + I4 * oy + I7 * oz;
+				}
+			}
 		}
 	}
 }
+
 
 __global__ void __launch_bounds__(CAM_SUM_THREADS) k_cam_image_sum(CamGradArgs a) {
 	const uint32_t n_kept = min(*a.ray_counter, a.n_rays_cap);
@@ -104,13 +128,32 @@ void camera_gradients(const CamGradArgs& a, uint32_t lanes, hipStream_t s) {
 	if (a.n_rays_cap == 0 || a.n_images == 0) return;
 	const uint32_t blocks = std::min(div_round_up((uint64_t)a.n_rays_cap * lanes, 256), 8u * 256u);
 	switch (lanes) {
-		case 1: k_cam_ray_grad<1><<<blocks, 256, 0, s>>>(a); break;
-		case 8: k_cam_ray_grad<8><<<blocks, 256, 0, s>>>(a); break;
-		case 16: k_cam_ray_grad<16><<<blocks, 256, 0, s>>>(a); break;
-		case 64: k_cam_ray_grad<64><<<blocks, 256, 0, s>>>(a); break;
+		case 1: k_cam_ray_grad<1, false><<<blocks, 256, 0, s>>>(a); break;
+		case 8: k_cam_ray_grad<8, false><<<blocks, 256, 0, s>>>(a); break;
+		case 16: k_cam_ray_grad<16, false><<<blocks, 256, 0, s>>>(a); break;
+		case 64: k_cam_ray_grad<64, false><<<blocks, 256, 0, s>>>(a); break;
 		default: throw Error("camera_gradients: lanes per ray must be 1, 8, 16 or 64");
 	}
 	NGP_HIP(hipGetLastError());
+	k_cam_image_sum<<<a.n_images, CAM_SUM_THREADS, 0, s>>>(a);
+	NGP_HIP(hipGetLastError());
+}
+
+void camera_gradients_distortion(const CamGradArgs& a, const CamDistArgs& d, uint32_t lanes, bool image_sums, hipStream_t s) {
+	if (a.n_rays_cap == 0 || a.n_images == 0) return;
+	const uint32_t blocks = std::min(div_round_up((uint64_t)a.n_rays_cap * lanes, 256), 8u * 256u);
+	CamGradArgsDist ad;
+	(CamGradArgs&)ad = a;
+	ad.dist = d;
+	switch (lanes) {
+		case 1: k_cam_ray_grad<1, true><<<blocks, 256, 0, s>>>(ad); break;
+		case 8: k_cam_ray_grad<8, true><<<blocks, 256, 0, s>>>(ad); break;
+		case 16: k_cam_ray_grad<16, true><<<blocks, 256, 0, s>>>(ad); break;
+		case 64: k_cam_ray_grad<64, true><<<blocks, 256, 0, s>>>(ad); break;
+		default: throw Error("camera_gradients: lanes per ray must be 1, 8, 16 or 64");
+	}
+	NGP_HIP(hipGetLastError());
+	if (!image_sums) return;
 	k_cam_image_sum<<<a.n_images, CAM_SUM_THREADS, 0, s>>>(a);
 	NGP_HIP(hipGetLastError());
 }
@@ -432,15 +475,11 @@ int ngp_pose_apply(const float* xform, const float* rot_offset, const float* pos
 	return NGP_OK;
 }
 
-int ngp_nerf_camera_gradients(const ngp_nerf_config* cfg, void* stream, uint32_t n_rays_total, uint32_t n_images,
-                              const uint32_t* ray_counter, const uint32_t* ray_indices, const float* rays,
-                              const uint32_t* numsteps, const float* coords, const float* coords_gradient,
-                              uint32_t gradient_stride, float* pos_gradient, float* rot_gradient) {
-	if (!cfg || !ray_counter || !ray_indices || !rays || !numsteps || !coords || !coords_gradient || !pos_gradient || !rot_gradient ||
-	    n_rays_total == 0 || n_images == 0 || gradient_stride < 7 || (uint64_t)n_rays_total * n_images > 0xffffffffull)
-		return invalid("invalid argument: camera gradients: null pointer, no rays or images, gradient stride < 7 or n_rays_total * n_images >= 2^32");
-	for (int k = 0; k < 3; ++k)
-		if (!(cfg->aabb_max[k] > cfg->aabb_min[k])) return invalid("invalid argument: camera gradients: empty training box");
+// ngp_nerf_camera_gradients and ngp_nerf_distortion_ray_gradients (mats null: the former)
+static int camera_gradients_abi(const ngp_nerf_config* cfg, void* stream, uint32_t n_rays_total, uint32_t n_images,
+                                const uint32_t* ray_counter, const uint32_t* ray_indices, const float* rays, const uint32_t* numsteps,
+                                const float* coords, const float* coords_gradient, uint32_t gradient_stride, float* pos_gradient,
+                                float* rot_gradient, const float* mats, float* dist_grad) {
 	try {
 		nerf::CamGradArgs a{};
 		// kept rays are distinct ids below n_rays_total: at most that many rows
@@ -460,12 +499,42 @@ int ngp_nerf_camera_gradients(const ngp_nerf_config* cfg, void* stream, uint32_t
 			ws.n = need;
 		}
 		a.ray_grad = ws.p; a.pos_grad = pos_gradient; a.rot_grad = rot_gradient;
-		nerf::camera_gradients(a, nerf::CAM_GRAD_LANES, (hipStream_t)stream);
+		if (mats) nerf::camera_gradients_distortion(a, nerf::CamDistArgs{mats, 9, dist_grad}, nerf::CAM_GRAD_LANES, pos_gradient != nullptr,
+		                                            (hipStream_t)stream);
+		else nerf::camera_gradients(a, nerf::CAM_GRAD_LANES, (hipStream_t)stream);
 		return NGP_OK;
 	} catch (const std::exception& e) {
 		ngp::set_last_error(e.what());
 		return NGP_ERROR;
 	}
+}
+
+int ngp_nerf_camera_gradients(const ngp_nerf_config* cfg, void* stream, uint32_t n_rays_total, uint32_t n_images,
+                              const uint32_t* ray_counter, const uint32_t* ray_indices, const float* rays,
+                              const uint32_t* numsteps, const float* coords, const float* coords_gradient,
+                              uint32_t gradient_stride, float* pos_gradient, float* rot_gradient) {
+	if (!cfg || !ray_counter || !ray_indices || !rays || !numsteps || !coords || !coords_gradient || !pos_gradient || !rot_gradient ||
+	    n_rays_total == 0 || n_images == 0 || gradient_stride < 7 || (uint64_t)n_rays_total * n_images > 0xffffffffull)
+		return invalid("invalid argument: camera gradients: null pointer, no rays or images, gradient stride < 7 or n_rays_total * n_images >= 2^32");
+	for (int k = 0; k < 3; ++k)
+		if (!(cfg->aabb_max[k] > cfg->aabb_min[k])) return invalid("invalid argument: camera gradients: empty training box");
+	return camera_gradients_abi(cfg, stream, n_rays_total, n_images, ray_counter, ray_indices, rays, numsteps, coords, coords_gradient,
+	                            gradient_stride, pos_gradient, rot_gradient, nullptr, nullptr);
+}
+
+int ngp_nerf_distortion_ray_gradients(const ngp_nerf_config* cfg, void* stream, uint32_t n_rays_total, uint32_t n_images,
+                                      const uint32_t* ray_counter, const uint32_t* ray_indices, const float* rays,
+                                      const uint32_t* numsteps, const float* coords, const float* coords_gradient,
+                                      uint32_t gradient_stride, float* pos_gradient, float* rot_gradient, const float* camera_matrices,
+                                      float* ray_gradients) {
+	if (!cfg || !ray_counter || !ray_indices || !rays || !numsteps || !coords || !coords_gradient || !camera_matrices || !ray_gradients ||
+	    (pos_gradient == nullptr) != (rot_gradient == nullptr) || n_rays_total == 0 || n_images == 0 || gradient_stride < 7 ||
+	    (uint64_t)n_rays_total * n_images > 0xffffffffull)
+		return invalid("invalid argument: distortion ray gradients: null pointer, one pose gradient without the other, no rays or images, gradient stride < 7 or n_rays_total * n_images >= 2^32");
+	for (int k = 0; k < 3; ++k)
+		if (!(cfg->aabb_max[k] > cfg->aabb_min[k])) return invalid("invalid argument: distortion ray gradients: empty training box");
+	return camera_gradients_abi(cfg, stream, n_rays_total, n_images, ray_counter, ray_indices, rays, numsteps, coords, coords_gradient,
+	                            gradient_stride, pos_gradient, rot_gradient, camera_matrices, ray_gradients);
 }
 
 }  // extern "C"

@@ -114,6 +114,7 @@ inline void nerf_set_error(const char* m) { ngp::set_last_error(m); }
 inline void check_rc(int rc) { if (rc != NGP_OK) throw Error(ngp_last_error()); }
 
 inline bool envmap_dims_ok(uint32_t w, uint32_t h) { return w >= 1 && h >= 1 && w <= 8192 && h <= 8192; }
+inline bool distortion_dims_ok(uint32_t w, uint32_t h) { return envmap_dims_ok(w, h); }  // the same bounds
 
 // ngp_nerf_error_cdfs -> ErrorCdfs (null: none). The position CDFs come as a pair with a resolution; without
 // cdf_x_cond_y the other two members are not looked at.
@@ -135,7 +136,9 @@ inline bool error_cdfs_arg(const ngp_nerf_error_cdfs* c, ErrorCdfs* out) {
 // comes back in *exposure_ray_grad for exposure_gradients, and holds until the thread's next loss pass.
 int run_compute_loss(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, LossArgs a, bool exposure_grad = false,
                      const float** exposure_ray_grad = nullptr);
-int run_sampler(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, SampleArgs a, const Camera* cams);
+// dist (optional): the distortion map the rays are traced through
+int run_sampler(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, SampleArgs a, const Camera* cams,
+                const DistMap* dist = nullptr);
 
 }  // namespace nerf
 }  // namespace ngp
@@ -242,7 +245,7 @@ struct ngp_nerf_trainer {
 	// gradient kernels read the ray buffers after the training pass: the next sampler, prelaunched under that pass,
 	// then writes the other set (last read by the step before this one, complete once this step's counters are
 	// published) instead of waiting for this step's release
-	bool two_sets() const { return early() || (cam.optimize_extrinsics != 0 && !dp()); }
+	bool two_sets() const { return early() || ((cam.optimize_extrinsics != 0 || dist.optimize) && !dp()); }
 	Buf loss_state;  // compute_loss: pass 1's per-sample compositing state for pass 2 (LossArgs::state)
 	// depth supervision (ngp_nerf_trainer_set_depth_supervision): off at 0, or while no image of the dataset has depth
 	float depth_lambda = 0.0f;
@@ -313,6 +316,28 @@ struct ngp_nerf_trainer {
 	const float* envmap_inference() const {
 		return (const float*)(env.ema_valid ? env.ema_out.p : env.params.p);
 	}
+	// Lens distortion map (Testbed::m_distortion and Training::optimize_distortion; testbed.cu:4066-4076,
+	// testbed_nerf.cu:2088-2099, 3811-3818; distortion.h): fp32 parameters [h][w][2], the offset the trainer's sampler adds
+	// to every ray's dir.xy whenever a map is bound, whether `optimize` is on or off. With `optimize` on the step takes the
+	// input gradient as pose refinement does, deposits every kept ray's image-plane gradient into the exact accumulator
+	// `acc`, which starts from zero after every update, and every n_steps_between_cam_updates steps (the counter shared
+	// with poses and exposure) turns it into `grad` and steps the map's optimizer on the step's stream. Not bound: the
+	// step issues exactly the launches it would without any of this.
+	struct Distortion {
+		uint32_t w = 0, h = 0;
+		Buf params, ema, ema_out, m1, m2, steps, grad, acc, ray_grad;
+		uint32_t step = 0;          // optimizer steps taken
+		bool ema_valid = false;     // ema_out holds the debiased EMA (an optimizer with an Ema wrapper has stepped)
+		AdamConfig opt;             // the "distortion_map" section's optimizer; opt_set false: the main trainer's
+		bool opt_set = false;
+		uint32_t def_w = 32, def_h = 32;  // the section's resolution: the map `optimize` creates when none is bound
+		bool optimize = false;
+		size_t n() const { return (size_t)w * h * 2; }
+		bool bound() const { return w != 0; }
+		DistMap view() const { return DistMap{bound() ? (const float*)params.p : nullptr, w, h}; }
+	} dist;
+	const AdamConfig& distortion_optimizer() const { return dist.opt_set ? dist.opt : trainer_adam_config(trainer); }
+	const float* distortion_inference() const { return (const float*)(dist.ema_valid ? dist.ema_out.p : dist.params.p); }
 	ErrorCdfs sampling_cdfs() const {
 		ErrorCdfs e{};
 		if (!em_cdf_valid || !em_cdf_w || !em_cdf_h) return e;

@@ -6,6 +6,7 @@
 #include "nerf_device.h"
 #include "rng.h"
 #include "envmap.h"
+#include "distortion.h"
 
 namespace ngp {
 namespace nerf {
@@ -36,7 +37,13 @@ struct Payload {  // NerfPayload (nerf.h:32-40)
 	uint32_t idx, n_steps, alive;
 };
 
-__global__ void k_render_init(RenderArgs a, Payload* __restrict__ pay, float* __restrict__ rgba) {
+// DIST: the distortion map of the arguments adds its offset at the pixel's uv to dir.xy after the lens (render_with_lens_distortion)
+template <bool DIST> using RenderArgsK = std::conditional_t<DIST, RenderArgsDist, RenderArgs>;
+__device__ __forceinline__ DistMap dist_of(const RenderArgs&) { return DistMap{}; }
+__device__ __forceinline__ DistMap dist_of(const RenderArgsDist& a) { return a.dist; }
+
+template <bool DIST>
+__global__ void k_render_init(RenderArgsK<DIST> a, Payload* __restrict__ pay, float* __restrict__ rgba) {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 	const uint32_t W = a.width, H = a.height;
 	if (i >= W * H) return;
@@ -50,6 +57,13 @@ __global__ void k_render_init(RenderArgs a, Payload* __restrict__ pay, float* __
 	float dx = (u - a.screen_center[0]) * (float)W / a.focal[0];
 	float dy = (v - a.screen_center[1]) * (float)H / a.focal[1];
 	lens_undistort(a.lens_mode, a.lens, &dx, &dy);
+	if (DIST) {
+		const DistMap dm = dist_of(a);
+		float fx, fy;
+		distortion_offset(dm.data, dm.w, dm.h, u, v, &fx, &fy);
+		dx += fx;
+		dy += fy;
+	}
 	const float* m = a.cam;
 	V3 d = v3(m[0] * dx + m[3] * dy + m[6], m[1] * dx + m[4] * dy + m[7], m[2] * dx + m[5] * dy + m[8]);
 	V3 o = v3(m[9] + d.x * a.near_distance, m[10] + d.y * a.near_distance, m[11] + d.z * a.near_distance);
@@ -251,7 +265,8 @@ __global__ void k_render_fill(uint32_t n, f32x4 bg, float* __restrict__ frame) {
 }
 // The frame pre-filled with the environment map in each pixel's ray direction (testbed_nerf.cu:2315-2319); the
 // direction is the one k_render_init gives the pixel's payload (same operations)
-__global__ void k_render_fill_envmap(RenderArgs a, float* __restrict__ frame) {
+template <bool DIST>
+__global__ void k_render_fill_envmap(RenderArgsK<DIST> a, float* __restrict__ frame) {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 	const uint32_t W = a.width, H = a.height;
 	if (i >= W * H) return;
@@ -262,6 +277,13 @@ __global__ void k_render_fill_envmap(RenderArgs a, float* __restrict__ frame) {
 	float dx = (u - a.screen_center[0]) * (float)W / a.focal[0];
 	float dy = (v - a.screen_center[1]) * (float)H / a.focal[1];
 	lens_undistort(a.lens_mode, a.lens, &dx, &dy);
+	if (DIST) {
+		const DistMap dm = dist_of(a);
+		float fx, fy;
+		distortion_offset(dm.data, dm.w, dm.h, u, v, &fx, &fy);
+		dx += fx;
+		dy += fy;
+	}
 	const float* m = a.cam;
 	const V3 d = v3(m[0] * dx + m[3] * dy + m[6], m[1] * dx + m[4] * dy + m[7], m[2] * dx + m[5] * dy + m[8]);
 	const float inv = 1.0f / sqrtf(d.x * d.x + d.y * d.y + d.z * d.z);
@@ -272,17 +294,59 @@ __global__ void k_render_fill_envmap(RenderArgs a, float* __restrict__ frame) {
 	for (int k = 0; k < 4; ++k) c[k] = envmap_mix(t, e0[k], e1[k], e2[k], e3[k]);
 	*(f32x4*)(frame + 4 * (size_t)i) = c;
 }
+
+// hsv_to_rgb and to_rgb (common_device.cuh:802-827)
+__device__ inline void hsv_to_rgb(float h, float s, float v, float rgb[3]) {
+	if (s == 0.0f) {
+		rgb[0] = rgb[1] = rgb[2] = v;
+		return;
+	}
+	h = fmodf(h, 1.0f) * 6.0f;
+	const int i = (int)h;
+	const float f = h - (float)i;
+	const float p = v * (1.0f - s), q = v * (1.0f - s * f), t = v * (1.0f - s * (1.0f - f));
+	switch (i) {
+		case 0: rgb[0] = v; rgb[1] = t; rgb[2] = p; break;
+		case 1: rgb[0] = q; rgb[1] = v; rgb[2] = p; break;
+		case 2: rgb[0] = p; rgb[1] = v; rgb[2] = t; break;
+		case 3: rgb[0] = p; rgb[1] = q; rgb[2] = v; break;
+		case 4: rgb[0] = t; rgb[1] = p; rgb[2] = v; break;
+		default: rgb[0] = v; rgb[1] = p; rgb[2] = q; break;
+	}
+}
+__device__ inline void to_rgb(float x, float y, float rgb[3]) {
+	const float PI = 3.14159265358979323846f;
+	hsv_to_rgb(atan2f(y, x) / (2.0f * PI) + 0.5f, 1.0f, sqrtf(x * x + y * y), rgb);
+}
+// ERenderMode::Distortion (testbed_nerf.cu:2331-2344): every pixel to_rgb(offset * 50) with alpha 1, the offset read at
+// the pixel's centre; no ray is marched. dm.data null: the offset is zero.
+__global__ void k_render_distortion(uint32_t W, uint32_t H, DistMap dm, float* __restrict__ out) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= W * H) return;
+	const uint32_t x = i % W, y = i / W;
+	float ox = 0.0f, oy = 0.0f;
+	if (dm.data) distortion_offset(dm.data, dm.w, dm.h, ((float)x + 0.5f) / (float)W, ((float)y + 0.5f) / (float)H, &ox, &oy);
+	float rgb[3];
+	to_rgb(ox * 50.0f, oy * 50.0f, rgb);
+	*(f32x4*)(out + 4 * (size_t)i) = f32x4{rgb[0], rgb[1], rgb[2], 1.0f};
+}
 __global__ void k_render_accumulate(uint32_t n4, float w, const float* __restrict__ frame, float* __restrict__ acc, bool first) {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i < n4) acc[i] = (first ? 0.f : acc[i]) + frame[i] * w;
 }
 
 void render_frame(const RenderArgs& a, uint32_t spp, RenderWorkspace& ws, const std::function<void(uint32_t, const float*, f16*)>& infer,
-                  float* out, hipStream_t s, const std::function<void(uint32_t, float*)>& grad) {
-	NGP_CHECK((a.render_mode <= RENDER_DEPTH || a.render_mode == RENDER_ENCODING_VIS) && (a.render_mode != RENDER_NORMALS || grad),
-	          "render: AO, Shade, Normals, Positions, Depth and EncodingVis are implemented");
+                  float* out, hipStream_t s, const std::function<void(uint32_t, float*)>& grad, const DistMap* dist) {
+	NGP_CHECK((a.render_mode <= RENDER_DISTORTION || a.render_mode == RENDER_ENCODING_VIS) && (a.render_mode != RENDER_NORMALS || grad),
+	          "render: AO, Shade, Normals, Positions, Depth, Distortion and EncodingVis are implemented");
 	const uint32_t n_px = a.width * a.height;
 	if (n_px == 0) return;
+	const DistMap dm = dist && dist->data ? *dist : DistMap{};
+	if (a.render_mode == RENDER_DISTORTION) {  // the same frame for every sample: written once
+		k_render_distortion<<<div_round_up(n_px, 256), 256, 0, s>>>(a.width, a.height, dm, out);
+		NGP_HIP(hipGetLastError());
+		return;
+	}
 	const uint32_t MARCH_ITER = 10000, MIN_STEPS = 1, MAX_STEPS = 8, TARGET_QUERIES = 2 * 1024 * 1024;
 	Payload* pay[2] = {(Payload*)ws.payload[0], (Payload*)ws.payload[1]};
 	float* rgba[2] = {ws.rgba[0], ws.rgba[1]};
@@ -290,10 +354,15 @@ void render_frame(const RenderArgs& a, uint32_t spp, RenderWorkspace& ws, const 
 	for (uint32_t sidx = 0; sidx < spp; ++sidx) {
 		RenderArgs r = a;
 		r.sample_index = a.sample_index + sidx;
-		if (a.envmap) k_render_fill_envmap<<<div_round_up(n_px, 256), 256, 0, s>>>(r, ws.frame);
+		RenderArgsDist rd;  // the DIST forms' arguments
+		(RenderArgs&)rd = r;
+		rd.dist = dm;
+		if (a.envmap && dm.data) k_render_fill_envmap<true><<<div_round_up(n_px, 256), 256, 0, s>>>(rd, ws.frame);
+		else if (a.envmap) k_render_fill_envmap<false><<<div_round_up(n_px, 256), 256, 0, s>>>(r, ws.frame);
 		else k_render_fill<<<div_round_up(n_px, 256), 256, 0, s>>>(n_px, f32x4{a.background[0], a.background[1], a.background[2],
 		                                                                         a.background[3]}, ws.frame);
-		k_render_init<<<div_round_up(n_px, 128), 128, 0, s>>>(r, pay[0], rgba[0]);
+		if (dm.data) k_render_init<true><<<div_round_up(n_px, 128), 128, 0, s>>>(rd, pay[0], rgba[0]);
+		else k_render_init<false><<<div_round_up(n_px, 128), 128, 0, s>>>(r, pay[0], rgba[0]);
 		NGP_HIP(hipGetLastError());
 		NGP_HIP(hipMemsetAsync(ws.counters, 0, 8, s));  // counters[1]: hits (whole trace)
 		uint32_t n_alive = n_px, it = 1, db = 0;

@@ -9,6 +9,7 @@
 #include "profiler.h"
 #include "rng.h"
 #include "nerf_pixel.h"
+#include "distortion.h"
 
 namespace ngp {
 namespace nerf {
@@ -23,9 +24,11 @@ struct RaySetup {
 // CDF: the ray's pixel comes from the error map's CDFs `e` (a separate instantiation: the uniform one carries none of it)
 // TEX: the dataset holds a Half or Float image (Dataset::tex): `pixels` is then the image table, ImageRef [n_images],
 // and the texel is read by its image's type; otherwise it is the packed RGBA8 buffer
-template <bool CDF, bool TEX>
+// DIST: the distortion map `dm` adds its offset at the ray's (u, v) to dir.xy after the lens (uv_to_ray,
+// common_device.cuh:443-510); the rng draws and the pixel choice are those of the form without it
+template <bool CDF, bool TEX, bool DIST>
 __device__ RaySetup setup_ray(const Camera* cams, const void* pixels, uint32_t n_images, const ngp_nerf_config& cfg,
-                              uint32_t ig, uint32_t n_rays_div, Rng rng, const Cone& cone, const ErrorCdfs& e) {
+                              uint32_t ig, uint32_t n_rays_div, Rng rng, const Cone& cone, const ErrorCdfs& e, const DistMap& dm) {
 	RaySetup r;
 	r.valid = false;
 	pcg_advance(rng, (uint64_t)ig * N_MAX_RANDOM_SAMPLES_PER_RAY);
@@ -49,6 +52,12 @@ __device__ RaySetup setup_ray(const Camera* cams, const void* pixels, uint32_t n
 	float dx = (u - cam.principal[0]) * (float)cam.width / cam.focal[0];
 	float dy = (v - cam.principal[1]) * (float)cam.height / cam.focal[1];
 	lens_undistort(cam.lens_mode, cam.lens, &dx, &dy);
+	if (DIST) {
+		float ox, oy;
+		distortion_offset(dm.data, dm.w, dm.h, u, v, &ox, &oy);
+		dx += ox;
+		dy += oy;
+	}
 	const float dz = 1.0f;
 	const float* m = cam.m;
 	r.d = v3(m[0] * dx + m[3] * dy + m[6] * dz, m[1] * dx + m[4] * dy + m[7] * dz, m[2] * dx + m[5] * dy + m[8] * dz);
@@ -351,15 +360,16 @@ __device__ __forceinline__ unsigned long long sampler_clock() {
 
 // generate_training_samples_nerf pass 1: count the occupied steps of ray i (lane L of its group), keep their t;
 // returns the count (uniform over the group).
-template <bool CONE0, bool CDF, bool TEX>
+template <bool CONE0, bool CDF, bool TEX, bool DIST>
 __device__ __forceinline__ uint32_t count_ray(const Camera* __restrict__ cams, const void* __restrict__ pixels, uint32_t n_images,
                                               const ngp_nerf_config& cfg, const SampleArgs& a, uint32_t* __restrict__ nsteps,
                                               float* __restrict__ tbuf, RayGeo* __restrict__ geo, const Cone& cone, uint32_t i,
-                                              uint32_t L) {
+                                              uint32_t L, const DistMap& dm) {
 	constexpr uint32_t RGk = sampler_rg<CONE0>();
 	if (!CONE0 && NGP_SAMPLER_PRIO) __builtin_amdgcn_s_setprio(NGP_SAMPLER_PRIO);
 	SAMPLER_STAT(const unsigned long long ck0 = sampler_clock();)
-	const RaySetup r = setup_ray<CDF, TEX>(cams, pixels, n_images, cfg, i + a.ray_offset, a.n_rays_total_for_image_idx, a.rng, cone, a.cdfs);
+	const RaySetup r = setup_ray<CDF, TEX, DIST>(cams, pixels, n_images, cfg, i + a.ray_offset, a.n_rays_total_for_image_idx, a.rng, cone,
+	                                             a.cdfs, dm);
 	SAMPLER_STAT(const unsigned long long ck1 = sampler_clock(); unsigned long long ck2 = ck1, ck_g = 0, ck_o = 0, ck_q = 0;)
 	uint32_t j = 0;
 	if (r.valid) {
@@ -551,9 +561,14 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 // The count pass, and per wave the sum of its rays' counts and the number of its rays with samples (wsum[2 w],
 // wsum[2 w + 1]): the sampler's prefix sums over rays become a scan over waves (k_sample_bscan, ~2 K values at
 // the Lego stand-in's ~32 K rays) plus an in-wave prefix in k_sample_write, instead of a scan over the rays.
-template <bool CONE0, bool CDF, bool TEX>
+// DIST: the launch's arguments carry a distortion map (SampleArgsDist), which setup_ray adds to the rays
+template <bool DIST> using SampleArgsK = std::conditional_t<DIST, SampleArgsDist, SampleArgs>;
+__device__ __forceinline__ DistMap dist_of(const SampleArgs&) { return DistMap{}; }
+__device__ __forceinline__ DistMap dist_of(const SampleArgsDist& a) { return a.dist; }
+
+template <bool CONE0, bool CDF, bool TEX, bool DIST>
 __global__ void __launch_bounds__(256) k_sample_count(const Camera* __restrict__ cams, const void* __restrict__ pixels,
-                                                      uint32_t n_images, const ngp_nerf_config cfg, SampleArgs a,
+                                                      uint32_t n_images, const ngp_nerf_config cfg, SampleArgsK<DIST> a,
                                                       uint32_t* __restrict__ nsteps, float* __restrict__ tbuf,
                                                       RayGeo* __restrict__ geo, const Cone cone, uint32_t* __restrict__ wsum) {
 	constexpr uint32_t RGk = sampler_rg<CONE0>();
@@ -561,7 +576,7 @@ __global__ void __launch_bounds__(256) k_sample_count(const Camera* __restrict__
 	const uint32_t i = gid / RGk, L = gid % RGk;
 	const bool live = i < a.n_rays;  // whole rows
 	uint32_t j = 0;
-	if (live) j = count_ray<CONE0, CDF, TEX>(cams, pixels, n_images, cfg, a, nsteps, tbuf, geo, cone, i, L);
+	if (live) j = count_ray<CONE0, CDF, TEX, DIST>(cams, pixels, n_images, cfg, a, nsteps, tbuf, geo, cone, i, L, dist_of(a));
 	const bool head = live && L == 0;
 	const uint32_t sum = wave_sum(head ? j : 0u);
 	const uint32_t nz = (uint32_t)__popcll(__ballot(head && j > 0));
@@ -715,24 +730,27 @@ static uint32_t sample_count_waves(uint32_t n_rays, uint32_t rgk) {
 }
 size_t sample_tmp_u32(uint32_t n_rays) { return n_rays + 4 * (size_t)sample_count_waves(n_rays, std::max(RG, sampler_rg<true>())); }
 
-// k_sample_count's 8 instantiations by their switches. Bit 0: cone stepping (CONE0 = false), bit 1: CDF, bit 2: TEX.
+// k_sample_count's 8 instantiations by their switches, without and with a distortion map. Bit 0: cone stepping (CONE0 = false), bit 1: CDF, bit 2: TEX.
 // The order is the order the kernels are instantiated in, and their machine code depends on it: each CONE0 = true form
 // before the cone-stepping form it shares setup_ray<CDF, TEX> with, as the launch code listed them before there was a
 // table. With CONE0 as a plain bit 0 the four cone-stepping kernels come out scheduled differently (60 VGPRs for 62,
 // one or two instructions more); tools/kernel_asm_diff.py against the commit before shows it.
-using SampleCount = void (*)(const Camera*, const void*, uint32_t, const ngp_nerf_config, SampleArgs, uint32_t*, float*, RayGeo*,
+template <bool DIST>
+using SampleCount = void (*)(const Camera*, const void*, uint32_t, const ngp_nerf_config, SampleArgsK<DIST>, uint32_t*, float*, RayGeo*,
                              const Cone, uint32_t*);
-template <size_t... I>
-static SampleCount sample_count_kernel(uint32_t i, std::index_sequence<I...>) {
-	static const SampleCount k[] = {k_sample_count<(I & 1) == 0, (I & 2) != 0, (I & 4) != 0>...};
+template <bool DIST, size_t... I>
+static SampleCount<DIST> sample_count_kernel(uint32_t i, std::index_sequence<I...>) {
+	static const SampleCount<DIST> k[] = {k_sample_count<(I & 1) == 0, (I & 2) != 0, (I & 4) != 0, DIST>...};
 	return k[i];
 }
-static SampleCount sample_count_kernel(bool cone0, bool cdf, bool tex) {
-	return sample_count_kernel((cone0 ? 0u : 1u) | (cdf ? 2u : 0u) | (tex ? 4u : 0u), std::make_index_sequence<8>{});
+// DIST is no bit of the index: the 8 forms without a map first, in their order, then the 8 with one
+template <bool DIST>
+static SampleCount<DIST> sample_count_kernel(bool cone0, bool cdf, bool tex) {
+	return sample_count_kernel<DIST>((cone0 ? 0u : 1u) | (cdf ? 2u : 0u) | (tex ? 4u : 0u), std::make_index_sequence<8>{});
 }
 
 void sample_rays(const Dataset& ds, const ngp_nerf_config& cfg, const SampleArgs& a, uint32_t* tmp, float* tmpf, hipStream_t s,
-                 const Camera* cams) {
+                 const Camera* cams, const DistMap* dist) {
 	if (a.n_rays == 0) return;
 	if (!cams) cams = ds.d_cams;
 	NGP_CHECK(tmpf != nullptr, "sample_rays: float scratch of sample_tmp_f32(n_rays) floats required");
@@ -752,9 +770,17 @@ void sample_rays(const Dataset& ds, const ngp_nerf_config& cfg, const SampleArgs
 		// pixels from the error map's CDFs, or a Half or Float image in the dataset (the TEX forms read the image table): the
 		// count pass's other instantiations (the write pass copies what it stored)
 		const bool tex = ds.tex();
-		const SampleCount count = sample_count_kernel(cone0, a.cdfs.any(), tex);
 		const void* pixels = tex ? (const void*)ds.d_images : (const void*)ds.d_pixels;
-		count<<<cone0 ? blocks0 : blocks, NGP_SAMPLER_BLOCK, 0, s>>>(cams, pixels, ds.n_images, cfg, a, nsteps, tbuf, geo, cone, wsum);
+		const SampleCount<false> count = sample_count_kernel<false>(cone0, a.cdfs.any(), tex);
+		if (dist && dist->data) {  // a distortion map: the DIST forms
+			SampleArgsDist ad;
+			(SampleArgs&)ad = a;
+			ad.dist = *dist;
+			sample_count_kernel<true>(cone0, a.cdfs.any(), tex)<<<cone0 ? blocks0 : blocks, NGP_SAMPLER_BLOCK, 0, s>>>(
+			    cams, pixels, ds.n_images, cfg, ad, nsteps, tbuf, geo, cone, wsum);
+		} else {
+			count<<<cone0 ? blocks0 : blocks, NGP_SAMPLER_BLOCK, 0, s>>>(cams, pixels, ds.n_images, cfg, a, nsteps, tbuf, geo, cone, wsum);
+		}
 		NGP_HIP(hipGetLastError());
 	}
 	NGP_CHECK(nw == (cone0 ? blocks0 : blocks) * (NGP_SAMPLER_BLOCK / 64) && 64 % rgk == 0, "sampler: count waves");

@@ -279,6 +279,32 @@ int ngp_nerf_save_snapshot(ngp_nerf_trainer* t, void* stream, const char* path, 
 			}
 			snap["envmap"] = em;
 		}
+		// engine extension (the reference does not save m_distortion): the lens distortion map and its optimizer
+		if (t->dist.bound()) {
+			NGP_HIP(hipDeviceSynchronize());
+			const ngp_nerf_trainer::Distortion& d = t->dist;
+			const size_t n = d.n();
+			auto put = [&](Value& to, const char* name, const void* p) {
+				auto h = device_to_host<float>(p, n);
+				to[name] = Value::bin(h.data(), n * 4);
+			};
+			Value dm = Value::object();
+			dm["width"] = Value::uint(d.w);
+			dm["height"] = Value::uint(d.h);
+			put(dm, "params_binary", d.params.p);
+			if (include_optimizer_state) {
+				Value opt = Value::object();
+				opt["current_step"] = Value::uint(d.step);
+				opt["ema_valid"] = Value::uint(d.ema_valid ? 1 : 0);
+				put(opt, "ema_binary", d.ema.p);
+				put(opt, "ema_params_binary", d.ema_out.p);
+				put(opt, "first_moments_binary", d.m1.p);
+				put(opt, "second_moments_binary", d.m2.p);
+				put(opt, "param_steps_binary", d.steps.p);
+				dm["optimizer"] = opt;
+			}
+			snap["distortion_map"] = dm;
+		}
 		write_snapshot(path, root, snap, compress);
 	});
 }
@@ -379,6 +405,34 @@ int ngp_nerf_load_snapshot(ngp_nerf_trainer* t, void* stream, const char* path) 
 				up(e.m1, bin(*opt, "first_moments_binary"));
 				up(e.m2, bin(*opt, "second_moments_binary"));
 				up(e.steps, bin(*opt, "param_steps_binary"));
+			}
+		}
+		// the lens distortion map likewise
+		if (const Value* dm = snap.find("distortion_map")) {
+			const uint32_t w = (uint32_t)dm->at("width").number(), h = (uint32_t)dm->at("height").number();
+			NGP_CHECK(distortion_dims_ok(w, h), "snapshot: distortion_map resolution");
+			const size_t n = (size_t)w * h * 2;
+			auto bin = [&](const Value& v, const char* name) -> const float* {
+				const Value* b = v.find(name);
+				if (!b) return nullptr;
+				NGP_CHECK(b->s.size() == n * 4, std::string("snapshot: distortion_map ") + name + " size");
+				return (const float*)b->s.data();
+			};
+			const float* params = bin(*dm, "params_binary");
+			NGP_CHECK(params, "snapshot: distortion_map without params_binary");
+			check_rc(ngp_nerf_trainer_set_distortion_map(t, w, h, params));
+			ngp_nerf_trainer::Distortion& d = t->dist;
+			auto up = [&](Buf& dst, const float* src) {
+				if (src) NGP_HIP(hipMemcpy(dst.p, src, n * 4, hipMemcpyHostToDevice));
+			};
+			if (const Value* opt = dm->find("optimizer")) {
+				d.step = (uint32_t)opt->number_or("current_step", 0.0);
+				d.ema_valid = opt->number_or("ema_valid", 0.0) != 0.0;
+				up(d.ema, bin(*opt, "ema_binary"));
+				up(d.ema_out, bin(*opt, "ema_params_binary"));
+				up(d.m1, bin(*opt, "first_moments_binary"));
+				up(d.m2, bin(*opt, "second_moments_binary"));
+				up(d.steps, bin(*opt, "param_steps_binary"));
 			}
 		}
 		NGP_HIP(hipStreamSynchronize(s));

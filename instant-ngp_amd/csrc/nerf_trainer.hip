@@ -9,6 +9,9 @@
 // rays_per_batch adaptation.
 #include <chrono>
 
+#include <cstddef>
+
+#include "distortion.h"
 #include "nerf_host.h"
 #include "profiler.h"
 
@@ -161,10 +164,19 @@ static const char* const EXPOSURE_VS_DATA_PARALLEL =
 	"exposure optimisation is single-GPU: the per-image gradient sums of a data-parallel trainer would need their own "
 	"all-reduce";
 
+// The deposit recomputes a ray's uv by the uniform draw and takes uv_pdf as 1
+static const char* const ERROR_SAMPLING_VS_DISTORTION =
+	"optimize_distortion cannot be combined with sample_focal_plane_proportional_to_error / "
+	"sample_image_proportional_to_error: turn one of them off first";
+static const char* const DISTORTION_VS_DATA_PARALLEL =
+	"optimize_distortion is single-GPU (the distortion map's gradient is not all-reduced): it cannot be combined with a "
+	"data-parallel exchange hook; turn one of them off first";
+
 int ngp_nerf_trainer_set_error_sampling(ngp_nerf_trainer* t, int focal_plane, int image) {
 	if (!t) return NGP_INVALID;
 	NERF_TRY({
 		NGP_CHECK(!(focal_plane || image) || !t->cam.optimize_extrinsics, ERROR_SAMPLING_VS_EXTRINSICS);
+		NGP_CHECK(!(focal_plane || image) || !t->dist.optimize, ERROR_SAMPLING_VS_DISTORTION);
 		NGP_CHECK(!image || !t->optimize_exposure, IMAGE_SAMPLING_VS_EXPOSURE);
 		t->drain();  // a prelaunched sampler drew its pixels under the old switches
 		t->sample_focal_plane_by_error = focal_plane != 0;
@@ -281,6 +293,118 @@ int ngp_nerf_trainer_set_envmap_training(ngp_nerf_trainer* t, int loss_type, con
 		t->env.opt_set = optimizer_json != nullptr;
 		if (optimizer_json) t->env.opt = c;
 	});
+}
+
+// ---- lens distortion map -----------------------------------------------------------------------------------------
+// the map is about to change outside a step: nothing may still trace through, or be launched to trace through, the old one
+int ngp_nerf_trainer_set_distortion_map(ngp_nerf_trainer* t, uint32_t width, uint32_t height, const float* params) {
+	if (!t || !distortion_dims_ok(width, height)) return NGP_INVALID;
+	NERF_TRY({
+		cameras_quiesce(t);
+		ngp_nerf_trainer::Distortion& d = t->dist;
+		d.w = width; d.h = height; d.step = 0; d.ema_valid = false;
+		const size_t n = d.n(), b = n * sizeof(float);
+		float* p = d.params.get<float>(n);
+		if (params) NGP_HIP(hipMemcpy(p, params, b, hipMemcpyHostToDevice));
+		else NGP_HIP(hipMemset(p, 0, b));  // TrainableBuffer::initialize_params
+		for (Buf* q : {&d.ema, &d.ema_out, &d.m1, &d.m2, &d.steps, &d.grad}) NGP_HIP(hipMemset(q->get<float>(n), 0, b));
+		const size_t words = distortion_acc_words64(width, height);
+		NGP_HIP(hipMemset(d.acc.get<unsigned long long>(words), 0, words * 8));
+		if (d.optimize && !t->cam.optimize_extrinsics && !t->optimize_exposure) t->n_steps_since_cam_update = 0;
+	});
+}
+
+int ngp_nerf_trainer_clear_distortion_map(ngp_nerf_trainer* t) {
+	if (!t) return NGP_INVALID;
+	NERF_TRY({
+		cameras_quiesce(t);
+		t->dist.w = t->dist.h = 0;
+		t->dist.step = 0;
+		t->dist.ema_valid = false;
+		t->dist.optimize = false;  // nothing left to optimise
+	});
+}
+
+static const void* distortion_array(const ngp_nerf_trainer* t, int which) {
+	const ngp_nerf_trainer::Distortion& d = t->dist;
+	switch (which) {
+		case NGP_DISTORTION_PARAMS: return d.params.p;
+		case NGP_DISTORTION_GRADIENT: return d.grad.p;
+		case NGP_DISTORTION_FIRST_MOMENTS: return d.m1.p;
+		case NGP_DISTORTION_SECOND_MOMENTS: return d.m2.p;
+		case NGP_DISTORTION_PARAM_STEPS: return d.steps.p;
+		case NGP_DISTORTION_INFERENCE_PARAMS: return t->distortion_inference();
+	}
+	return nullptr;
+}
+
+int ngp_nerf_trainer_distortion_map(const ngp_nerf_trainer* t, int which, float* out, uint64_t cap, uint32_t* width, uint32_t* height) {
+	if (!t || which < NGP_DISTORTION_PARAMS || which > NGP_DISTORTION_INFERENCE_PARAMS) return NGP_INVALID;
+	if (width) *width = t->dist.w;
+	if (height) *height = t->dist.h;
+	if (!out || !t->dist.bound()) return NGP_OK;
+	if (cap < t->dist.n()) return NGP_INVALID;
+	NERF_TRY({
+		NGP_HIP(hipDeviceSynchronize());
+		NGP_HIP(hipMemcpy(out, distortion_array(t, which), t->dist.n() * sizeof(float), hipMemcpyDeviceToHost));
+	});
+}
+
+int ngp_nerf_trainer_distortion_map_device(const ngp_nerf_trainer* t, int which, const float** data, uint32_t* width, uint32_t* height) {
+	if (!t || !data || (which != NGP_DISTORTION_PARAMS && which != NGP_DISTORTION_INFERENCE_PARAMS)) return NGP_INVALID;
+	*data = t->dist.bound() ? (const float*)distortion_array(t, which) : nullptr;
+	if (width) *width = t->dist.w;
+	if (height) *height = t->dist.h;
+	return NGP_OK;
+}
+
+int ngp_nerf_trainer_distortion_accumulator(const ngp_nerf_trainer* t, uint64_t* out, uint64_t cap, uint64_t* words) {
+	if (!t) return NGP_INVALID;
+	const uint64_t n = t->dist.bound() ? (uint64_t)distortion_acc_words64(t->dist.w, t->dist.h) : 0;
+	if (words) *words = n;
+	if (!out || n == 0) return NGP_OK;
+	if (cap < n) return NGP_INVALID;
+	NERF_TRY({
+		NGP_HIP(hipDeviceSynchronize());
+		NGP_HIP(hipMemcpy(out, t->dist.acc.p, n * 8, hipMemcpyDeviceToHost));
+	});
+}
+
+int ngp_nerf_trainer_set_distortion_training(ngp_nerf_trainer* t, const char* optimizer_json, uint32_t width, uint32_t height) {
+	if (!t || !distortion_dims_ok(width, height)) return NGP_INVALID;
+	NERF_TRY({
+		AdamConfig c;
+		if (optimizer_json) parse_optimizer_json(optimizer_json, c);
+		t->dist.opt_set = optimizer_json != nullptr;
+		if (optimizer_json) t->dist.opt = c;
+		t->dist.def_w = width; t->dist.def_h = height;
+	});
+}
+
+int ngp_nerf_trainer_set_optimize_distortion(ngp_nerf_trainer* t, int optimize) {
+	if (!t) return NGP_INVALID;
+	NERF_TRY({
+		const bool on = optimize != 0;
+		NGP_CHECK(!on || !t->dp(), DISTORTION_VS_DATA_PARALLEL);
+		NGP_CHECK(!on || !t->error_sampling(), ERROR_SAMPLING_VS_DISTORTION);
+		if (on == t->dist.optimize) return NGP_OK;
+		// the training pass is re-captured with (or without) the input gradient; a prelaunched sampler was released under
+		// the other rule (step_release_samples), and traced without the map this creates
+		cameras_quiesce(t);
+		if (on && !t->dist.bound()) check_rc(ngp_nerf_trainer_set_distortion_map(t, t->dist.def_w, t->dist.def_h, nullptr));
+		t->dist.optimize = on;
+		if (on) {
+			// a window of its own unless pose refinement's or the exposures' is running: the sums start from zero either way
+			if (!t->cam.optimize_extrinsics && !t->optimize_exposure) t->n_steps_since_cam_update = 0;
+			NGP_HIP(hipMemset(t->dist.acc.p, 0, distortion_acc_words64(t->dist.w, t->dist.h) * 8));
+		}
+	});
+}
+
+int ngp_nerf_trainer_get_optimize_distortion(const ngp_nerf_trainer* t, int* optimize) {
+	if (!t || !optimize) return NGP_INVALID;
+	*optimize = t->dist.optimize ? 1 : 0;
+	return NGP_OK;
 }
 
 int ngp_nerf_trainer_get_camera_training(const ngp_nerf_trainer* t, ngp_nerf_camera_training* out) {
@@ -439,6 +563,10 @@ int ngp_nerf_trainer_set_data_parallel(ngp_nerf_trainer* t, uint32_t rank, uint3
 	}
 	if (allreduce && t->env.train) {
 		nerf_set_error(TRAIN_ENVMAP_VS_DATA_PARALLEL);
+		return NGP_ERROR;
+	}
+	if (allreduce && t->dist.optimize) {
+		nerf_set_error(DISTORTION_VS_DATA_PARALLEL);
 		return NGP_ERROR;
 	}
 	t->drain();
@@ -650,7 +778,8 @@ static void launch_sampler(ngp_nerf_trainer* t, const SamplePlan& p, hipStream_t
 	a.n_rays = p.Rl; a.ray_offset = p.r_lo; a.n_rays_total_for_image_idx = p.R; a.cdfs = t->sampling_cdfs();
 	a.max_samples = p.max_inference; a.rng = t->rng.dev(); a.bitfield = (const uint8_t*)t->bitfield.p;
 	a.ray_indices = p.ray_indices; a.rays = p.rays; a.numsteps = p.numsteps; a.coords = p.coords; a.counters = p.ctr;
-	check_rc(run_sampler(t->data, &t->cfg, s, a, t->d_cams));
+	const DistMap dm = t->dist.view();  // a bound map is always traced through, whether it is being optimised or not
+	check_rc(run_sampler(t->data, &t->cfg, s, a, t->d_cams, dm.data ? &dm : nullptr));
 }
 static bool density_grid_update_due(uint32_t step) {
 	const uint32_t skip = std::min(std::max(step / 16u, 1u), 16u);
@@ -805,7 +934,8 @@ struct Step {
 	                            // stream-ordered (single GPU, or the engine's RCCL communicator)
 	bool cam = false;           // camera pose refinement: the training pass also writes dL/dinput
 	float* dinput = nullptr;    // [Bl x 7]
-	bool cam_updated = false;   // this step ended with a pose update (step_camera_update)
+	bool dist = false;          // optimize_distortion: likewise, for the map's gradient
+	bool cam_updated = false;   // this step ended with a pose or distortion map update (step_camera_update)
 	bool expo = false;          // optimize_exposure: the loss pass also takes the rays' exposure gradients
 	const float* expo_ray_grad = nullptr;  // ... kept here for step_exposure_gradients
 	bool expo_due = false;      // an exposure-only update is due at the end of this step (step_exposure_update)
@@ -849,7 +979,8 @@ static void step_plan(ngp_nerf_trainer* t, Step& c) {
 	c.expo = t->optimize_exposure && sp.Rl > 0;
 	t->last_rng = c.rng; t->last_n_rays = sp.R; t->last_max_samples = sp.max_inference;
 	t->last_ray_indices = sp.ray_indices; t->last_rays = sp.rays; t->last_counters = sp.ctr;
-	c.dinput = c.cam ? t->dinput.get<float>((size_t)sp.Bl * 7) : nullptr;
+	c.dist = t->dist.optimize && t->dist.bound() && !c.dp && sp.Rl > 0;
+	c.dinput = c.cam || c.dist ? t->dinput.get<float>((size_t)sp.Bl * 7) : nullptr;
 }
 
 // The step's samples (launched here, or awaited from the prelaunch) and the network's output for every one of them.
@@ -1014,12 +1145,14 @@ static void step_envmap_update(ngp_nerf_trainer* t, hipStream_t s, const Step& c
 
 // Camera pose refinement, device part (testbed_nerf.cu:3641-3644, 4071-4125): the compacted batch's input gradient summed per
 // image into the trainer's accumulators, which start from zero after every pose update.
+// optimize_distortion (:2088-2099): pass 1's DIST form also stores every kept ray's image-plane gradient, which
+// k_distortion_deposit adds into the map's exact accumulator; with the map alone pass 2 is not launched.
 static void step_camera_gradients(ngp_nerf_trainer* t, hipStream_t s, const Step& c) {
-	if (!c.cam) return;
+	if (!c.cam && !c.dist) return;
 	ProfScope ps("nerf_camera_gradients", s);
 	const uint32_t n_images = t->data->ds.n_images;
-	float* acc = t->cam_grad.get<float>((size_t)6 * n_images);
-	if (t->n_steps_since_cam_update == 0) NGP_HIP(hipMemsetAsync(acc, 0, (size_t)6 * n_images * sizeof(float), s));
+	float* acc = c.cam ? t->cam_grad.get<float>((size_t)6 * n_images) : nullptr;
+	if (c.cam && t->n_steps_since_cam_update == 0) NGP_HIP(hipMemsetAsync(acc, 0, (size_t)6 * n_images * sizeof(float), s));
 	const SamplePlan& sp = c.sp;
 	CamGradArgs a{};
 	a.n_rays_cap = sp.Rl; a.n_rays_total = sp.R; a.n_images = n_images;
@@ -1027,8 +1160,43 @@ static void step_camera_gradients(ngp_nerf_trainer* t, hipStream_t s, const Step
 	a.coords = c.coords_c; a.coords_grad = c.dinput; a.grad_stride = 7;
 	for (int k = 0; k < 3; ++k) { a.aabb_min[k] = t->cfg.aabb_min[k]; a.aabb_max[k] = t->cfg.aabb_max[k]; }
 	a.ray_grad = t->cam_ray_grad.get<float>((size_t)sp.Ra * 6);
-	a.pos_grad = acc; a.rot_grad = acc + (size_t)3 * n_images;
-	camera_gradients(a, CAM_GRAD_LANES, s);
+	a.pos_grad = acc; a.rot_grad = acc ? acc + (size_t)3 * n_images : nullptr;
+	if (!c.dist) {
+		camera_gradients(a, CAM_GRAD_LANES, s);
+		return;
+	}
+	ngp_nerf_trainer::Distortion& d = t->dist;
+	const size_t words = distortion_acc_words64(d.w, d.h);
+	if (t->n_steps_since_cam_update == 0) NGP_HIP(hipMemsetAsync(d.acc.p, 0, words * 8, s));
+	float* ray_g = d.ray_grad.get<float>((size_t)sp.Ra * 2);
+	// xform_img: the camera the sampler traced the image through (the refined one)
+	static_assert(sizeof(Camera) % sizeof(float) == 0 && offsetof(Camera, m) % sizeof(float) == 0, "Camera::m as a strided float array");
+	const CamDistArgs da{(const float*)((const char*)t->d_cams + offsetof(Camera, m)), (uint32_t)(sizeof(Camera) / sizeof(float)), ray_g};
+	camera_gradients_distortion(a, da, CAM_GRAD_LANES, c.cam, s);
+	DistDepositArgs dep{};
+	dep.n_rays_cap = sp.Rl; dep.n_rays_total = sp.R; dep.n_images = n_images;
+	dep.snap = t->cfg.snap_to_pixel_centers != 0; dep.rng = Rng{c.rng.state, c.rng.inc}; dep.cams = t->d_cams;
+	dep.ray_counter = sp.ctr; dep.ray_indices = sp.ray_indices; dep.numsteps = sp.numsteps; dep.ray_grad = ray_g;
+	dep.w = d.w; dep.h = d.h; dep.acc = (unsigned long long*)d.acc.p;
+	distortion_deposit_rays(dep, s);
+}
+
+// optimize_distortion's update (testbed_nerf.cu:3811-3818): safe_divide of the summed gradient by the summed weight, then
+// the map's optimizer step with LOSS_SCALE * n_steps_between_cam_updates, on the step's stream: no host round trip. The
+// next sampler runs behind it on the same stream (Step::cam_updated).
+static void distortion_update(ngp_nerf_trainer* t, hipStream_t s, uint32_t between) {
+	ngp_nerf_trainer::Distortion& d = t->dist;
+	ProfScope ps("nerf_distortion_update", s);
+	distortion_gradient_f32(d.w, d.h, (const unsigned long long*)d.acc.p, (float*)d.grad.p, s);
+	AdamState st{};
+	st.w32 = (float*)d.params.p; st.g32 = (const float*)d.grad.p;
+	st.m1 = (float*)d.m1.p; st.m2 = (float*)d.m2.p; st.steps = (uint32_t*)d.steps.p;
+	st.ema32 = (float*)d.ema.p; st.ema_f32 = (float*)d.ema_out.p;
+	st.step_add = d.step;
+	const AdamConfig& oc = t->distortion_optimizer();
+	adam_ema_update_f32(oc, (uint32_t)d.n(), 128.0f * (float)between, st, s);
+	++d.step;
+	d.ema_valid = oc.ema_decay > 0.f;
 }
 
 // Camera pose refinement, host part (testbed_nerf.cu:3754-3809): every n_steps_between_cam_updates steps the sums come
@@ -1044,11 +1212,15 @@ static void exposure_update_host(ngp_nerf_trainer* t, hipStream_t s, const std::
 }
 static void step_camera_update(ngp_nerf_trainer* t, hipStream_t s, Step& c) {
 	const bool expo = t->optimize_exposure;  // also on a step without rays, as the counter is
-	if (!c.cam && !expo) return;
+	if (!c.cam && !expo && !c.dist) return;
 	const uint32_t between = std::max(t->cam.n_steps_between_cam_updates, 1u);
 	if (++t->n_steps_since_cam_update < between) return;
 	t->n_steps_since_cam_update = 0;
-	if (!c.cam) { c.expo_due = true; return; }
+	if (c.dist) {
+		distortion_update(t, s, between);
+		c.cam_updated = true;
+	}
+	if (!c.cam) { c.expo_due = expo; return; }
 	const uint32_t n_images = t->data->ds.n_images;
 	std::vector<float> g((size_t)6 * n_images), ge(expo ? (size_t)3 * n_images : 0);
 	NGP_HIP(hipMemcpyAsync(g.data(), t->cam_grad.p, g.size() * sizeof(float), hipMemcpyDeviceToHost, s));

@@ -420,6 +420,17 @@ PYBIND11_MODULE(pyngp, m) {
 			     return std::move(out);
 		     }, py::arg("ema") = false,
 		     "Engine extension: the environment map [H, W, 4] (the raw parameters, or the EMA parameters rendering reads); None without one.")
+		// the lens distortion map (python_api.cu:618-653; testbed.cu:4066-4076)
+		.def_property("optimize_distortion", [](NerfTrainingView& v) { return v.t->optimize_distortion(); },
+		              [](NerfTrainingView& v, bool x) { v.t->set_optimize_distortion(x); })
+		.def_property_readonly("distortion_map", [](NerfTrainingView& v) -> py::object {
+			     uint32_t w = 0, h = 0;
+			     const std::vector<float> a = v.t->distortion_map(&w, &h);
+			     if (a.empty()) return py::none();
+			     py::array_t<float> out({(py::ssize_t)h, (py::ssize_t)w, (py::ssize_t)2});
+			     std::memcpy(out.mutable_data(), a.data(), a.size() * sizeof(float));
+			     return std::move(out);
+		     }, "Engine extension: the lens distortion map [H, W, 2], the offsets added to the rays' dir.xy; None without one.")
 		// depth supervision (python_api.cu:616, 635, 657)
 		.def_property("depth_supervision_lambda", [](NerfTrainingView& v) { return v.t->depth_supervision_lambda(); },
 		              [](NerfTrainingView& v, float x) { v.t->set_depth_supervision(x, v.t->depth_loss_type()); })

@@ -128,7 +128,10 @@ inline std::string default_network_config(ETestbedMode mode) {
  "network": {"otype": "FullyFusedMLP", "activation": "ReLU", "output_activation": "None", "n_neurons": 64, "n_hidden_layers": 1},
  "dir_encoding": {"otype": "Composite", "nested": [{"n_dims_to_encode": 3, "otype": "SphericalHarmonics", "degree": 4},
    {"otype": "Identity"}]},
- "rgb_network": {"otype": "FullyFusedMLP", "activation": "ReLU", "output_activation": "None", "n_neurons": 64, "n_hidden_layers": 2}})";
+ "rgb_network": {"otype": "FullyFusedMLP", "activation": "ReLU", "output_activation": "None", "n_neurons": 64, "n_hidden_layers": 2},
+ "distortion_map": {"resolution": [32, 32], "optimizer": {"otype": "ExponentialDecay", "decay_start": 10000,
+   "decay_interval": 5000, "decay_end": 25000, "decay_base": 0.33, "nested": {"otype": "Adam", "learning_rate": 1e-4, "beta1": 0.9,
+   "beta2": 0.99, "epsilon": 1e-8}}}})";
 	case ETestbedMode::Sdf:  // configs/sdf/base.json
 		return R"({"loss": {"otype": "MAPE"},
  "optimizer": {"otype": "Ema", "decay": 0.95, "nested": {"otype": "ExponentialDecay", "decay_start": 10000,
@@ -397,6 +400,7 @@ public:
 			push_envmap();
 			push_depth_supervision();
 			push_exposure_training();
+			push_distortion_training();
 		}
 	}
 	uint64_t n_params() const { return m_model ? ngp_model_n_params(m_model) : 0; }
@@ -546,8 +550,8 @@ public:
 		if (!m_model) throw std::runtime_error("render: no network (train or load a snapshot first)");
 		std::vector<float> out((size_t)width * height * 4);
 		if (m_testbed_mode == ETestbedMode::Nerf) {
-			if ((int)m_render_mode > (int)ERenderMode::Depth)
-				throw std::runtime_error("render: ERenderMode AO, Shade, Normals, Positions and Depth are implemented");
+			if ((int)m_render_mode > (int)ERenderMode::Distortion)
+				throw std::runtime_error("render: ERenderMode AO, Shade, Normals, Positions, Depth and Distortion are implemented");
 			require_nerf_trainer("render");
 			if (!m_renderer) check(ngp_nerf_renderer_create(&m_renderer), "ngp_nerf_renderer_create");
 			check(ngp_nerf_renderer_set_mode(m_renderer, (int)m_render_mode), "ngp_nerf_renderer_set_mode");
@@ -563,6 +567,15 @@ public:
 				uint32_t ew = 0, eh = 0;
 				check(ngp_nerf_trainer_envmap_device(m_nerf_trainer, NGP_ENVMAP_INFERENCE_PARAMS, &env, &ew, &eh), "ngp_nerf_trainer_envmap_device");
 				check(ngp_nerf_renderer_set_envmap(m_renderer, env, ew, eh), "ngp_nerf_renderer_set_envmap");
+			}
+			{  // the trainer's lens distortion map under render_with_lens_distortion (testbed_nerf.cu:2229-2344), which
+			   // ERenderMode::Distortion shows; none, or the switch off: unbound
+				const float* dm = nullptr;
+				uint32_t dw = 0, dh = 0;
+				if (m_render_with_lens_distortion)
+					check(ngp_nerf_trainer_distortion_map_device(m_nerf_trainer, NGP_DISTORTION_INFERENCE_PARAMS, &dm, &dw, &dh),
+					      "ngp_nerf_trainer_distortion_map_device");
+				check(ngp_nerf_renderer_set_distortion_map(m_renderer, dm, dw, dh), "ngp_nerf_renderer_set_distortion_map");
 			}
 			float* dev = m_render_buf.get<float>(out.size());
 			ngp_nerf_config cfg = m_nerf_cfg;
@@ -760,6 +773,7 @@ public:
 		try {
 			check_error_sampling_vs_extrinsics();
 			check_image_sampling_vs_exposure();
+			check_error_sampling_vs_distortion();
 			push_error_sampling();
 		} catch (...) {
 			m_sample_focal_plane_by_error = was_f;
@@ -812,6 +826,53 @@ public:
 		if (m_nerf_trainer)
 			check(ngp_nerf_trainer_set_exposure_training(m_nerf_trainer, m_optimize_exposure ? 1 : 0, m_exposure_l2_reg),
 			      "ngp_nerf_trainer_set_exposure_training");
+	}
+	// ---- lens distortion map (nerf.training.optimize_distortion, python_api.cu:618-653; m_distortion, testbed.cu:4066-4076):
+	// the switch is kept here until there is a trainer and pushed to a live one with the config's "distortion_map"
+	// section (its optimizer, falling back to the main one, and its resolution); the map itself belongs to the trainer,
+	// which creates it, zero, when the switch first goes on (reset_network starts over)
+	bool optimize_distortion() const { return m_optimize_distortion; }
+	void set_optimize_distortion(bool on) {
+		const bool was = m_optimize_distortion;
+		m_optimize_distortion = on;
+		try {
+			check_error_sampling_vs_distortion();
+			push_distortion_training();
+		} catch (...) {
+			m_optimize_distortion = was;
+			throw;
+		}
+	}
+	void push_distortion_training() {
+		if (!m_nerf_trainer) return;
+		uint32_t w = 32, h = 32;
+		std::string opt;
+		if (m_network_config.contains("distortion_map")) {
+			const Json& d = m_network_config["distortion_map"];
+			if (d.contains("resolution")) {
+				const Json& r = d["resolution"];
+				if (r.type == Json::Array && r.arr.size() == 2) { w = (uint32_t)r.arr[0].num; h = (uint32_t)r.arr[1].num; }
+				else if (r.type == Json::Number) w = h = (uint32_t)r.num;
+				else throw std::runtime_error("distortion_map: resolution is [width, height]");
+			}
+			if (d.contains("optimizer")) opt = d["optimizer"].dump();
+		}
+		// no section, or none with an optimizer: the main optimizer (testbed.cu:4068)
+		if (opt.empty() && m_network_config.contains("optimizer")) opt = m_network_config["optimizer"].dump();
+		check(ngp_nerf_trainer_set_distortion_training(m_nerf_trainer, opt.empty() ? nullptr : opt.c_str(), w, h),
+		      "ngp_nerf_trainer_set_distortion_training");
+		check(ngp_nerf_trainer_set_optimize_distortion(m_nerf_trainer, m_optimize_distortion ? 1 : 0), "ngp_nerf_trainer_set_optimize_distortion");
+	}
+	// the trainer's map on the host: [height x width x 2] offsets of dir.xy; empty without a map
+	std::vector<float> distortion_map(uint32_t* width, uint32_t* height) {
+		*width = *height = 0;
+		if (!m_nerf_trainer) return {};
+		check(ngp_nerf_trainer_distortion_map(m_nerf_trainer, NGP_DISTORTION_PARAMS, nullptr, 0, width, height), "ngp_nerf_trainer_distortion_map");
+		std::vector<float> out((size_t)*width * *height * 2);
+		if (!out.empty())
+			check(ngp_nerf_trainer_distortion_map(m_nerf_trainer, NGP_DISTORTION_PARAMS, out.data(), out.size(), width, height),
+			      "ngp_nerf_trainer_distortion_map");
+		return out;
 	}
 	// cam_exposure[i].variable(): zeros before there is a trainer, and for a frame out of range
 	void get_camera_exposure(int frame_idx, float out[3]) const {
@@ -921,6 +982,11 @@ public:
 	void check_error_sampling_vs_extrinsics() const {
 		if (m_cam_training.optimize_extrinsics && (m_sample_focal_plane_by_error || m_sample_image_by_error))
 			throw std::runtime_error("optimize_extrinsics cannot be combined with sample_focal_plane_proportional_to_error / "
+			                         "sample_image_proportional_to_error: turn one of them off first");
+	}
+	void check_error_sampling_vs_distortion() const {
+		if (m_optimize_distortion && (m_sample_focal_plane_by_error || m_sample_image_by_error))
+			throw std::runtime_error("optimize_distortion cannot be combined with sample_focal_plane_proportional_to_error / "
 			                         "sample_image_proportional_to_error: turn one of them off first");
 	}
 	void check_image_sampling_vs_exposure() const {
@@ -1101,6 +1167,7 @@ private:
 	bool m_sample_focal_plane_by_error = false, m_sample_image_by_error = false;  // testbed.h:733-734
 	bool m_train_envmap = false;            // Training::train_envmap
 	bool m_optimize_exposure = false;       // Training::optimize_exposure
+	bool m_optimize_distortion = false;     // Training::optimize_distortion
 	float m_exposure_l2_reg = 0.f;          // Training::exposure_l2_reg
 	float m_depth_lambda = 0.f;             // Training::depth_supervision_lambda (testbed.h:719)
 	uint32_t m_depth_loss_type = 1;         // Training::depth_loss_type: L1 (testbed.h:745)

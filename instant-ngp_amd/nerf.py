@@ -224,9 +224,11 @@ def _error_cdfs(cdfs, device, n_images):
 
 
 def generate_training_samples(ds, cfg, n_rays, rng, max_samples, bitfield, ray_offset=0, n_rays_total=None,
-                              stream=None, cdfs=None):
+                              stream=None, cdfs=None, distortion=None):
     """generate_training_samples_nerf (testbed_nerf.cu:1382-1658). cdfs: draw the rays' pixels from the error map's
-    CDFs (a dict, see _error_cdfs; ngp_nerf_generate_training_samples_cdf)."""
+    CDFs (a dict, see _error_cdfs; ngp_nerf_generate_training_samples_cdf). distortion: a lens distortion map, a
+    contiguous float32 device tensor [h, w, 2], whose offset at the ray's uv is added to dir.xy after the lens
+    (ngp_nerf_generate_training_samples_distortion)."""
     dev = bitfield.device
     out = {
         "ray_indices": torch.zeros(n_rays, dtype=torch.int32, device=dev),
@@ -238,7 +240,13 @@ def generate_training_samples(ds, cfg, n_rays, rng, max_samples, bitfield, ray_o
     args = (ds.handle, C.byref(cfg), _stream(stream), n_rays, ray_offset, n_rays_total or n_rays, rng, max_samples,
             _ptr(bitfield), _ptr(out["ray_indices"]), _ptr(out["rays"]), _ptr(out["numsteps"]), _ptr(out["coords"]),
             _ptr(out["counters"]))
-    if cdfs is None:
+    if distortion is not None:
+        _check_distortion_map(distortion, dev, "generate_training_samples")
+        e, keep = _error_cdfs(cdfs, dev, len(ds))
+        check(lib().ngp_nerf_generate_training_samples_distortion(*args, C.byref(e) if e is not None else None,
+                                                                  _ptr(distortion), distortion.shape[1], distortion.shape[0]))
+        torch.cuda.synchronize(dev)  # the kernels read `keep`
+    elif cdfs is None:
         check(lib().ngp_nerf_generate_training_samples(*args))
     else:
         e, keep = _error_cdfs(cdfs, dev, len(ds))
@@ -467,6 +475,118 @@ def grid_mean_and_bitfield(grid, max_cascade, stream=None):
     bf = torch.zeros(BITFIELD_BYTES, dtype=torch.uint8, device=grid.device)
     check(lib().ngp_nerf_grid_mean_and_bitfield(_stream(stream), _ptr(grid), max_cascade, _ptr(mean), _ptr(bf)))
     return mean, bf
+
+
+# ---- lens distortion map ------------------------------------------------------------------------
+def _check_distortion_map(m, device, who):
+    if not torch.is_tensor(m) or m.dtype != torch.float32 or m.dim() != 3 or m.shape[2] != 2 or not m.is_contiguous() \
+            or (device is not None and m.device != device):
+        raise ValueError(f"{who}: the distortion map is a contiguous float32 device tensor [h, w, 2]")
+
+
+def distortion_lookup(width, height, uv, map=None, host=False, stream=None):
+    """The four texels and bilinear weights of positions uv [n, 2] in a width x height lens distortion map, as
+    Buffer2DView::at_lerp (common.h:384-400) and deposit_image_gradient (common_device.cuh:124-156) both derive them:
+    (texels [n, 4] int64 indices x + y * width in the order (x, y), (x+1, y), (x, y+1), (x+1, y+1), each clamped into the
+    map, weights [n, 4] float32); with map ([height, width, 2] float32) also the mixed offsets [n, 2]. uv is folded into
+    [0, 2] with NaN to 0 first. Device tensors (ngp_nerf_distortion_lookup) or, host=True, numpy arrays
+    (ngp_nerf_distortion_lookup_host: the same function compiled for the host, no GPU call); the two agree bit for bit."""
+    if host:
+        u = np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 2)
+        tex, wt = np.zeros((u.shape[0], 4), np.uint32), np.zeros((u.shape[0], 4), np.float32)
+        m = off = None
+        if map is not None:
+            m = np.ascontiguousarray(map, dtype=np.float32)
+            if m.shape != (int(height), int(width), 2):
+                raise ValueError("distortion_lookup: map is [height, width, 2]")
+            off = np.zeros((u.shape[0], 2), np.float32)
+        check(lib().ngp_nerf_distortion_lookup_host(int(width), int(height), u.shape[0], u.ctypes.data, tex.ctypes.data,
+                                                    wt.ctypes.data, m.ctypes.data if m is not None else None,
+                                                    off.ctypes.data if off is not None else None))
+        return (tex.astype(np.int64), wt) if map is None else (tex.astype(np.int64), wt, off)
+    u = uv.to(torch.float32).contiguous().view(-1, 2)
+    tex = torch.zeros((u.shape[0], 4), dtype=torch.int32, device=u.device)
+    wt = torch.zeros((u.shape[0], 4), dtype=torch.float32, device=u.device)
+    off = None
+    if map is not None:
+        _check_distortion_map(map, u.device, "distortion_lookup")
+        if tuple(map.shape) != (int(height), int(width), 2):
+            raise ValueError("distortion_lookup: map is [height, width, 2]")
+        off = torch.zeros((u.shape[0], 2), dtype=torch.float32, device=u.device)
+    check(lib().ngp_nerf_distortion_lookup(_stream(stream), int(width), int(height), u.shape[0], _ptr(u), _ptr(tex), _ptr(wt),
+                                           _ptr(map) if map is not None else None, _ptr(off) if off is not None else None))
+    return (tex.to(torch.int64), wt) if map is None else (tex.to(torch.int64), wt, off)
+
+
+def distortion_ray_gradients(cfg, n_rays_total, n_images, samples, coords_compacted, coords_gradient, camera_matrices,
+                             pos_gradient=None, rot_gradient=None, stream=None):
+    """compute_cam_gradient_train_nerf's distortion branch per ray (testbed_nerf.cu:2088-2099;
+    ngp_nerf_distortion_ray_gradients): camera_gradients' arguments plus camera_matrices, float32 [n_images, 3, 3] with
+    [i, c, r] the column-major element (column c, row r) of image i's rotation. Returns float32 [n_rays_total, 2]: row r
+    of a kept ray r holds (inverse(mat3(xform_img)) * (gd - d dot(gd, d))).xy, zeros for a ray without samples.
+    pos_gradient / rot_gradient (both or neither): the per-image pose sums are added onto them as camera_gradients does."""
+    for t in (coords_compacted, coords_gradient, camera_matrices) + ((pos_gradient, rot_gradient) if pos_gradient is not None else ()):
+        if t is None or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("distortion_ray_gradients: contiguous float32 tensors")
+    if (pos_gradient is None) != (rot_gradient is None):
+        raise ValueError("distortion_ray_gradients: pos_gradient and rot_gradient, both or neither")
+    if camera_matrices.numel() != 9 * n_images:
+        raise ValueError("distortion_ray_gradients: camera_matrices are [n_images, 3, 3]")
+    if coords_gradient.shape[0] < coords_compacted.shape[0] or coords_compacted.shape[1] != 7:
+        raise ValueError("distortion_ray_gradients: one gradient row per compacted coordinate")
+    out = torch.zeros((int(n_rays_total), 2), dtype=torch.float32, device=coords_compacted.device)
+    check(lib().ngp_nerf_distortion_ray_gradients(
+        C.byref(cfg), _stream(stream), int(n_rays_total), int(n_images), _ptr(samples["counters"]),
+        _ptr(samples["ray_indices"]), _ptr(samples["rays"]), _ptr(samples["numsteps"]), _ptr(coords_compacted),
+        _ptr(coords_gradient), coords_gradient.shape[1], _ptr(pos_gradient) if pos_gradient is not None else None,
+        _ptr(rot_gradient) if rot_gradient is not None else None, _ptr(camera_matrices), _ptr(out)))
+    return out
+
+
+DISTORTION_BINS = 16  # 64-bit bins per channel of the distortion map's gradient accumulator; bin b's unit is 2^(16 b - 149)
+
+
+def distortion_accumulator(width, height, device="cuda"):
+    """A zeroed gradient accumulator for a width x height map (ngp_nerf_distortion_accumulator_words int64 words):
+    [height * width * 3 * 16] bins, channels sum g.x w, sum g.y w and sum w per texel, then the count of rays dropped
+    for a non-finite gradient."""
+    n = int(lib().ngp_nerf_distortion_accumulator_words(int(width), int(height)))
+    if n == 0:
+        raise ValueError("distortion_accumulator: width and height in 1..8192")
+    return torch.zeros(n, dtype=torch.int64, device=device)
+
+
+def distortion_deposit(ds, cfg, n_rays_total, rng, ray_counter, ray_indices, ray_gradients, width, height, accumulator,
+                       numsteps=None, stream=None):
+    """deposit_image_gradient (common_device.cuh:124-156) of every kept ray's image-plane gradient (ray_gradients,
+    float32 [R, 2]) into `accumulator` (distortion_accumulator(); added to its content) at the ray's uv, recomputed from
+    its id (ray_indices int32 [R], *ray_counter of them) and rng as the sampler and the loss pass draw it. numsteps
+    (int32 [R, 2], optional): rays whose count is 0 deposit nothing. Exact integer sums: independent of arrival order."""
+    if accumulator.dtype != torch.int64 or not accumulator.is_contiguous() or \
+            accumulator.numel() != int(lib().ngp_nerf_distortion_accumulator_words(int(width), int(height))):
+        raise ValueError("distortion_deposit: accumulator from distortion_accumulator(width, height)")
+    g = ray_gradients.to(torch.float32).contiguous()
+    if g.dim() != 2 or g.shape[1] != 2 or g.shape[0] < ray_indices.numel():
+        raise ValueError("distortion_deposit: ray_gradients are [R, 2], one row per ray index")
+    if ray_indices.numel() < min(int(n_rays_total), int(ray_counter.reshape(-1)[0])):
+        raise ValueError("distortion_deposit: fewer ray indices than the ray counter says")
+    if numsteps is not None and numsteps.numel() < 2 * ray_indices.numel():
+        raise ValueError("distortion_deposit: numsteps are [R, 2]")
+    check(lib().ngp_nerf_distortion_deposit(ds.handle, C.byref(cfg), _stream(stream), int(n_rays_total), rng, _ptr(ray_counter),
+                                            _ptr(ray_indices), _ptr(numsteps) if numsteps is not None else None, _ptr(g),
+                                            int(width), int(height), _ptr(accumulator)))
+    torch.cuda.synchronize(accumulator.device)  # the kernel reads `g`
+
+
+def distortion_gradient(width, height, accumulator, stream=None):
+    """safe_divide of the accumulated gradient by the accumulated weight (testbed_nerf.cu:3811-3816;
+    ngp_nerf_distortion_gradient): float32 [height, width, 2], 0 where no weight arrived."""
+    if accumulator.dtype != torch.int64 or not accumulator.is_contiguous() or \
+            accumulator.numel() != int(lib().ngp_nerf_distortion_accumulator_words(int(width), int(height))):
+        raise ValueError("distortion_gradient: accumulator from distortion_accumulator(width, height)")
+    g = torch.empty((int(height), int(width), 2), dtype=torch.float32, device=accumulator.device)
+    check(lib().ngp_nerf_distortion_gradient(_stream(stream), int(width), int(height), _ptr(accumulator), _ptr(g)))
+    return g
 
 
 # ---- camera pose refinement ---------------------------------------------------------------------
@@ -860,6 +980,81 @@ class NerfTraining:
     def train_envmap(self, on):
         check(lib().ngp_nerf_trainer_set_train_envmap(self.handle, int(bool(on))))
 
+    # ---- lens distortion map (nerf.training.optimize_distortion, python_api.cu:618-653; testbed.cu:4066-4076) ----
+    DISTORTION_ARRAYS = {"params": 0, "gradient": 1, "first_moments": 2, "second_moments": 3, "param_steps": 4, "inference": 5}
+
+    def set_distortion_map(self, params=None, resolution=None, optimizer=None, default_resolution=(32, 32)):
+        """Give the trainer a lens distortion map: params, float32 [h, w, 2] offsets of dir.xy, or zeros of resolution =
+        (width, height). params=None and resolution=None: remove the map (and turn optimize_distortion off). A bound
+        map is added to every training ray, whether optimize_distortion is on or off. optimizer: the network config's
+        "distortion_map" optimizer section (not given: the main optimizer); default_resolution: the section's
+        resolution, the size of the map optimize_distortion creates when none is bound."""
+        if optimizer is not None or tuple(default_resolution) != (32, 32):
+            check(lib().ngp_nerf_trainer_set_distortion_training(
+                self.handle, json.dumps(optimizer).encode() if optimizer is not None else None, int(default_resolution[0]),
+                int(default_resolution[1])))
+        if params is None and resolution is None:
+            if optimizer is None:
+                check(lib().ngp_nerf_trainer_clear_distortion_map(self.handle))
+            return
+        if params is not None:
+            a = np.ascontiguousarray(params.detach().cpu().numpy() if torch.is_tensor(params) else params, dtype=np.float32)
+            if a.ndim != 3 or a.shape[2] != 2 or (resolution is not None and tuple(resolution) != (a.shape[1], a.shape[0])):
+                raise ValueError("set_distortion_map: params are [h, w, 2] (and resolution, if given, their (width, height))")
+            check(lib().ngp_nerf_trainer_set_distortion_map(self.handle, a.shape[1], a.shape[0], a.ctypes.data))
+        else:
+            check(lib().ngp_nerf_trainer_set_distortion_map(self.handle, int(resolution[0]), int(resolution[1]), None))
+
+    def set_distortion_training(self, network_config):
+        """The "distortion_map" section of a network config dict (testbed.cu:4068-4076): its optimizer, falling back to
+        the config's main "optimizer", and its resolution (default 32 x 32)."""
+        from .config import distortion_map_config
+        sec = distortion_map_config(network_config)
+        check(lib().ngp_nerf_trainer_set_distortion_training(self.handle, json.dumps(sec["optimizer"]).encode(),
+                                                             int(sec["resolution"][0]), int(sec["resolution"][1])))
+
+    def distortion_map(self, which="params"):
+        """The map as a numpy array [h, w, 2] (None without one): "params", "gradient" (the last update's, sum g w / sum w,
+        scaled by 128 * n_steps_between_cam_updates), "first_moments", "second_moments", "param_steps" (int32) or
+        "inference" (the parameters; the debiased EMA under an optimizer with an Ema wrapper)."""
+        w, h = C.c_uint32(), C.c_uint32()
+        k = self.DISTORTION_ARRAYS[which]
+        check(lib().ngp_nerf_trainer_distortion_map(self.handle, k, None, 0, C.byref(w), C.byref(h)))
+        if w.value == 0:
+            return None
+        a = np.zeros((h.value, w.value, 2), np.float32)
+        check(lib().ngp_nerf_trainer_distortion_map(self.handle, k, a.ctypes.data, a.size, C.byref(w), C.byref(h)))
+        return a.view(np.int32) if which == "param_steps" else a
+
+    def distortion_map_device(self, inference=True):
+        """(device pointer, width, height) of the parameters for NerfRenderer.set_distortion_map; (None, 0, 0) without a map."""
+        p, w, h = C.c_void_p(), C.c_uint32(), C.c_uint32()
+        check(lib().ngp_nerf_trainer_distortion_map_device(self.handle, 5 if inference else 0, C.byref(p), C.byref(w), C.byref(h)))
+        return p.value, w.value, h.value
+
+    def distortion_accumulator(self):
+        """The trainer's gradient accumulator as it is: numpy int64 (layout: distortion_accumulator()); None without a map."""
+        n = C.c_uint64()
+        check(lib().ngp_nerf_trainer_distortion_accumulator(self.handle, None, 0, C.byref(n)))
+        if n.value == 0:
+            return None
+        a = np.zeros(n.value, np.int64)
+        check(lib().ngp_nerf_trainer_distortion_accumulator(self.handle, a.ctypes.data, a.size, C.byref(n)))
+        return a
+
+    @property
+    def optimize_distortion(self):
+        """Training::optimize_distortion: train the lens distortion map with the scene (default off). Turning it on
+        without a map creates a zero map of the configured resolution. Single GPU; cannot be combined with error-driven
+        sampling."""
+        v = C.c_int()
+        check(lib().ngp_nerf_trainer_get_optimize_distortion(self.handle, C.byref(v)))
+        return bool(v.value)
+
+    @optimize_distortion.setter
+    def optimize_distortion(self, on):
+        check(lib().ngp_nerf_trainer_set_optimize_distortion(self.handle, int(bool(on))))
+
     def last_samples(self):
         """The last step's sampler call (ngp_nerf_trainer_last_samples): {"rng", "n_rays", "max_samples"} and views of
         the "ray_indices", "rays" and "counters" it wrote (valid until a later sampler runs: turn pipelining off)."""
@@ -913,7 +1108,8 @@ class NerfRenderer:
         check(lib().ngp_nerf_renderer_create(C.byref(h)))
         self.handle = h
 
-    RENDER_MODES = {"AO": 0, "Shade": 1, "Normals": 2, "Positions": 3, "Depth": 4, "EncodingVis": 9}  # ERenderMode (common.h:110-121)
+    RENDER_MODES = {"AO": 0, "Shade": 1, "Normals": 2, "Positions": 3, "Depth": 4, "Distortion": 5,
+                    "EncodingVis": 9}  # ERenderMode (common.h:110-121)
 
     def render(self, network, cfg, camera, bitfield=None, spp=1, sample_index=0, min_transmittance=0.01,
                background=(0.0, 0.0, 0.0, 0.0), use_inference_params=True, stream=None, render_mode="Shade",
@@ -947,6 +1143,24 @@ class NerfRenderer:
                 raise ValueError("set_envmap: a contiguous float32 device tensor [h, w, 4]")
             self._envmap = envmap
             check(lib().ngp_nerf_renderer_set_envmap(self.handle, _ptr(envmap), envmap.shape[1], envmap.shape[0]))
+
+    def set_distortion_map(self, distortion=None):
+        """Render through a lens distortion map (render_with_lens_distortion; testbed_nerf.cu:2229-2344), which render
+        mode "Distortion" also shows: a contiguous float32 device tensor [h, w, 2] (kept alive by the renderer), a
+        NerfTraining (its map; bind again after the trainer's map is set or cleared), or None to unbind."""
+        if distortion is None:
+            self._distortion = None
+            check(lib().ngp_nerf_renderer_set_distortion_map(self.handle, None, 0, 0))
+        elif isinstance(distortion, NerfTraining):
+            p, w, h = distortion.distortion_map_device(inference=True)
+            self._distortion = distortion
+            check(lib().ngp_nerf_renderer_set_distortion_map(self.handle, p, w, h))
+        else:
+            _check_distortion_map(distortion, None, "set_distortion_map")
+            if not distortion.is_cuda:
+                raise ValueError("set_distortion_map: a device tensor")
+            self._distortion = distortion
+            check(lib().ngp_nerf_renderer_set_distortion_map(self.handle, _ptr(distortion), distortion.shape[1], distortion.shape[0]))
 
     def __del__(self):
         h = getattr(self, "handle", None)

@@ -56,16 +56,25 @@ _BOXES = [  # min, max, colour
 ]
 
 
-def render(c2w, width, height, camera_angle_x=LEGO_CAMERA_ANGLE_X, device="cpu", return_depth=False, exposure=None):
+def render(c2w, width, height, camera_angle_x=LEGO_CAMERA_ANGLE_X, device="cpu", return_depth=False, exposure=None,
+           dir_offset=None):
     """RGBA8 [H, W, 4] of the procedural scene from Blender pose c2w. return_depth: also the scene's z-depth per pixel,
     float32 [H, W] in Blender units (distance along the camera's forward axis, what a depth image stores; 0 where the
     ray misses): NerfDataset.set_depth(i, depth, scale=0.33) puts it into the engine's units. exposure: the image's log2
     exposure (a number, or one per channel): the pixels' linear colours are multiplied by 2^exposure and clipped to 1
-    before they are stored as sRGB bytes, as a camera's auto-exposure would; None: the image as it is."""
+    before they are stored as sRGB bytes, as a camera's auto-exposure would; None: the image as it is. dir_offset: an
+    [H, W, 2] array added to each pixel's camera-space direction xy before the rotation, in the engine's camera
+    convention (x right, y down, z = 1 forward: what a lens distortion map holds), a lens the declared pinhole does not
+    explain; None: the pinhole as it is."""
     f = 0.5 * width / math.tan(0.5 * camera_angle_x)
     j, i = torch.meshgrid(torch.arange(height, device=device, dtype=torch.float32),
                           torch.arange(width, device=device, dtype=torch.float32), indexing="ij")
     d = torch.stack([(i + 0.5 - 0.5 * width) / f, -(j + 0.5 - 0.5 * height) / f, -torch.ones_like(i)], -1)
+    if dir_offset is not None:
+        off = torch.as_tensor(np.asarray(dir_offset, np.float32), device=device)
+        if tuple(off.shape) != (height, width, 2):
+            raise ValueError("render: dir_offset is [H, W, 2]")
+        d = d + torch.stack([off[..., 0], -off[..., 1], torch.zeros_like(i)], -1)  # this camera looks down -z with y up
     R = torch.tensor(c2w[:3, :3], dtype=torch.float32, device=device)
     o = torch.tensor(c2w[:3, 3], dtype=torch.float32, device=device)
     d = d @ R.T
