@@ -1299,9 +1299,10 @@ int ngp_trainer_create(ngp_model* m, const char* optimizer_json, uint64_t seed, 
 		const size_t b32 = al(n * 4), b16 = al((n + ngp_trainer::SHARD_PAD) * 2);
 		// lazy-EMA records from 2^20 parameters (C5: 105 M parameters, ~28 % updated per step; C2' 13 M: captured
 		// step 351 -> 330 us with the fused update, profiles/r03bw; C2, 3.3 M parameters, ~96 % updated: pass
-		// 140.6-142.8 -> 136.0 us since the MLP's update runs in the backward, NeRF steps unchanged with the
-		// EMA's closed-form catch-up, gpurun_out/r04cg); the eager arrays for small models. NGP_LAZY_EMA=0/1
-		// forces the choice.
+		// 147.5 us with both updates in the backward, against 163.0 us on the eager arrays and 183.3 us with the
+		// lazy layout's separate launch, one box and session, profiles/r09a_bench_c2_ab.json; round 4's 140.6-142.8
+		// -> 136.0 us was measured while the bench's gradients were zero); the eager arrays for small
+		// models. NGP_LAZY_EMA=0/1 forces the choice.
 		bool lazy = n >= (1ull << 20);
 		if (t->knobs.lazy_ema != KNOB_UNSET) lazy = t->knobs.lazy_ema != 0;
 		lazy = lazy && n % 4 == 0;

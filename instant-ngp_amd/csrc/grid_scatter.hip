@@ -1134,11 +1134,12 @@ __global__ void __launch_bounds__(SC_BT) k_sc_accumulate(const GridConst c, cons
 		// Only for sparse buckets (fewer than 2 items per entry: C5's hashed levels); dense ones (C2', ~4 per
 		// entry) update in place, where the list pass measured slower (r03bz: C2' 329 -> 335 us; r03ca/cb:
 		// threshold 1 vs 2 items per entry, C5 1.262 vs 1.20 ms on a faster box, C2' unchanged).
+		const FusedStep fs = fused_adam_step(fa);  // block-uniform: once, not per pair
 		if (t >= 2 * n_e) {
 			for (uint32_t k = threadIdx.x; k < n_e * F / 2; k += blockDim.x) {
 				uint32_t ia, ib;
 				pair_slots<F>(k, NEP, ia, ib);
-				fused_adam_pair(fa, e0 * F / 2 + k, (f16)fix_to_f32(acc[ia]), (f16)fix_to_f32(acc[ib]));
+				fused_adam_pair(fa, fs, e0 * F / 2 + k, (f16)fix_to_f32(acc[ia]), (f16)fix_to_f32(acc[ib]));
 			}
 			return;
 		}
@@ -1166,7 +1167,7 @@ __global__ void __launch_bounds__(SC_BT) k_sc_accumulate(const GridConst c, cons
 			const uint32_t k = list[i];
 			uint32_t ia, ib;
 			pair_slots<F>(k, NEP, ia, ib);
-			fused_adam_pair(fa, e0 * F / 2 + k, (f16)fix_to_f32(acc[ia]), (f16)fix_to_f32(acc[ib]));
+			fused_adam_pair(fa, fs, e0 * F / 2 + k, (f16)fix_to_f32(acc[ia]), (f16)fix_to_f32(acc[ib]));
 		}
 		return;
 	}

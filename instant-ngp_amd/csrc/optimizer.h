@@ -217,10 +217,25 @@ __device__ __forceinline__ bool fused_adam_load(const FusedAdam& fa, uint32_t r,
 	p.q0 = rp[0]; p.q1 = rp[1]; p.q2 = rp[2];
 	return true;
 }
-__device__ __forceinline__ void fused_adam_store(const FusedAdam& fa, uint32_t r, FusedPair& p) {
-	const AdamConfig c = fa.cfg_dev ? *fa.cfg_dev : fa.cfg;
-	const uint32_t step = (fa.step_base ? *fa.step_base : 0u) + fa.step_add;
-	const float lr = lr_schedule(c, step);
+// What every pair of one launch shares: the hyperparameters (from device memory in a captured step), the optimizer
+// step and its scheduled learning rate (a loop). A block that updates many pairs derives it once, ahead of them;
+// left inside the per-pair store it was re-derived every round (C2: 147.2 -> 144.9 us per step).
+struct FusedStep {
+	AdamConfig c;
+	uint32_t step;
+	float lr;
+};
+__device__ __forceinline__ FusedStep fused_adam_step(const FusedAdam& fa) {
+	FusedStep fs;
+	fs.c = fa.cfg_dev ? *fa.cfg_dev : fa.cfg;
+	fs.step = (fa.step_base ? *fa.step_base : 0u) + fa.step_add;
+	fs.lr = lr_schedule(fs.c, fs.step);
+	return fs;
+}
+__device__ __forceinline__ void fused_adam_store(const FusedAdam& fa, const FusedStep& fs, uint32_t r, FusedPair& p) {
+	const AdamConfig& c = fs.c;
+	const uint32_t step = fs.step;
+	const float lr = fs.lr;
 	const float d = c.ema_decay;
 	float m1[2] = {p.q0[0], p.q0[1]}, m2[2] = {p.q0[2], p.q0[3]}, ema[2] = {p.q1[2], p.q1[3]};
 	uint32_t steps[2] = {__float_as_uint(p.q1[0]), __float_as_uint(p.q1[1])};
@@ -248,9 +263,14 @@ __device__ __forceinline__ void fused_adam_store(const FusedAdam& fa, uint32_t r
 	rp[2] = f32x4{__uint_as_float(done[0]), __uint_as_float(done[1]), w[0], w[1]};
 	*(f16x2*)(fa.w16 + 2 * (size_t)r) = f16x2{(f16)w[0], (f16)w[1]};
 }
+__device__ __forceinline__ void fused_adam_pair(const FusedAdam& fa, const FusedStep& fs, uint32_t r, f16 g0h, f16 g1h) {
+	FusedPair p;
+	if (fused_adam_load(fa, r, g0h, g1h, p)) fused_adam_store(fa, fs, r, p);
+}
+// a thread's only pair (k_sc_split_reduce): the step is derived once the pair is known to be updated
 __device__ __forceinline__ void fused_adam_pair(const FusedAdam& fa, uint32_t r, f16 g0h, f16 g1h) {
 	FusedPair p;
-	if (fused_adam_load(fa, r, g0h, g1h, p)) fused_adam_store(fa, r, p);
+	if (fused_adam_load(fa, r, g0h, g1h, p)) fused_adam_store(fa, fused_adam_step(fa), r, p);
 }
 
 // The trainer's device control block: ctl[0] optimizer step, ctl[1] block counter, AdamConfig at
