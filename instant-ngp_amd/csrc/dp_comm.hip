@@ -13,11 +13,8 @@
 #include <cstring>
 #include <string>
 
-#include "../../include/ngp_engine.h"
-#include "common.h"
+#include "abi_guard.h"
 #include "profiler.h"
-
-namespace ngp { void set_last_error(const char* msg); }
 
 struct ngp_dp_comm {
 	ncclComm_t comm = nullptr;

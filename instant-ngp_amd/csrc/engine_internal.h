@@ -18,6 +18,18 @@ struct Exchange {
 	bool rank_known = false;  // set_data_parallel (sharding possible) vs set_allreduce (all-reduce only)
 };
 void widen_f16(const _Float16* a, float* b, uint64_t n, hipStream_t s);  // dp_comm.hip
+// The batch of one training step from its dL/doutput (train_step_with, capture_training_step_with). dL_dinput: as
+// forward_backward_with's below
+struct StepBatch {
+	uint32_t n = 0;
+	const float* input = nullptr;
+	uint32_t input_stride = 0;
+	const void* dL_doutput = nullptr;
+	uint32_t dL_stride = 0;
+	float loss_scale = 0.f;
+	float* dL_dinput = nullptr;
+	uint32_t dL_dinput_stride = 0;
+};
 // ngp_forward_backward with the grid's lazy optimizer update fused into the backward (fopt may be NULL). dL_dinput
 // (here and below; NULL: none, and then exactly the launches without it): fp32 AoS [n x dL_dinput_stride], the input
 // gradient with respect to the forward's weights (BwdExtra::dL_dinput); must not alias the input in a training step
@@ -26,9 +38,8 @@ int forward_backward_with(ngp_model* m, void* stream, uint32_t n, const float* i
                           float* dL_dinput = nullptr, uint32_t dL_dinput_stride = 0);
 // ngp_trainer_capture_training_step with an explicit gradient exchange hook: `allreduce` (may be NULL)
 // runs on the gradient buffer between backward and optimizer, which scales by loss_scale * world.
-int capture_training_step_with(ngp_trainer* t, void* stream, uint32_t n, const float* input, uint32_t input_stride,
-                               const void* dL_doutput, uint32_t dL_stride, float loss_scale, uint32_t n_steps, int with_optimizer,
-                               const Exchange& ex, ngp_graph** out, float* dL_dinput = nullptr, uint32_t dL_dinput_stride = 0);
+int capture_training_step_with(ngp_trainer* t, void* stream, const StepBatch& batch, uint32_t n_steps, int with_optimizer,
+                               const Exchange& ex, ngp_graph** out);
 // The optimizer chain's JSON (Ema / ExponentialDecay / Adam, as ngp_trainer_create takes it) into c; and a trainer's
 // own configuration (the NeRF environment map's optimizer falls back to it, testbed.cu:4135-4136)
 struct AdamConfig;
@@ -45,7 +56,5 @@ constexpr uint32_t DENSITY_LAYOUT_ROW0 = 3;  // == MLP_LAYOUT_ROW0 (mlp.h)
 int density_impl(ngp_model* m, void* stream, uint32_t n, const float* input, uint32_t input_stride, void* output,
                  uint32_t output_stride, uint32_t output_layout, int use_inference_params);
 // One eager step of what capture_training_step_with records (the host-callback exchange of gloo ranks)
-int train_step_with(ngp_trainer* t, void* stream, uint32_t n, const float* input, uint32_t input_stride, const void* dL_doutput,
-                    uint32_t dL_stride, float loss_scale, const Exchange& ex, float* dL_dinput = nullptr,
-                    uint32_t dL_dinput_stride = 0);
+int train_step_with(ngp_trainer* t, void* stream, const StepBatch& batch, const Exchange& ex);
 }  // namespace ngp

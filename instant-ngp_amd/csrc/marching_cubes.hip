@@ -21,14 +21,12 @@
 #include <mutex>
 #include <string>
 
-#include "../../include/ngp_engine.h"
-#include "common.h"
+#include "abi_guard.h"
 #include "marching_cubes.h"
 #include "nerf_device.h"
 #include "profiler.h"
 
 namespace ngp {
-void set_last_error(const char* msg);
 namespace mc {
 namespace {
 
@@ -354,7 +352,6 @@ int invalid(const char* what) {
 	ngp::set_last_error(what);
 	return NGP_INVALID;
 }
-void check_rc(int rc) { if (rc != NGP_OK) throw Error(ngp_last_error()); }
 
 // the generated table, uploaded once per device
 void upload_tables() {
@@ -447,7 +444,7 @@ int ngp_density_on_grid(ngp_model* model, void* stream, int kind, const uint32_t
 	if (width != 3 && width != 7) return mc::invalid("ngp_density_on_grid: the model must take 3 inputs or be a NerfNetwork (7)");
 	if (kind == NGP_MC_NERF && width != 7) return mc::invalid("ngp_density_on_grid: NGP_MC_NERF needs a NerfNetwork");
 	if (kind == NGP_MC_SDF && width != 3) return mc::invalid("ngp_density_on_grid: NGP_MC_SDF needs a 3-input network");
-	try {
+	NGP_TRY({
 		hipStream_t s = (hipStream_t)stream;
 		mc::SampleArgs a{};
 		a.rx = res[0]; a.ry = res[1];
@@ -465,7 +462,7 @@ int ngp_density_on_grid(ngp_model* model, void* stream, int kind, const uint32_t
 		mc::Buf pos_buf, out_buf;
 		float* pos = pos_buf.alloc<float>((size_t)cap * width);
 		f16* out16 = out_buf.alloc<f16>((size_t)cap * 16);
-		mc::check_rc(ngp_model_reserve(model, cap));
+		check_rc(ngp_model_reserve(model, cap));
 		for (uint64_t start = 0; start < a.n_points; start += per) {
 			const uint32_t n = (uint32_t)std::min<uint64_t>(per, a.n_points - start);
 			const uint32_t n_pad = next_multiple(n, 256u);
@@ -474,8 +471,8 @@ int ngp_density_on_grid(ngp_model* model, void* stream, int kind, const uint32_t
 				hipLaunchKernelGGL(mc::k_mc_positions, dim3(n_pad / 256), dim3(256), 0, s, a, start, n_pad, pos);
 			}
 			// SoA: output row 0 is n_pad contiguous halves
-			if (width == 7) mc::check_rc(ngp_density(model, s, n_pad, pos, 7, out16, n_pad, NGP_LAYOUT_SOA, use_inference_params));
-			else mc::check_rc(ngp_inference(model, s, n_pad, pos, 3, out16, n_pad, NGP_LAYOUT_SOA, use_inference_params));
+			if (width == 7) check_rc(ngp_density(model, s, n_pad, pos, 7, out16, n_pad, NGP_LAYOUT_SOA, use_inference_params));
+			else check_rc(ngp_inference(model, s, n_pad, pos, 3, out16, n_pad, NGP_LAYOUT_SOA, use_inference_params));
 			{
 				ProfScope ps("mc_values", s);
 				hipLaunchKernelGGL(mc::k_mc_values, dim3(n_pad / 256), dim3(256), 0, s, n, out16, kind, density_activation, density_out + start);
@@ -483,11 +480,7 @@ int ngp_density_on_grid(ngp_model* model, void* stream, int kind, const uint32_t
 		}
 		NGP_HIP(hipGetLastError());
 		NGP_HIP(hipStreamSynchronize(s));  // the workspace is released on return
-		return NGP_OK;
-	} catch (const std::exception& e) {
-		ngp::set_last_error(e.what());
-		return NGP_ERROR;
-	}
+	});
 }
 
 int ngp_marching_cubes(void* stream, const float* density, const uint32_t* res, const float* aabb_min, const float* aabb_max,
@@ -495,7 +488,7 @@ int ngp_marching_cubes(void* stream, const float* density, const uint32_t* res, 
 	if (!density || !out) return mc::invalid("ngp_marching_cubes: null argument");
 	if (const char* why = mc::check_grid(res, aabb_min, aabb_max)) return mc::invalid((std::string("ngp_marching_cubes: ") + why).c_str());
 	if (!std::isfinite(thresh)) return mc::invalid("ngp_marching_cubes: non-finite threshold");
-	try {
+	NGP_TRY({
 		hipStream_t s = (hipStream_t)stream;
 		mc::upload_tables();
 		mc::Grid g{};
@@ -550,11 +543,7 @@ int ngp_marching_cubes(void* stream, const float* density, const uint32_t* res, 
 			NGP_HIP(hipStreamSynchronize(s));  // the vertex map is released on return
 		}
 		*out = mesh.release();
-		return NGP_OK;
-	} catch (const std::exception& e) {
-		ngp::set_last_error(e.what());
-		return NGP_ERROR;
-	}
+	});
 }
 
 int ngp_mesh_vertex_colors(ngp_mesh* mesh, ngp_model* model, void* stream, int kind, const float* warp_aabb_min,
@@ -569,7 +558,7 @@ int ngp_mesh_vertex_colors(ngp_mesh* mesh, ngp_model* model, void* stream, int k
 				if (!(warp_aabb_max[k] - warp_aabb_min[k] > 0.f)) return mc::invalid("ngp_mesh_vertex_colors: empty warp box");
 		if (rgb_activation > nerf::ACT_EXP) return mc::invalid("ngp_mesh_vertex_colors: unknown rgb activation");
 	}
-	try {
+	NGP_TRY({
 		hipStream_t s = (hipStream_t)stream;
 		const uint32_t n = mesh->n_verts;
 		if (n == 0) return NGP_OK;
@@ -591,7 +580,7 @@ int ngp_mesh_vertex_colors(ngp_mesh* mesh, ngp_model* model, void* stream, int k
 		mc::Buf in_buf, out_buf;
 		float* in = in_buf.alloc<float>((size_t)cap * 7);
 		f16* rgbd = out_buf.alloc<f16>((size_t)cap * 4);
-		mc::check_rc(ngp_model_reserve(model, cap));
+		check_rc(ngp_model_reserve(model, cap));
 		for (uint32_t start = 0; start < n; start += batch) {
 			const uint32_t m = std::min(batch, n - start), m_pad = next_multiple(m, 256u);
 			{
@@ -599,7 +588,7 @@ int ngp_mesh_vertex_colors(ngp_mesh* mesh, ngp_model* model, void* stream, int k
 				hipLaunchKernelGGL(mc::k_mc_color_inputs, dim3(m_pad / 256), dim3(256), 0, s, m, m_pad, mesh->verts + 3 * (size_t)start,
 				                   mesh->normals + 3 * (size_t)start, a, in);
 			}
-			mc::check_rc(ngp_inference(model, s, m_pad, in, 7, rgbd, 4, NGP_LAYOUT_AOS_RGBD, use_inference_params));
+			check_rc(ngp_inference(model, s, m_pad, in, 7, rgbd, 4, NGP_LAYOUT_AOS_RGBD, use_inference_params));
 			{
 				ProfScope ps("mc_colors", s);
 				hipLaunchKernelGGL(mc::k_mc_colors_nerf, dim3(m_pad / 256), dim3(256), 0, s, m, rgbd, rgb_activation,
@@ -608,11 +597,7 @@ int ngp_mesh_vertex_colors(ngp_mesh* mesh, ngp_model* model, void* stream, int k
 		}
 		NGP_HIP(hipGetLastError());
 		NGP_HIP(hipStreamSynchronize(s));  // the workspace is released on return
-		return NGP_OK;
-	} catch (const std::exception& e) {
-		ngp::set_last_error(e.what());
-		return NGP_ERROR;
-	}
+	});
 }
 
 int ngp_mesh_counts(const ngp_mesh* mesh, uint32_t* n_verts, uint32_t* n_tris) {
@@ -625,7 +610,7 @@ int ngp_mesh_counts(const ngp_mesh* mesh, uint32_t* n_verts, uint32_t* n_tris) {
 int ngp_mesh_read(const ngp_mesh* mesh, void* stream, float* verts_host, float* normals_host, float* colors_host, int32_t* faces_host) {
 	if (!mesh) return mc::invalid("ngp_mesh_read: null mesh");
 	if (colors_host && mesh->n_verts && !mesh->colors) return mc::invalid("ngp_mesh_read: no colours (ngp_mesh_vertex_colors first)");
-	try {
+	NGP_TRY({
 		hipStream_t s = (hipStream_t)stream;
 		const size_t vb = (size_t)mesh->n_verts * 12, fb = (size_t)mesh->n_tris * 12;
 		if (vb && verts_host) NGP_HIP(hipMemcpyAsync(verts_host, mesh->verts, vb, hipMemcpyDeviceToHost, s));
@@ -633,11 +618,7 @@ int ngp_mesh_read(const ngp_mesh* mesh, void* stream, float* verts_host, float* 
 		if (vb && colors_host) NGP_HIP(hipMemcpyAsync(colors_host, mesh->colors, vb, hipMemcpyDeviceToHost, s));
 		if (fb && faces_host) NGP_HIP(hipMemcpyAsync(faces_host, mesh->faces, fb, hipMemcpyDeviceToHost, s));
 		if (vb || fb) NGP_HIP(hipStreamSynchronize(s));
-		return NGP_OK;
-	} catch (const std::exception& e) {
-		ngp::set_last_error(e.what());
-		return NGP_ERROR;
-	}
+	});
 }
 
 int ngp_mesh_save(const char* path, uint32_t n_verts, const float* verts_host, const float* normals_host, const float* colors_host,

@@ -84,7 +84,7 @@ extern "C" __attribute__((visibility("default"))) int ngp_debug_math_check(int w
 int run_sampler(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, SampleArgs a, const Camera* cams,
                 const DistMap* dist) {
 	if (!ds || !cfg || !a.bitfield || !a.ray_indices || !a.rays || !a.numsteps || !a.coords || !a.counters) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		if (!a.n_rays_total_for_image_idx) a.n_rays_total_for_image_idx = a.n_rays;
 		static thread_local Buf tmp, tmpf;
 		if (a.n_rays == 0) { NGP_HIP(hipMemsetAsync(a.counters, 0, 8, S(stream))); return NGP_OK; }
@@ -98,7 +98,7 @@ int run_compute_loss(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, voi
 	if (!ds || !cfg || !a.ray_counter || !a.network_output || !a.numsteps || !a.coords_in || !a.coords_out || !a.dloss_doutput ||
 	    !a.compacted_counter || !a.mean_density)
 		return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		if (!a.n_rays_total_for_image_idx) a.n_rays_total_for_image_idx = a.n_rays;
 		if (!a.state) a.state_cap = 0;
 		if (!a.envmap) a.env_acc = nullptr;
@@ -170,7 +170,7 @@ static void store_image(Dataset& ds, uint32_t i, const void* host, uint32_t type
 static int ngp_nerf_dataset_create_typed_impl(uint32_t n_images, const ngp_nerf_image* images, const void* const* pixels,
                                               const uint32_t* types, ngp_nerf_dataset** out) {
 	if (!out || !images || !pixels || n_images == 0) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		auto d = std::make_unique<ngp_nerf_dataset>();
 		d->ds.n_images = n_images;
 		uint64_t total = 0;
@@ -262,7 +262,7 @@ int ngp_nerf_dataset_set_image(ngp_nerf_dataset* d, uint32_t image, const void* 
                                uint32_t height) {
 	if (!d || !pixels_host || image >= d->ds.n_images || !image_type_ok(image_type)) return NGP_INVALID;
 	if (width != d->ds.cams[image].width || height != d->ds.cams[image].height) return NGP_INVALID;  // resizing is not built
-	NERF_TRY({
+	NGP_TRY({
 		Dataset& ds = d->ds;
 		NGP_HIP(hipDeviceSynchronize());  // no sampler or loss pass may still be reading the image or the table
 		const bool table_changes = image_type != IMAGE_BYTE || ds.types[image] != IMAGE_BYTE;
@@ -281,7 +281,7 @@ int ngp_nerf_dataset_image(const ngp_nerf_dataset* d, uint32_t image, void* out_
 	if (image_type) *image_type = type;
 	if (!out_host) return NGP_OK;
 	const void* src = type == IMAGE_BYTE ? (const void*)(ds.d_pixels + ds.cams[image].pixel_offset) : (const void*)ds.hdr[image];
-	NERF_TRY(NGP_HIP(hipMemcpy(out_host, src, bytes, hipMemcpyDeviceToHost)));
+	NGP_TRY(NGP_HIP(hipMemcpy(out_host, src, bytes, hipMemcpyDeviceToHost)));
 }
 
 void ngp_nerf_dataset_destroy(ngp_nerf_dataset* d) { delete d; }
@@ -290,7 +290,7 @@ void ngp_nerf_dataset_destroy(ngp_nerf_dataset* d) { delete d; }
 // per pixel, done on the host, so the stored value is (float)pixel * depth_scale bit for bit
 int ngp_nerf_dataset_set_depth(ngp_nerf_dataset* d, uint32_t image, const void* depth_host, int dtype, float depth_scale) {
 	if (!d || image >= d->ds.n_images || (dtype != 0 && dtype != 1) || std::isnan(depth_scale)) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		Dataset& ds = d->ds;
 		NGP_HIP(hipDeviceSynchronize());  // no loss pass may still be reading the pointers or the image
 		if (ds.depth.empty()) ds.depth.assign(ds.n_images, nullptr);
@@ -319,7 +319,7 @@ int ngp_nerf_dataset_depth(const ngp_nerf_dataset* d, uint32_t image, float* out
 	if (src && out_host && cap < n) return NGP_INVALID;
 	if (has_depth) *has_depth = src ? 1 : 0;
 	if (!src || !out_host) return NGP_OK;
-	NERF_TRY(NGP_HIP(hipMemcpy(out_host, src, n * 4, hipMemcpyDeviceToHost)));
+	NGP_TRY(NGP_HIP(hipMemcpy(out_host, src, n * 4, hipMemcpyDeviceToHost)));
 }
 
 int ngp_nerf_generate_training_samples(const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg, void* stream, uint32_t n_rays,
@@ -363,15 +363,15 @@ int ngp_nerf_training_pixels(const ngp_nerf_dataset* ds, const ngp_nerf_config* 
                              uint32_t n_rays_total, ngp_rng rng, const ngp_nerf_error_cdfs* cdfs, uint32_t* img, float* uv, float* pdf) {
 	ErrorCdfs e;
 	if (!ds || !cfg || !img || !uv || !pdf || !error_cdfs_arg(cdfs, &e)) return NGP_INVALID;
-	NERF_TRY(training_pixels(ds->ds, *cfg, n_rays, ray_offset, n_rays_total ? n_rays_total : n_rays, Rng{rng.state, rng.inc}, e, img, uv,
-	                         pdf, S(stream)));
+	NGP_TRY(training_pixels(ds->ds, *cfg, n_rays, ray_offset, n_rays_total ? n_rays_total : n_rays, Rng{rng.state, rng.inc}, e, img, uv,
+	                        pdf, S(stream)));
 }
 int ngp_nerf_training_pixels_host(uint32_t n_images, const ngp_nerf_image* images, const ngp_nerf_config* cfg, uint32_t n_rays,
                                   uint32_t ray_offset, uint32_t n_rays_total, ngp_rng rng, const ngp_nerf_error_cdfs* cdfs,
                                   uint32_t* img, float* uv, float* pdf) {
 	ErrorCdfs e;
 	if (!images || n_images == 0 || !cfg || !img || !uv || !pdf || !error_cdfs_arg(cdfs, &e)) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		std::vector<Camera> cams(n_images);
 		for (uint32_t i = 0; i < n_images; ++i) {
 			if (images[i].width == 0 || images[i].height == 0) return NGP_INVALID;
@@ -440,7 +440,7 @@ int ngp_nerf_compute_loss_envmap(const ngp_nerf_dataset* ds, const ngp_nerf_conf
                                  uint32_t* compacted_counter, const float* mean_density, float loss_scale, const float* envmap,
                                  uint32_t env_width, uint32_t env_height, uint32_t envmap_loss_type, float* envmap_gradient) {
 	if (!envmap || !rays || !envmap_dims_ok(env_width, env_height) || envmap_loss_type > LOSS_RELL2) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		static thread_local Buf acc;
 		LossArgs a = public_loss_args(n_rays, n_rays_total, rng, max_samples_compacted, ray_counter, network_output, ray_indices, rays,
 		                              numsteps, coords_in, coords_out, dloss_doutput, loss, compacted_counter, mean_density, loss_scale);
@@ -494,7 +494,7 @@ int ngp_nerf_compute_loss_exposure(const ngp_nerf_dataset* ds, const ngp_nerf_co
 	if (exposure_gradient && (!exposure || (cdfs && cdfs->cdf_img))) return NGP_INVALID;
 	const uint32_t total = n_rays_total ? n_rays_total : n_rays;
 	if (exposure_gradient && (uint64_t)total * ds->ds.n_images > 0xffffffffull) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		static thread_local Buf acc;
 		LossArgs a = public_loss_args(n_rays, n_rays_total, rng, max_samples_compacted, ray_counter, network_output, ray_indices, rays,
 		                              numsteps, coords_in, coords_out, dloss_doutput, loss, compacted_counter, mean_density, loss_scale);
@@ -527,7 +527,7 @@ int ngp_nerf_compute_loss_exposure(const ngp_nerf_dataset* ds, const ngp_nerf_co
 
 int ngp_envmap_lookup(void* stream, uint32_t width, uint32_t height, uint32_t n, const float* dirs, uint32_t* texels, float* weights) {
 	if (!envmap_dims_ok(width, height) || (n && (!dirs || !texels || !weights))) return NGP_INVALID;
-	NERF_TRY({ envmap_lookup_device(width, height, n, dirs, texels, weights, S(stream)); });
+	NGP_TRY({ envmap_lookup_device(width, height, n, dirs, texels, weights, S(stream)); });
 }
 
 int ngp_envmap_lookup_host(uint32_t width, uint32_t height, uint32_t n, const float* dirs, uint32_t* texels, float* weights) {
@@ -539,7 +539,7 @@ int ngp_envmap_lookup_host(uint32_t width, uint32_t height, uint32_t n, const fl
 int ngp_envmap_deposit(void* stream, uint32_t width, uint32_t height, uint32_t n, const float* dirs, const void* values_f16,
                        float* gradient) {
 	if (!envmap_dims_ok(width, height) || !gradient || (n && (!dirs || !values_f16))) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		static thread_local Buf acc;
 		const size_t words = envmap_acc_words64(width, height);
 		unsigned long long* a = acc.get<unsigned long long>(words);
@@ -553,7 +553,7 @@ int ngp_envmap_deposit(void* stream, uint32_t width, uint32_t height, uint32_t n
 int ngp_nerf_distortion_lookup(void* stream, uint32_t width, uint32_t height, uint32_t n, const float* uv, uint32_t* texels,
                                float* weights, const float* map, float* offsets) {
 	if (!distortion_dims_ok(width, height) || (n && (!uv || !texels || !weights)) || (offsets && !map)) return NGP_INVALID;
-	NERF_TRY({ distortion_lookup_device(width, height, n, uv, texels, weights, map, offsets, S(stream)); });
+	NGP_TRY({ distortion_lookup_device(width, height, n, uv, texels, weights, map, offsets, S(stream)); });
 }
 
 int ngp_nerf_distortion_lookup_host(uint32_t width, uint32_t height, uint32_t n, const float* uv, uint32_t* texels, float* weights,
@@ -573,7 +573,7 @@ int ngp_nerf_distortion_deposit(const ngp_nerf_dataset* ds, const ngp_nerf_confi
 	if (!ds || !cfg || !ray_counter || !ray_indices || !ray_gradients || !accumulator || n_rays_total == 0 ||
 	    !distortion_dims_ok(width, height) || (uint64_t)n_rays_total * ds->ds.n_images > 0xffffffffull)
 		return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		DistDepositArgs a{};
 		// kept rays are distinct ids below n_rays_total: at most that many rows
 		a.n_rays_cap = n_rays_total; a.n_rays_total = n_rays_total; a.n_images = ds->ds.n_images;
@@ -586,7 +586,7 @@ int ngp_nerf_distortion_deposit(const ngp_nerf_dataset* ds, const ngp_nerf_confi
 
 int ngp_nerf_distortion_gradient(void* stream, uint32_t width, uint32_t height, const uint64_t* accumulator, float* gradient) {
 	if (!distortion_dims_ok(width, height) || !accumulator || !gradient) return NGP_INVALID;
-	NERF_TRY({ distortion_gradient_f32(width, height, (const unsigned long long*)accumulator, gradient, S(stream)); });
+	NGP_TRY({ distortion_gradient_f32(width, height, (const unsigned long long*)accumulator, gradient, S(stream)); });
 }
 
 int ngp_envmap_optimizer_step(void* stream, const char* optimizer_json, uint32_t step, float loss_scale, uint32_t n, float* params,
@@ -594,7 +594,7 @@ int ngp_envmap_optimizer_step(void* stream, const char* optimizer_json, uint32_t
                               float* ema_params) {
 	if (!optimizer_json || !params || !gradient || !first_moments || !second_moments || !param_steps || !(loss_scale > 0.f))
 		return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		AdamConfig c;
 		parse_optimizer_json(optimizer_json, c);
 		AdamState st{};
@@ -607,7 +607,7 @@ int ngp_envmap_optimizer_step(void* stream, const char* optimizer_json, uint32_t
 int ngp_nerf_fill_rollover(void* stream, uint32_t n_elements, uint32_t stride, const uint32_t* n_input, void* data, int dtype,
                            int rescale) {
 	if (!n_input || !data) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		if (dtype == 1) fill_rollover_f16(n_elements, stride, n_input, (f16*)data, rescale != 0, S(stream));
 		else fill_rollover_f32(n_elements, stride, n_input, (float*)data, S(stream));
 	});
@@ -616,7 +616,7 @@ int ngp_nerf_fill_rollover(void* stream, uint32_t n_elements, uint32_t stride, c
 int ngp_nerf_grid_generate_samples(void* stream, const ngp_nerf_config* cfg, uint32_t n, ngp_rng rng, uint32_t step,
                                    const float* grid, uint32_t n_cascades, float thresh, float* positions, uint32_t* indices) {
 	if (!cfg || !grid || !positions || !indices) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		static thread_local Buf mask;
 		grid_generate_samples(n, Rng{rng.state, rng.inc}, step, *cfg, grid, n_cascades, thresh, positions, indices,
 		                      mask.get<uint32_t>(grid_mask_words(n_cascades)), S(stream));
@@ -624,12 +624,12 @@ int ngp_nerf_grid_generate_samples(void* stream, const ngp_nerf_config* cfg, uin
 }
 int ngp_nerf_grid_splat_max(void* stream, uint32_t n, const uint32_t* indices, const void* density_rm, uint32_t act, float* tmp) {
 	if (!indices || !density_rm || !tmp) return NGP_INVALID;
-	NERF_TRY(grid_splat_max(n, indices, (const f16*)density_rm, act, tmp, S(stream)));
+	NGP_TRY(grid_splat_max(n, indices, (const f16*)density_rm, act, tmp, S(stream)));
 }
 int ngp_nerf_grid_splat_max_cells(void* stream, uint32_t n, const uint32_t* indices, const void* density_rm, uint32_t act,
                                   float* tmp, uint32_t n_cells) {
 	if ((n && (!indices || !density_rm)) || !tmp || n_cells == 0 || n_cells % 8192 || n_cells > 8 * GRID_N_CELLS) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		static thread_local Buf scratch;
 		grid_splat_max_binned(n, indices, (const f16*)density_rm, act, tmp, n_cells,
 		                      scratch.get<uint32_t>(grid_splat_scratch_u32(n, n_cells)), S(stream));
@@ -637,17 +637,17 @@ int ngp_nerf_grid_splat_max_cells(void* stream, uint32_t n, const uint32_t* indi
 }
 int ngp_nerf_grid_ema(void* stream, uint32_t n, float decay, float* grid, const float* tmp) {
 	if (!grid || !tmp) return NGP_INVALID;
-	NERF_TRY(grid_ema(n, decay, grid, tmp, S(stream)));
+	NGP_TRY(grid_ema(n, decay, grid, tmp, S(stream)));
 }
 int ngp_nerf_grid_mean_and_bitfield(void* stream, const float* grid, uint32_t max_cascade, float* mean, uint8_t* bitfield) {
 	if (!grid || !mean || !bitfield || max_cascade >= CASCADES) return NGP_INVALID;
-	NERF_TRY(grid_mean_bitfield(grid, max_cascade, mean, bitfield, S(stream)));
+	NGP_TRY(grid_mean_bitfield(grid, max_cascade, mean, bitfield, S(stream)));
 }
 
 // ---- rendering ---------------------------------------------------------------------------------
 int ngp_nerf_renderer_create(ngp_nerf_renderer** out) {
 	if (!out) return NGP_INVALID;
-	NERF_TRY({ *out = new ngp_nerf_renderer(); });
+	NGP_TRY({ *out = new ngp_nerf_renderer(); });
 }
 void ngp_nerf_renderer_destroy(ngp_nerf_renderer* r) { delete r; }
 int ngp_nerf_renderer_set_mode(ngp_nerf_renderer* r, int render_mode) {
@@ -684,7 +684,7 @@ int ngp_nerf_render(ngp_nerf_renderer* r, ngp_model* model, const ngp_nerf_confi
                     const uint8_t* bitfield, uint32_t spp, uint32_t sample_index, float min_transmittance, const float* background_rgba,
                     int use_inference_params, float* out_rgba) {
 	if (!r || !model || !cfg || !camera || !out_rgba || spp == 0) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		hipStream_t s = S(stream);
 		RenderArgs a{};
 		a.width = camera->width; a.height = camera->height;

@@ -7,13 +7,11 @@
 #include <memory>
 #include <vector>
 
-#include "../../include/ngp_engine.h"
+#include "abi_guard.h"
 #include "nerf.h"
 #include "nerf_camera.h"
 
 using namespace ngp;
-
-namespace ngp { void set_last_error(const char* msg); }
 
 // ---- device: per-image camera gradients (the two passes are described in nerf_camera.h) ----------------------------
 namespace ngp {
@@ -480,7 +478,7 @@ static int camera_gradients_abi(const ngp_nerf_config* cfg, void* stream, uint32
                                 const uint32_t* ray_counter, const uint32_t* ray_indices, const float* rays, const uint32_t* numsteps,
                                 const float* coords, const float* coords_gradient, uint32_t gradient_stride, float* pos_gradient,
                                 float* rot_gradient, const float* mats, float* dist_grad) {
-	try {
+	NGP_TRY({
 		nerf::CamGradArgs a{};
 		// kept rays are distinct ids below n_rays_total: at most that many rows
 		a.n_rays_cap = n_rays_total; a.n_rays_total = n_rays_total; a.n_images = n_images;
@@ -502,11 +500,7 @@ static int camera_gradients_abi(const ngp_nerf_config* cfg, void* stream, uint32
 		if (mats) nerf::camera_gradients_distortion(a, nerf::CamDistArgs{mats, 9, dist_grad}, nerf::CAM_GRAD_LANES, pos_gradient != nullptr,
 		                                            (hipStream_t)stream);
 		else nerf::camera_gradients(a, nerf::CAM_GRAD_LANES, (hipStream_t)stream);
-		return NGP_OK;
-	} catch (const std::exception& e) {
-		ngp::set_last_error(e.what());
-		return NGP_ERROR;
-	}
+	});
 }
 
 int ngp_nerf_camera_gradients(const ngp_nerf_config* cfg, void* stream, uint32_t n_rays_total, uint32_t n_images,

@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "abi_guard.h"
 #include "engine_internal.h"
 #include "knobs.h"
 #include "nerf.h"
@@ -21,9 +22,6 @@ using namespace ngp::nerf;
 struct ngp_nerf_dataset {
 	Dataset ds;
 };
-
-// share the engine's thread-local error string through a tiny hook in engine.hip
-namespace ngp { void set_last_error(const char* msg); }
 
 namespace ngp {
 namespace nerf {
@@ -97,21 +95,6 @@ struct Handoff {
 		if (sig) (void)hipFree(sig);
 	}
 };
-
-inline hipStream_t S(void* s) { return (hipStream_t)s; }
-
-inline void nerf_set_error(const char* m) { ngp::set_last_error(m); }
-
-#define NERF_TRY(...)                                  \
-	try {                                              \
-		__VA_ARGS__;                                   \
-		return NGP_OK;                                 \
-	} catch (const std::exception& e) {                \
-		nerf_set_error(e.what());                      \
-		return NGP_ERROR;                              \
-	}
-
-inline void check_rc(int rc) { if (rc != NGP_OK) throw Error(ngp_last_error()); }
 
 inline bool envmap_dims_ok(uint32_t w, uint32_t h) { return w >= 1 && h >= 1 && w <= 8192 && h <= 8192; }
 inline bool distortion_dims_ok(uint32_t w, uint32_t h) { return envmap_dims_ok(w, h); }  // the same bounds

@@ -201,7 +201,7 @@ extern "C" {
 int ngp_nerf_save_snapshot(ngp_nerf_trainer* t, void* stream, const char* path, const char* network_config_json,
                            int include_optimizer_state, int compress) {
 	if (!t || !path) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		NGP_HIP(hipStreamSynchronize(S(stream)));
 		Value root = snapshot_root(network_config_json);
 		Value snap = Value::object();
@@ -311,7 +311,7 @@ int ngp_nerf_save_snapshot(ngp_nerf_trainer* t, void* stream, const char* path, 
 
 int ngp_nerf_load_snapshot(ngp_nerf_trainer* t, void* stream, const char* path) {
 	if (!t || !path) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		t->drain();
 		hipStream_t s = S(stream);
 		NGP_HIP(hipStreamSynchronize(s));
@@ -445,7 +445,7 @@ int ngp_save_snapshot(ngp_trainer* t, void* stream, const char* path, const char
                       const float* aabb_min, const float* aabb_max, float bounding_radius, uint32_t training_step, float loss,
                       int include_optimizer_state, int compress) {
 	if (!t || !path || !mode) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		NGP_HIP(hipStreamSynchronize(S(stream)));
 		Value root = snapshot_root(network_config_json);
 		Value snap = Value::object();
@@ -465,7 +465,7 @@ int ngp_save_snapshot(ngp_trainer* t, void* stream, const char* path, const char
 int ngp_load_snapshot(ngp_trainer* t, void* stream, const char* path, uint32_t* training_step, float* loss, float* aabb_min,
                       float* aabb_max, float* bounding_radius) {
 	if (!t || !path) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		NGP_HIP(hipStreamSynchronize(S(stream)));
 		const Value root = load_network_config(path);
 		NGP_CHECK(root.find("snapshot"), std::string("File '") + path + "' does not contain a snapshot.");
@@ -488,7 +488,7 @@ int ngp_load_snapshot(ngp_trainer* t, void* stream, const char* path, uint32_t* 
 // member is a NeRF snapshot), so that a Testbed can switch mode before reset_network
 int ngp_snapshot_mode(const char* path, char* mode_buf, uint64_t cap) {
 	if (!path || !mode_buf || cap == 0) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		const Value root = load_network_config(path);
 		NGP_CHECK(root.find("snapshot"), std::string("File '") + path + "' does not contain a snapshot.");
 		const Value& snap = root.at("snapshot");
@@ -503,7 +503,7 @@ int ngp_snapshot_mode(const char* path, char* mode_buf, uint64_t cap) {
 
 int ngp_snapshot_network_config(const char* path, char* json_buf, uint64_t* size) {
 	if (!path || !size) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		Value root = load_network_config(path);
 		NGP_CHECK(root.is_map(), "snapshot: top level is not a map");
 		root.erase("snapshot");

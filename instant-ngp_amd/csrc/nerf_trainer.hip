@@ -77,7 +77,7 @@ extern "C" {
 int ngp_nerf_trainer_create(ngp_model* model, ngp_trainer* trainer, const ngp_nerf_dataset* ds, const ngp_nerf_config* cfg,
                             uint64_t seed, ngp_nerf_trainer** out) {
 	if (!model || !trainer || !ds || !cfg || !out) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		auto t = std::make_unique<ngp_nerf_trainer>();
 		t->model = model; t->trainer = trainer; t->data = ds; t->cfg = *cfg;
 		t->rng = HostPcg(seed);                          // m_rng = default_rng_t{m_seed} (testbed.cu:3906)
@@ -110,7 +110,7 @@ int ngp_nerf_trainer_get_config(const ngp_nerf_trainer* t, ngp_nerf_config* out)
 
 int ngp_nerf_trainer_set_config(ngp_nerf_trainer* t, const ngp_nerf_config* cfg) {
 	if (!t || !cfg) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		NGP_CHECK(cfg->max_cascade == t->cfg.max_cascade, "set_config: max_cascade sizes the density grid (reset the trainer)");
 		for (int k = 0; k < 3; ++k)
 			NGP_CHECK(cfg->aabb_min[k] == t->cfg.aabb_min[k] && cfg->aabb_max[k] == t->cfg.aabb_max[k],
@@ -174,7 +174,7 @@ static const char* const DISTORTION_VS_DATA_PARALLEL =
 
 int ngp_nerf_trainer_set_error_sampling(ngp_nerf_trainer* t, int focal_plane, int image) {
 	if (!t) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		NGP_CHECK(!(focal_plane || image) || !t->cam.optimize_extrinsics, ERROR_SAMPLING_VS_EXTRINSICS);
 		NGP_CHECK(!(focal_plane || image) || !t->dist.optimize, ERROR_SAMPLING_VS_DISTORTION);
 		NGP_CHECK(!image || !t->optimize_exposure, IMAGE_SAMPLING_VS_EXPOSURE);
@@ -214,7 +214,7 @@ static const char* const TRAIN_ENVMAP_VS_DATA_PARALLEL =
 
 int ngp_nerf_trainer_set_envmap(ngp_nerf_trainer* t, uint32_t width, uint32_t height, const float* rgba) {
 	if (!t || !envmap_dims_ok(width, height)) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		NGP_HIP(hipDeviceSynchronize());  // the last step may still read the old map (the prelaunched sampler reads none)
 		ngp_nerf_trainer::Envmap& e = t->env;
 		e.w = width; e.h = height; e.step = 0; e.ema_valid = false;
@@ -229,7 +229,7 @@ int ngp_nerf_trainer_set_envmap(ngp_nerf_trainer* t, uint32_t width, uint32_t he
 
 int ngp_nerf_trainer_clear_envmap(ngp_nerf_trainer* t) {
 	if (!t) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		NGP_HIP(hipDeviceSynchronize());
 		t->env.w = t->env.h = 0;
 		t->env.step = 0;
@@ -256,7 +256,7 @@ int ngp_nerf_trainer_envmap(const ngp_nerf_trainer* t, int which, float* out, ui
 	if (height) *height = t->env.h;
 	if (!out || !t->env.bound()) return NGP_OK;
 	if (cap < t->env.n()) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		NGP_HIP(hipDeviceSynchronize());
 		NGP_HIP(hipMemcpy(out, envmap_array(t, which), t->env.n() * sizeof(float), hipMemcpyDeviceToHost));
 	});
@@ -272,7 +272,7 @@ int ngp_nerf_trainer_envmap_device(const ngp_nerf_trainer* t, int which, const f
 
 int ngp_nerf_trainer_set_train_envmap(ngp_nerf_trainer* t, int train) {
 	if (!t) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		NGP_CHECK(!train || !t->dp(), TRAIN_ENVMAP_VS_DATA_PARALLEL);
 		t->env.train = train != 0;
 	});
@@ -286,7 +286,7 @@ int ngp_nerf_trainer_get_train_envmap(const ngp_nerf_trainer* t, int* train) {
 
 int ngp_nerf_trainer_set_envmap_training(ngp_nerf_trainer* t, int loss_type, const char* optimizer_json) {
 	if (!t || loss_type < -1 || loss_type > (int)LOSS_RELL2) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		AdamConfig c;
 		if (optimizer_json) parse_optimizer_json(optimizer_json, c);
 		t->env.loss_type = loss_type;
@@ -299,7 +299,7 @@ int ngp_nerf_trainer_set_envmap_training(ngp_nerf_trainer* t, int loss_type, con
 // the map is about to change outside a step: nothing may still trace through, or be launched to trace through, the old one
 int ngp_nerf_trainer_set_distortion_map(ngp_nerf_trainer* t, uint32_t width, uint32_t height, const float* params) {
 	if (!t || !distortion_dims_ok(width, height)) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		cameras_quiesce(t);
 		ngp_nerf_trainer::Distortion& d = t->dist;
 		d.w = width; d.h = height; d.step = 0; d.ema_valid = false;
@@ -316,7 +316,7 @@ int ngp_nerf_trainer_set_distortion_map(ngp_nerf_trainer* t, uint32_t width, uin
 
 int ngp_nerf_trainer_clear_distortion_map(ngp_nerf_trainer* t) {
 	if (!t) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		cameras_quiesce(t);
 		t->dist.w = t->dist.h = 0;
 		t->dist.step = 0;
@@ -344,7 +344,7 @@ int ngp_nerf_trainer_distortion_map(const ngp_nerf_trainer* t, int which, float*
 	if (height) *height = t->dist.h;
 	if (!out || !t->dist.bound()) return NGP_OK;
 	if (cap < t->dist.n()) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		NGP_HIP(hipDeviceSynchronize());
 		NGP_HIP(hipMemcpy(out, distortion_array(t, which), t->dist.n() * sizeof(float), hipMemcpyDeviceToHost));
 	});
@@ -364,7 +364,7 @@ int ngp_nerf_trainer_distortion_accumulator(const ngp_nerf_trainer* t, uint64_t*
 	if (words) *words = n;
 	if (!out || n == 0) return NGP_OK;
 	if (cap < n) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		NGP_HIP(hipDeviceSynchronize());
 		NGP_HIP(hipMemcpy(out, t->dist.acc.p, n * 8, hipMemcpyDeviceToHost));
 	});
@@ -372,7 +372,7 @@ int ngp_nerf_trainer_distortion_accumulator(const ngp_nerf_trainer* t, uint64_t*
 
 int ngp_nerf_trainer_set_distortion_training(ngp_nerf_trainer* t, const char* optimizer_json, uint32_t width, uint32_t height) {
 	if (!t || !distortion_dims_ok(width, height)) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		AdamConfig c;
 		if (optimizer_json) parse_optimizer_json(optimizer_json, c);
 		t->dist.opt_set = optimizer_json != nullptr;
@@ -383,7 +383,7 @@ int ngp_nerf_trainer_set_distortion_training(ngp_nerf_trainer* t, const char* op
 
 int ngp_nerf_trainer_set_optimize_distortion(ngp_nerf_trainer* t, int optimize) {
 	if (!t) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		const bool on = optimize != 0;
 		NGP_CHECK(!on || !t->dp(), DISTORTION_VS_DATA_PARALLEL);
 		NGP_CHECK(!on || !t->error_sampling(), ERROR_SAMPLING_VS_DISTORTION);
@@ -416,7 +416,7 @@ int ngp_nerf_trainer_get_camera_training(const ngp_nerf_trainer* t, ngp_nerf_cam
 int ngp_nerf_trainer_set_camera_training(ngp_nerf_trainer* t, const ngp_nerf_camera_training* c) {
 	if (!t || !c || c->n_steps_between_cam_updates == 0 || !(c->extrinsic_learning_rate >= 0.f) || !(c->extrinsic_l2_reg >= 0.f))
 		return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		NGP_CHECK(!c->optimize_extrinsics || !t->dp(),
 		          "camera pose refinement is single-GPU: the per-image gradient sums of a data-parallel trainer would need "
 		          "their own all-reduce");
@@ -458,7 +458,7 @@ static void exposures_changed(ngp_nerf_trainer* t) {
 
 int ngp_nerf_trainer_set_exposure_training(ngp_nerf_trainer* t, int optimize_exposure, float exposure_l2_reg) {
 	if (!t || !(exposure_l2_reg >= 0.0f) || std::isinf(exposure_l2_reg)) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		NGP_CHECK(!optimize_exposure || !t->dp(), EXPOSURE_VS_DATA_PARALLEL);
 		NGP_CHECK(!optimize_exposure || !t->sample_image_by_error, IMAGE_SAMPLING_VS_EXPOSURE);
 		const bool on = optimize_exposure != 0;
@@ -491,7 +491,7 @@ int ngp_nerf_trainer_set_camera_exposure(ngp_nerf_trainer* t, uint32_t i, const 
 	if (!t || !rgb || i >= t->cams.size()) return NGP_INVALID;
 	for (int k = 0; k < 3; ++k)
 		if (!std::isfinite(rgb[k])) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		check_rc(ngp_exposure_optimizer_reset_one(t->expo, i));
 		ngp_adam_state e;
 		check_rc(ngp_exposure_optimizer_get(t->expo, i, &e));
@@ -507,12 +507,12 @@ int ngp_nerf_trainer_exposure_optimizer_state(const ngp_nerf_trainer* t, uint32_
 
 int ngp_nerf_trainer_camera_extrinsics(const ngp_nerf_trainer* t, uint32_t i, float* out) {
 	if (!t || !out || i >= t->cams.size()) return NGP_INVALID;
-	NERF_TRY(t->refined_xform(i, out));
+	NGP_TRY(t->refined_xform(i, out));
 }
 
 int ngp_nerf_trainer_set_camera_extrinsics(ngp_nerf_trainer* t, uint32_t i, const float* xform) {
 	if (!t || !xform || i >= t->cams.size()) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		cameras_quiesce(t);
 		memcpy(&t->xforms[(size_t)12 * i], xform, 48);
 		check_rc(ngp_pose_optimizer_reset_one(t->pose, i));
@@ -524,7 +524,7 @@ int ngp_nerf_trainer_set_camera_extrinsics(ngp_nerf_trainer* t, uint32_t i, cons
 
 int ngp_nerf_trainer_reset_camera_extrinsics(ngp_nerf_trainer* t) {
 	if (!t) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		cameras_quiesce(t);
 		check_rc(ngp_pose_optimizer_reset(t->pose));
 		check_rc(ngp_exposure_optimizer_reset(t->expo));  // :2930-2932
@@ -554,19 +554,19 @@ int ngp_nerf_trainer_pose_optimizer_state(const ngp_nerf_trainer* t, uint32_t i,
 int ngp_nerf_trainer_set_data_parallel(ngp_nerf_trainer* t, uint32_t rank, uint32_t world, ngp_allreduce_fn allreduce, void* user) {
 	if (!t || world == 0 || rank >= world || (world > 1 && !allreduce)) return NGP_INVALID;
 	if (allreduce && t->cam.optimize_extrinsics) {
-		nerf_set_error("camera pose refinement is single-GPU: turn optimize_extrinsics off before setting an exchange hook");
+		set_last_error("camera pose refinement is single-GPU: turn optimize_extrinsics off before setting an exchange hook");
 		return NGP_ERROR;
 	}
 	if (allreduce && t->optimize_exposure) {
-		nerf_set_error("exposure optimisation is single-GPU: turn optimize_exposure off before setting an exchange hook");
+		set_last_error("exposure optimisation is single-GPU: turn optimize_exposure off before setting an exchange hook");
 		return NGP_ERROR;
 	}
 	if (allreduce && t->env.train) {
-		nerf_set_error(TRAIN_ENVMAP_VS_DATA_PARALLEL);
+		set_last_error(TRAIN_ENVMAP_VS_DATA_PARALLEL);
 		return NGP_ERROR;
 	}
 	if (allreduce && t->dist.optimize) {
-		nerf_set_error(DISTORTION_VS_DATA_PARALLEL);
+		set_last_error(DISTORTION_VS_DATA_PARALLEL);
 		return NGP_ERROR;
 	}
 	t->drain();
@@ -846,7 +846,7 @@ static bool error_map_step_done(ngp_nerf_trainer* t, hipStream_t s) {
 
 int ngp_nerf_trainer_error_map(ngp_nerf_trainer* t, int which, float* out, uint64_t cap, ngp_nerf_error_map_info* info) {
 	if (!t || which < 0 || which > 4) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		const uint32_t n_img = t->data->ds.n_images;
 		const uint64_t sizes[5] = {(uint64_t)t->em_w * t->em_h * n_img, (uint64_t)t->em_cdf_w * t->em_cdf_h * n_img,
 		                           (uint64_t)t->em_cdf_h * n_img, t->em_cdf_valid ? n_img : 0u, t->em_pmf_img.size()};
@@ -874,7 +874,7 @@ int ngp_nerf_trainer_error_map(ngp_nerf_trainer* t, int which, float* out, uint6
 
 int ngp_nerf_trainer_set_pipeline(ngp_nerf_trainer* t, int enable) {
 	if (!t) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		t->drain();
 		t->pipeline = enable != 0;
 	});
@@ -1097,6 +1097,9 @@ static void step_release_samples(ngp_nerf_trainer* t, hipStream_t s, const Step&
 static void step_train_pass(ngp_nerf_trainer* t, hipStream_t s, const Step& c) {
 	const uint32_t Bl = c.sp.Bl;
 	ProfScope ps("nerf_train_pass", s);
+	StepBatch batch;
+	batch.n = Bl; batch.input = c.coords_c; batch.input_stride = 7; batch.dL_doutput = c.dloss; batch.dL_stride = 16;
+	batch.loss_scale = 128.0f;
 	if (!c.dp || t->dp_capturable) {
 		// one HIP graph per step: forward_backward [+ the gradient all-reduce, RCCL] + optimizer. Re-record
 		// when the graph's buffers moved: the sample buffers, or any model workspace (a density-grid
@@ -1107,8 +1110,8 @@ static void step_train_pass(ngp_nerf_trainer* t, hipStream_t s, const Step& c) {
 			t->train_graph = nullptr;
 			// data parallel: the shards' dL/doutput is scaled by 128 / R_global, so the summed gradient is the
 			// 1-GPU gradient: world factor 1 in the optimizer
-			check_rc(capture_training_step_with(t->trainer, s, Bl, c.coords_c, 7, c.dloss, 16, 128.0f, 1, 1, t->exchange(),
-			                                    &t->train_graph, c.dinput, 7));
+			batch.dL_dinput = c.dinput; batch.dL_dinput_stride = 7;
+			check_rc(capture_training_step_with(t->trainer, s, batch, 1, 1, t->exchange(), &t->train_graph));
 			t->graph_in = c.coords_c;
 			t->graph_dinput = c.dinput;
 			t->graph_dl = c.dloss;
@@ -1119,7 +1122,7 @@ static void step_train_pass(ngp_nerf_trainer* t, hipStream_t s, const Step& c) {
 		else graph_launch_ctl_written(t->train_graph, s);  // the control block was written by the rollover launch
 	} else {
 		// host-callback exchange (gloo): not capturable; the same step body, launched eagerly
-		check_rc(train_step_with(t->trainer, s, Bl, c.coords_c, 7, c.dloss, 16, 128.0f, t->exchange()));
+		check_rc(train_step_with(t->trainer, s, batch, t->exchange()));
 	}
 	t->rng.advance();  // m_rng.advance() (testbed_nerf.cu:4127)
 }
@@ -1311,7 +1314,7 @@ static void step_pregenerate_grid_samples(ngp_nerf_trainer* t, const Step& c) {
 
 int ngp_nerf_train_step(ngp_nerf_trainer* t, void* stream, int get_loss, ngp_nerf_stats* st) {
 	if (!t) return NGP_INVALID;
-	NERF_TRY({
+	NGP_TRY({
 		hipStream_t s = step_stream(t, stream);
 		Step c;
 		if (t->data_epoch != t->data->ds.image_epoch) {  // an image was replaced (ngp_nerf_dataset_set_image)

@@ -6,13 +6,13 @@
 #include <cmath>
 #include <cstring>
 
+#include "abi_guard.h"
 #include "lens.h"
 #include "nerf.h"
 #include "render_common.h"
 #include "sdf_render.h"
 
 namespace ngp {
-void set_last_error(const char* msg);
 namespace sdf {
 
 using nerf::Aabb;
@@ -505,7 +505,6 @@ struct Buf {  // grows on demand; new memory is zeroed so that padded batch rows
 	}
 	~Buf() { if (p) (void)hipFree(p); }
 };
-void check_rc(int rc) { if (rc != NGP_OK) throw Error(ngp_last_error()); }
 int invalid(const char* what) {
 	ngp::set_last_error(what);
 	return NGP_INVALID;
@@ -548,13 +547,9 @@ int ngp_sdf_render_default_config(ngp_sdf_render_config* out) {
 
 int ngp_sdf_renderer_create(ngp_sdf_renderer** out) {
 	if (!out) return invalid("ngp_sdf_renderer_create: null output");
-	try {
+	NGP_TRY({
 		*out = new ngp_sdf_renderer();
-		return NGP_OK;
-	} catch (const std::exception& e) {
-		ngp::set_last_error(e.what());
-		return NGP_ERROR;
-	}
+	});
 }
 void ngp_sdf_renderer_destroy(ngp_sdf_renderer* r) { delete r; }
 
@@ -567,7 +562,7 @@ int ngp_sdf_render(ngp_sdf_renderer* r, ngp_model* model, ngp_sdf_mesh* ground_t
 	if (spp == 0 || camera->width == 0 || camera->height == 0 || (uint64_t)camera->width * camera->height > (1u << 28))
 		return invalid("ngp_sdf_render: empty or oversized frame");
 	if (camera->lens_mode > LENS_OPENCV_FISHEYE) return invalid("ngp_sdf_render: unsupported lens mode");
-	try {
+	NGP_TRY({
 		hipStream_t s = (hipStream_t)stream;
 		sdf::FrameArgs a{};
 		a.width = camera->width; a.height = camera->height;
@@ -649,23 +644,15 @@ int ngp_sdf_render(ngp_sdf_renderer* r, ngp_model* model, ngp_sdf_mesh* ground_t
 			};
 		}
 		sdf::render_frame(a, spp, ws, fn, out_rgba, out_depth, s);
-		return NGP_OK;
-	} catch (const std::exception& e) {
-		ngp::set_last_error(e.what());
-		return NGP_ERROR;
-	}
+	});
 }
 
 int ngp_sdf_iou_accumulate(void* stream, uint32_t n, const float* distances_ref, const float* distances_model, float scale_existing,
                            uint32_t* counters) {
 	if (!counters || (n > 0 && (!distances_ref || !distances_model))) return invalid("ngp_sdf_iou_accumulate: null argument");
-	try {
+	NGP_TRY({
 		sdf::iou_accumulate(n, distances_ref, distances_model, scale_existing, counters, (hipStream_t)stream);
-		return NGP_OK;
-	} catch (const std::exception& e) {
-		ngp::set_last_error(e.what());
-		return NGP_ERROR;
-	}
+	});
 }
 
 }  // extern "C"

@@ -7,16 +7,10 @@
 #include <string>
 #include <vector>
 
-#include "../../include/ngp_engine.h"
+#include "abi_guard.h"
 #include "training.h"
 
 using namespace ngp;
-
-extern "C" int ngp_trainer_training_step(ngp_trainer*, void*, uint32_t, const float*, uint32_t, const float*, uint32_t, int, float,
-                                         int, float*);
-extern "C" int ngp_trainer_optimizer_step(ngp_trainer*, void*, float);
-extern "C" const char* ngp_last_error(void);
-namespace ngp { void set_last_error(const char* msg); }
 
 namespace {
 struct Buf {
@@ -33,8 +27,6 @@ struct Buf {
 	}
 	~Buf() { if (p) (void)hipFree(p); }
 };
-void check_rc(int rc) { if (rc != 0) throw Error(ngp_last_error()); }
-hipStream_t S(void* s) { return (hipStream_t)s; }
 }  // namespace
 
 struct ngp_image {
@@ -68,27 +60,11 @@ struct ngp_sdf_mesh {
 	SdfMeshDev dev() const { return SdfMeshDev{n_triangles, tris, cdf, nodes, depth, qnodes, qtris, qdepth, blocks}; }
 };
 
-#define TRY(...)                                   \
-	try {                                          \
-		__VA_ARGS__;                               \
-		return NGP_OK;                             \
-	} catch (const std::exception& e) {            \
-		ngp::set_last_error(e.what());              \
-		return NGP_ERROR;                          \
-	}
-#define ARG(cond)                                                    \
-	do {                                                             \
-		if (!(cond)) {                                               \
-			ngp::set_last_error("invalid argument: " #cond);          \
-			return NGP_INVALID;                                      \
-		}                                                            \
-	} while (0)
-
 extern "C" {
 
 // ---- image ---------------------------------------------------------------------------------------
 int ngp_image_default_config(ngp_image_config* out) {
-	ARG(out);
+	NGP_ARG(out);
 	out->random_mode = NGP_IMAGE_STRATIFIED;  // testbed.h:875
 	out->snap_to_pixel_centers = 1;           // testbed.h:871
 	out->linear_colors = 0;                   // testbed.h:872
@@ -96,8 +72,8 @@ int ngp_image_default_config(ngp_image_config* out) {
 }
 
 int ngp_image_create(uint32_t width, uint32_t height, const float* rgba_host, ngp_image** out) {
-	ARG(out && rgba_host && width >= 2 && height >= 2);
-	TRY({
+	NGP_ARG(out && rgba_host && width >= 2 && height >= 2);
+	NGP_TRY({
 		auto img = std::make_unique<ngp_image>();
 		img->width = width;
 		img->height = height;
@@ -128,9 +104,9 @@ static ImageSampleArgs image_args(const ngp_image* img, uint32_t n, const ngp_rn
 
 int ngp_image_generate_training_samples(const ngp_image* img, void* stream, uint32_t n, ngp_rng* rng, const ngp_image_config* cfg,
                                         float* positions, float* targets) {
-	ARG(img && rng && cfg && (n == 0 || (positions && targets)));
-	ARG(cfg->random_mode == NGP_IMAGE_RANDOM || cfg->random_mode == NGP_IMAGE_STRATIFIED);
-	TRY({
+	NGP_ARG(img && rng && cfg && (n == 0 || (positions && targets)));
+	NGP_ARG(cfg->random_mode == NGP_IMAGE_RANDOM || cfg->random_mode == NGP_IMAGE_STRATIFIED);
+	NGP_TRY({
 		image_generate_samples(image_args(img, n, rng, cfg, positions, targets), S(stream));
 		HostPcg32 r{rng->state, rng->inc};
 		r.advance(2ull * n);  // generate_random_uniform advances m_rng by n_elements
@@ -140,8 +116,8 @@ int ngp_image_generate_training_samples(const ngp_image* img, void* stream, uint
 
 int ngp_image_train_step(ngp_image* img, ngp_trainer* t, void* stream, uint32_t batch, ngp_rng* rng, const ngp_image_config* cfg,
                          float* loss_sum) {
-	ARG(img && t && rng && cfg && batch > 0);
-	TRY({
+	NGP_ARG(img && t && rng && cfg && batch > 0);
+	NGP_TRY({
 		float* pos = img->positions.get<float>((size_t)batch * 2);
 		float* tgt = img->targets.get<float>((size_t)batch * 3);
 		check_rc(ngp_image_generate_training_samples(img, stream, batch, rng, cfg, pos, tgt));
@@ -154,8 +130,8 @@ int ngp_image_train_step(ngp_image* img, ngp_trainer* t, void* stream, uint32_t 
 
 // ---- SDF -----------------------------------------------------------------------------------------
 int ngp_sdf_mesh_create(uint32_t n_triangles, const float* tris_host, ngp_sdf_mesh** out) {
-	ARG(out && tris_host && n_triangles > 0);
-	TRY({
+	NGP_ARG(out && tris_host && n_triangles > 0);
+	NGP_TRY({
 		auto m = std::make_unique<ngp_sdf_mesh>();
 		m->n_triangles = n_triangles;
 		// Testbed::load_mesh (testbed_sdf.cu:1155-1172): the BVH build reorders the triangles, then the
@@ -214,8 +190,8 @@ int ngp_sdf_mesh_create(uint32_t n_triangles, const float* tris_host, ngp_sdf_me
 void ngp_sdf_mesh_destroy(ngp_sdf_mesh* m) { delete m; }
 
 int ngp_sdf_bvh_build(float* tris, uint32_t n_triangles, uint32_t n_primitives_per_leaf, void* nodes_out, uint32_t* n_nodes) {
-	ARG(tris && n_nodes && n_primitives_per_leaf >= 1);
-	TRY({
+	NGP_ARG(tris && n_nodes && n_primitives_per_leaf >= 1);
+	NGP_TRY({
 		std::vector<float> work(tris, tris + (size_t)n_triangles * 9);
 		std::vector<BvhNode> nodes;
 		build_bvh4(work.data(), n_triangles, n_primitives_per_leaf, nodes);
@@ -228,14 +204,14 @@ int ngp_sdf_bvh_build(float* tris, uint32_t n_triangles, uint32_t n_primitives_p
 }
 
 int ngp_sdf_mesh_triangles(const ngp_sdf_mesh* m, float* tris_out) {
-	ARG(m && tris_out);
-	TRY({ std::copy(m->tris_host.begin(), m->tris_host.end(), tris_out); });
+	NGP_ARG(m && tris_out);
+	NGP_TRY({ std::copy(m->tris_host.begin(), m->tris_host.end(), tris_out); });
 }
 
 int ngp_sdf_generate_training_samples(ngp_sdf_mesh* m, void* stream, uint32_t n, ngp_rng* rng, const float* aabb_min,
                                       const float* aabb_max, float stddev, float* positions, float* distances) {
-	ARG(m && rng && aabb_min && aabb_max && n % 8 == 0 && (n == 0 || (positions && distances)));
-	TRY({
+	NGP_ARG(m && rng && aabb_min && aabb_max && n % 8 == 0 && (n == 0 || (positions && distances)));
+	NGP_TRY({
 		const uint32_t n_offset = n / 8 * 3;
 		SdfSampleArgs a{};
 		a.n = n;
@@ -253,26 +229,26 @@ int ngp_sdf_generate_training_samples(ngp_sdf_mesh* m, void* stream, uint32_t n,
 }
 
 int ngp_sdf_signed_distance(ngp_sdf_mesh* m, void* stream, uint32_t n, const float* positions, float* distances) {
-	ARG(m && (n == 0 || (positions && distances)));
-	TRY({ sdf_signed_distance(m->dev(), n, positions, distances, false, S(stream)); });
+	NGP_ARG(m && (n == 0 || (positions && distances)));
+	NGP_TRY({ sdf_signed_distance(m->dev(), n, positions, distances, false, S(stream)); });
 }
 
 int ngp_sdf_signed_distance_rows(ngp_sdf_mesh* m, void* stream, uint32_t n, const float* positions, const uint32_t* rows,
                                  float* distances) {
-	ARG(m && (n == 0 || (positions && rows && distances)));
-	TRY({ sdf_signed_distance(m->dev(), n, positions, distances, false, S(stream), rows); });
+	NGP_ARG(m && (n == 0 || (positions && rows && distances)));
+	NGP_TRY({ sdf_signed_distance(m->dev(), n, positions, distances, false, S(stream), rows); });
 }
 
 int ngp_sdf_shuffle(void* stream, uint32_t n, uint32_t seed, const float* positions, const float* distances,
                     float* positions_shuffled, float* distances_shuffled) {
-	ARG(n == 0 || (positions && distances && positions_shuffled && distances_shuffled));
-	TRY({ sdf_shuffle(n, seed, positions, distances, positions_shuffled, distances_shuffled, S(stream)); });
+	NGP_ARG(n == 0 || (positions && distances && positions_shuffled && distances_shuffled));
+	NGP_TRY({ sdf_shuffle(n, seed, positions, distances, positions_shuffled, distances_shuffled, S(stream)); });
 }
 
 int ngp_sdf_train_step(ngp_trainer* t, void* stream, uint32_t n, const float* positions, const float* distances, uint32_t step,
                        float* positions_shuffled, float* distances_shuffled, float* loss_sum) {
-	ARG(t && n > 0 && positions && distances && positions_shuffled && distances_shuffled);
-	TRY({
+	NGP_ARG(t && n > 0 && positions && distances && positions_shuffled && distances_shuffled);
+	NGP_TRY({
 		// shuffle<vec3>/shuffle<float> seeded by m_training_step (testbed_sdf.cu:1295-1296), then
 		// training_step(stream, positions, distances) with the MAPE loss (configs/sdf/base.json) and
 		// the optimizer step (run_optimizer defaults to true), loss scale 128
