@@ -64,7 +64,13 @@ int ngp_debug_math_check(int which, void* stream, uint64_t* mismatches);
 
 /* ---- models (tcnn::Network<float, __half> surface) ------------------------------------------ */
 /* NerfNetwork ctor (nerf_network.h:81-112); JSON strings are the config sections the Testbed passes
- * (src/testbed.cu:4029-4042: "encoding", "dir_encoding", "network", "rgb_network"). */
+ * (src/testbed.cu:4029-4042: "encoding", "dir_encoding", "network", "rgb_network").
+ * The position encoding is tcnn's grid: "otype" HashGrid | DenseGrid | Grid (with "type" Hash | Dense), "n_levels",
+ * "n_features_per_level" (1, 2, 4, 8), "log2_hashmap_size", "base_resolution", "per_level_scale", and
+ * "interpolation": "Linear" (default) or "Smoothstep" (tcnn InterpolationType; matched without case). Smoothstep
+ * forms every corner weight from s(f) = f^2 (3 - 2f) of the cell fraction f and multiplies the input gradient's
+ * term of dimension d by s'(f_d) = 6 f_d (1 - f_d), which makes the encoding C1 across cell faces. "Nearest" is
+ * refused. ngp_model_query "grid_interpolation" reads the mode back (0 Linear, 1 Smoothstep). */
 int ngp_nerf_network_create(uint32_t n_pos_dims, uint32_t n_dir_dims, uint32_t n_extra_dims, uint32_t dir_offset,
                             const char* pos_encoding_json, const char* dir_encoding_json,
                             const char* density_network_json, const char* rgb_network_json, ngp_model** out);
@@ -107,7 +113,9 @@ int ngp_model_set_max_level(ngp_model* m, float max_level, const float* max_leve
  * "fuse_slabs", "fuse_opt", "fuse_mlp_opt", "overlap", "win_debug"  */
 int ngp_model_set_option(ngp_model* m, const char* key, double value);
 /* engine state for tests and tools: "grid_brick_levels" = how many dense levels the bucketed backward sums
- * per brick in its plan for the last batch size (0: all levels through items) */
+ * per brick in its plan for the last batch size (0: all levels through items); "grid_direct_levels",
+ * "grid_direct_part", "grid_plan_inline" likewise describe that plan; "grid_interpolation" = the encoding's
+ * interpolation (0 Linear, 1 Smoothstep); "fused_inference" = 1 when ngp_inference encodes inside the MLP kernel */
 int ngp_model_query(const ngp_model* m, const char* key, double* value);
 /* pre-size internal workspaces for batches up to n (lets callers capture steps into HIP graphs) */
 int ngp_model_reserve(ngp_model* m, uint32_t n);

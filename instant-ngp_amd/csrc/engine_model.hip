@@ -65,11 +65,14 @@ static GridDesc parse_grid(uint32_t n_dims, const Json& j) {
 	          "encoding: HashGrid and DenseGrid are implemented (got " + ot + ")");
 	const std::string type = j.string_or("type", iequals(ot, "DenseGrid") ? "Dense" : "Hash");
 	NGP_CHECK(iequals(type, "Hash") || iequals(type, "Dense"), "encoding: grid type Hash or Dense (got " + type + ")");
-	NGP_CHECK(iequals(j.string_or("interpolation", "Linear"), "Linear"), "encoding: only linear interpolation is implemented");
+	const std::string interp = j.string_or("interpolation", "Linear");
+	NGP_CHECK(iequals(interp, "Linear") || iequals(interp, "Smoothstep"),
+	          "encoding: interpolation Linear or Smoothstep (got " + interp + ")");
 	GridDesc g;
 	grid_desc_init(g, n_dims, (uint32_t)j.number_or("n_levels", 16), (uint32_t)j.number_or("n_features_per_level", 2),
 	               iequals(type, "Dense") ? GRID_LOG2_DENSE : (uint32_t)j.number_or("log2_hashmap_size", 19),
 	               (uint32_t)j.number_or("base_resolution", 16), (float)j.number_or("per_level_scale", 2.0));
+	g.interpolation = iequals(interp, "Smoothstep") ? GRID_SMOOTHSTEP : GRID_LINEAR;  // after grid_desc_init, which resets g
 	return g;
 }
 
@@ -215,12 +218,12 @@ void ngp_model::run_mlp(hipStream_t s, const MlpCall& c) {
 		a.n_matrix = (uint32_t)n_matrix(); a.density_woff = 0; a.rgb_woff = (uint32_t)mlp0_params;
 		a.dL_dsh = c.dL_dsh;
 		if (c.ex) { a.dL_ddens = c.ex->ddens; a.ddens_stride = c.ex->ddens_stride; }
-		if (mode == MLP_INFER_ENC) {
+		if (mode == MLP_INFER_ENC || mode == MLP_INFER_ENC_SMOOTH) {
 			if (c.inference) sync_inference(s);
 			a.table = pick(c.inference) + grid_offset(); a.max_level = max_level; a.gc = make_grid_const(grid);
 		}
 		ProfScope ps(mode == MLP_TRAIN ? "mlp_train" : mode == MLP_DENSITY ? "mlp_density"
-		             : mode == MLP_INFER_ENC ? "mlp_infer_enc"
+		             : (mode == MLP_INFER_ENC || mode == MLP_INFER_ENC_SMOOTH) ? "mlp_infer_enc"
 		             : mode == MLP_DENSITY_TRAIN ? "mlp_density_train" : "mlp_infer", s);
 		nerf_mlp_run(nplan, mode, a, s);
 	} else {
@@ -608,6 +611,8 @@ int ngp_model_query(const ngp_model* m, const char* key, double* value) {
 		else if (k == "grid_direct_levels") *value = m->sc_plan_n ? (double)m->sc_plan.direct_levels : 0.0;
 		else if (k == "grid_direct_part") *value = (double)make_scatter_plan(m->grid, 4096, m->scatter_opts(false)).direct_part;
 		else if (k == "grid_plan_inline") *value = m->sc_plan_n && m->sc_plan.plan_inline ? 1.0 : 0.0;
+		else if (k == "grid_interpolation") *value = (double)m->grid.interpolation;  // GridInterp: 0 Linear, 1 Smoothstep
+		else if (k == "fused_inference") *value = m->fused_inference_ok() ? 1.0 : 0.0;  // ngp_inference encodes in the MLP kernel
 		else throw Error("unknown model query: " + k);
 	});
 }
@@ -676,7 +681,7 @@ int ngp_inference(ngp_model* m, void* stream, uint32_t n, const float* input, ui
 		c.out = (f16*)output; c.out_stride = output_stride; c.out_layout = output_layout; c.inference = use_inference_params;
 		if (m->fused_inference_ok()) {
 			// the encoding never reaches HBM: the MLP kernel gathers and blends the grid levels itself
-			c.mode = MLP_INFER_ENC;
+			c.mode = m->grid.interpolation == GRID_SMOOTHSTEP ? MLP_INFER_ENC_SMOOTH : MLP_INFER_ENC;
 		} else {
 			f16* e = (f16*)m->enc.get((size_t)n * m->enc_width * sizeof(f16));
 			m->encode(S(stream), n, input, input_stride, e, m->enc_width, AoS, use_inference_params);

@@ -15,6 +15,7 @@ struct GridDesc {
 	uint32_t offsets[33] = {};  // entry offset of each level; offsets[L] = total entries
 	float scale[32] = {};       // exp2f(l*log2 b)*N_min - 1
 	uint32_t resolution[32] = {};
+	uint32_t interpolation = 0;  // GridInterp (tcnn InterpolationType): selects the kernels' SM instantiations
 	uint32_t n_entries() const { return offsets[n_levels]; }
 	uint64_t n_params() const { return (uint64_t)offsets[n_levels] * n_features; }
 };
@@ -25,6 +26,8 @@ constexpr uint32_t GRID_LOG2_DENSE = 31;
 void grid_desc_init(GridDesc& g, uint32_t D, uint32_t L, uint32_t F, uint32_t log2T, uint32_t Nmin, float b);
 
 enum Layout : uint32_t { AoS = 0, SoA = 1 };
+// tcnn InterpolationType ("interpolation" of the encoding config). Nearest is not implemented.
+enum GridInterp : uint32_t { GRID_LINEAR = 0, GRID_SMOOTHSTEP = 1 };
 
 struct GridFwdArgs {
 	uint32_t n;
@@ -298,8 +301,27 @@ __device__ __forceinline__ float corner_weight(const float* frac, uint32_t corne
 	return w;
 }
 
-template <uint32_t D>
-__device__ __forceinline__ void level_setup(const GridConst& c, uint32_t l, const float* x, float* frac, uint32_t* base) {
+// tcnn InterpolationType::Smoothstep: the fraction every corner weight is formed from becomes
+// s(f) = f^2 (3 - 2f), and the input gradient's term of dimension d takes the factor s'(f_d) = 6 f_d (1 - f_d),
+// from the untransformed fraction. The one text every kernel that forms weights compiles (SM = false: nothing).
+// fp32. The one product that feeds a subtraction, 2 f in 3 - 2 f, is exact, so fma(-2, f, 3) would give the same
+// bits, and 1 - f takes no product: contraction cannot change a bit.
+template <uint32_t D, bool SM>
+__device__ __forceinline__ void interp_frac(float* frac, float* deriv = nullptr) {
+	if constexpr (SM) {
+#pragma unroll
+		for (uint32_t d = 0; d < D; ++d) {
+			const float f = frac[d];
+			if (deriv) deriv[d] = 6.0f * f * (1.0f - f);
+			frac[d] = f * f * (3.0f - 2.0f * f);
+		}
+	}
+}
+
+// SM: the fractions come back transformed (interp_frac); users of the indices alone leave it off.
+template <uint32_t D, bool SM = false>
+__device__ __forceinline__ void level_setup(const GridConst& c, uint32_t l, const float* x, float* frac, uint32_t* base,
+                                            float* deriv = nullptr) {
 #pragma unroll
 	for (uint32_t d = 0; d < D; ++d) {
 		float p = __builtin_fmaf(c.scale[l], x[d], 0.5f);
@@ -307,6 +329,7 @@ __device__ __forceinline__ void level_setup(const GridConst& c, uint32_t l, cons
 		base[d] = (uint32_t)(int)t;
 		frac[d] = p - t;
 	}
+	interp_frac<D, SM>(frac, deriv);
 }
 
 // The brick of a 3D sample for the brick-summed dense levels 0..LD-1 (grid_scatter.hip): its cell at the

@@ -71,7 +71,7 @@ template <> struct FeatVec<2> { typedef f16x2 T; };
 template <> struct FeatVec<4> { typedef f16x4 T; };
 template <> struct FeatVec<8> { typedef f16x8 T; };
 
-template <uint32_t D, uint32_t F>
+template <uint32_t D, uint32_t F, bool SM>
 __global__ void __launch_bounds__(256) k_grid_forward(const GridConst c, const GridFwdArgs a) {
 	typedef typename FeatVec<F>::T V;
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -86,7 +86,7 @@ __global__ void __launch_bounds__(256) k_grid_forward(const GridConst c, const G
 		for (uint32_t f = 0; f < F; ++f) acc[f] = 0.f;
 		if (!((float)l >= ml + 1e-3f)) {
 			float frac[D]; uint32_t base[D];
-			level_setup<D>(c, l, x, frac, base);
+			level_setup<D, SM>(c, l, x, frac, base);
 			V v[1u << D];
 			gather_corners<D, F>(c, l, base, a.table, v);
 #pragma unroll
@@ -127,7 +127,7 @@ __global__ void __launch_bounds__(256) k_grid_forward(const GridConst c, const G
                            // F >= 4 only (C2 forward 28.9 -> 27.3 us; with 16 levels of F = 2 the index arrays cost
                            // registers: C2' step 350 -> 393 us, profiles/r03bp)
 #endif
-template <uint32_t D, uint32_t F, bool HIST>
+template <uint32_t D, uint32_t F, bool HIST, bool SM>
 __global__ void __launch_bounds__(HIST ? 512 : 256) k_grid_forward_rows(const GridConst c, const GridFwdArgs a, const GridHist h) {
 	typedef typename FeatVec<F>::T V;
 	constexpr uint32_t MAXL = 32 / F;
@@ -164,7 +164,7 @@ __global__ void __launch_bounds__(HIST ? 512 : 256) k_grid_forward_rows(const Gr
 		}
 		if (active) {
 			float frac[D]; uint32_t base[D];
-			level_setup<D>(c, l, x, frac, base);
+			level_setup<D, SM>(c, l, x, frac, base);
 			V v[1u << D];
 			if constexpr (NGP_FWD_FASTIDX && F >= 4) {
 				uint32_t cidx[1u << D];
@@ -216,7 +216,7 @@ __global__ void __launch_bounds__(HIST ? 512 : 256) k_grid_forward_rows(const Gr
 // 0..P-1]. One wave-instruction then updates a corner and its +x neighbour, which are adjacent
 // entries (dense levels) or in one aligned 8-entry group 7/8 of the time (the hash keeps x coherent:
 // prime 1), so both land in one 64-B atomic segment = one memory-side request instead of two.
-template <uint32_t D, uint32_t F>
+template <uint32_t D, uint32_t F, bool SM>
 __global__ void __launch_bounds__(256) k_grid_backward(const GridConst c, const GridBwdArgs a) {
 	constexpr uint32_t P = F >= 2 ? F / 2 : 1;
 	const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -244,7 +244,7 @@ __global__ void __launch_bounds__(256) k_grid_backward(const GridConst c, const 
 			g1 = F >= 2 ? (float)a.dL_dy[(size_t)(f0 + 1) * a.dy_stride + i] : 0.f;
 		}
 		float frac[D]; uint32_t base[D];
-		level_setup<D>(c, l, x, frac, base);
+		level_setup<D, SM>(c, l, x, frac, base);
 #pragma unroll
 		for (uint32_t q = 0; q < (1u << (D - 1)); ++q) {
 			const uint32_t k = xbit | (q << 1);
@@ -267,7 +267,7 @@ bool grid_forward_rows_ok(const GridDesc& g, const GridFwdArgs& a) {
 	       ((uintptr_t)a.out & 15) == 0;
 }
 
-template <uint32_t D>
+template <uint32_t D, bool SM>
 static void launch_fwd(uint32_t F, const GridConst& c, const GridFwdArgs& a, hipStream_t s, bool rows, const GridHist* h) {
 	const dim3 grid(div_round_up(a.n, 256)), block(256);
 	if (h) {
@@ -280,41 +280,41 @@ static void launch_fwd(uint32_t F, const GridConst& c, const GridFwdArgs& a, hip
 			kern<<<grid_h, 512, lds, s>>>(c, a, *h);
 		};
 		switch (F) {
-			case 1: go(k_grid_forward_rows<D, 1, true>); return;
-			case 2: go(k_grid_forward_rows<D, 2, true>); return;
-			case 4: go(k_grid_forward_rows<D, 4, true>); return;
-			case 8: go(k_grid_forward_rows<D, 8, true>); return;
+			case 1: go(k_grid_forward_rows<D, 1, true, SM>); return;
+			case 2: go(k_grid_forward_rows<D, 2, true, SM>); return;
+			case 4: go(k_grid_forward_rows<D, 4, true, SM>); return;
+			case 8: go(k_grid_forward_rows<D, 8, true, SM>); return;
 			default: throw Error("GridEncoding: unsupported F");
 		}
 	}
 	const GridHist none{};
 	if (rows) {
 		switch (F) {
-			case 1: k_grid_forward_rows<D, 1, false><<<grid, block, 0, s>>>(c, a, none); return;
-			case 2: k_grid_forward_rows<D, 2, false><<<grid, block, 0, s>>>(c, a, none); return;
-			case 4: k_grid_forward_rows<D, 4, false><<<grid, block, 0, s>>>(c, a, none); return;
-			case 8: k_grid_forward_rows<D, 8, false><<<grid, block, 0, s>>>(c, a, none); return;
+			case 1: k_grid_forward_rows<D, 1, false, SM><<<grid, block, 0, s>>>(c, a, none); return;
+			case 2: k_grid_forward_rows<D, 2, false, SM><<<grid, block, 0, s>>>(c, a, none); return;
+			case 4: k_grid_forward_rows<D, 4, false, SM><<<grid, block, 0, s>>>(c, a, none); return;
+			case 8: k_grid_forward_rows<D, 8, false, SM><<<grid, block, 0, s>>>(c, a, none); return;
 			default: throw Error("GridEncoding: unsupported F");
 		}
 	}
 	switch (F) {
-		case 1: k_grid_forward<D, 1><<<grid, block, 0, s>>>(c, a); break;
-		case 2: k_grid_forward<D, 2><<<grid, block, 0, s>>>(c, a); break;
-		case 4: k_grid_forward<D, 4><<<grid, block, 0, s>>>(c, a); break;
-		case 8: k_grid_forward<D, 8><<<grid, block, 0, s>>>(c, a); break;
+		case 1: k_grid_forward<D, 1, SM><<<grid, block, 0, s>>>(c, a); break;
+		case 2: k_grid_forward<D, 2, SM><<<grid, block, 0, s>>>(c, a); break;
+		case 4: k_grid_forward<D, 4, SM><<<grid, block, 0, s>>>(c, a); break;
+		case 8: k_grid_forward<D, 8, SM><<<grid, block, 0, s>>>(c, a); break;
 		default: throw Error("GridEncoding: unsupported F");
 	}
 }
 
-template <uint32_t D>
+template <uint32_t D, bool SM>
 static void launch_bwd(uint32_t F, const GridConst& c, const GridBwdArgs& a, hipStream_t s) {
 	const uint32_t P = F >= 2 ? F / 2 : 1;
 	const dim3 grid(div_round_up((uint64_t)a.n * 2 * P, 256)), block(256);
 	switch (F) {
-		case 1: k_grid_backward<D, 1><<<grid, block, 0, s>>>(c, a); break;
-		case 2: k_grid_backward<D, 2><<<grid, block, 0, s>>>(c, a); break;
-		case 4: k_grid_backward<D, 4><<<grid, block, 0, s>>>(c, a); break;
-		case 8: k_grid_backward<D, 8><<<grid, block, 0, s>>>(c, a); break;
+		case 1: k_grid_backward<D, 1, SM><<<grid, block, 0, s>>>(c, a); break;
+		case 2: k_grid_backward<D, 2, SM><<<grid, block, 0, s>>>(c, a); break;
+		case 4: k_grid_backward<D, 4, SM><<<grid, block, 0, s>>>(c, a); break;
+		case 8: k_grid_backward<D, 8, SM><<<grid, block, 0, s>>>(c, a); break;
 		default: throw Error("GridEncoding: unsupported F");
 	}
 }
@@ -323,7 +323,7 @@ static void launch_bwd(uint32_t F, const GridConst& c, const GridBwdArgs& a, hip
 // One thread per sample (the NeRF normals / SDF normals path: a render-time query, not the training hot
 // path). Corner order c = 0..2^D-1, feature order f = 0..F-1, fp32 without contraction (the oracle's
 // orc_grid_input_grad restates it in double).
-template <uint32_t D, uint32_t F>
+template <uint32_t D, uint32_t F, bool SM>
 __global__ void __launch_bounds__(256) k_input_grad(const GridConst c, const InputGradArgs a) {
 	typedef typename FeatVec<F>::T V;
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -339,9 +339,9 @@ __global__ void __launch_bounds__(256) k_input_grad(const GridConst c, const Inp
 	for (uint32_t d = 0; d < D; ++d) acc[d] = 0.f;
 	for (uint32_t l = 0; l < c.n_levels; ++l) {
 		if ((float)l >= ml + 1e-3f) continue;  // zeroed in the forward: the output does not depend on x
-		float frac[D];
+		float frac[D], deriv[D];
 		uint32_t base[D];
-		level_setup<D>(c, l, x, frac, base);
+		level_setup<D, SM>(c, l, x, frac, base, deriv);
 		float g[F];
 #pragma unroll
 		for (uint32_t f = 0; f < F; ++f) g[f] = (float)gy[l * F + f];
@@ -368,7 +368,11 @@ __global__ void __launch_bounds__(256) k_input_grad(const GridConst c, const Inp
 			}
 		}
 #pragma unroll
-		for (uint32_t d = 0; d < D; ++d) acc[d] = acc[d] + c.scale[l] * la[d];
+		for (uint32_t d = 0; d < D; ++d) {
+			// Smoothstep: dw/dx_d carries s'(frac_d); the other dimensions' weights above are already transformed
+			if constexpr (SM) acc[d] = acc[d] + c.scale[l] * deriv[d] * la[d];
+			else acc[d] = acc[d] + c.scale[l] * la[d];
+		}
 	}
 	float* o = a.out + (size_t)i * a.out_stride;
 #pragma unroll
@@ -422,14 +426,14 @@ __global__ void __launch_bounds__(256) k_input_grad(const GridConst c, const Inp
 	}
 }
 
-template <uint32_t D>
+template <uint32_t D, bool SM>
 static void launch_input_grad(uint32_t F, const GridConst& c, const InputGradArgs& a, hipStream_t s) {
 	const dim3 grid(div_round_up(a.n, 256)), block(256);
 	switch (F) {
-		case 1: k_input_grad<D, 1><<<grid, block, 0, s>>>(c, a); break;
-		case 2: k_input_grad<D, 2><<<grid, block, 0, s>>>(c, a); break;
-		case 4: k_input_grad<D, 4><<<grid, block, 0, s>>>(c, a); break;
-		case 8: k_input_grad<D, 8><<<grid, block, 0, s>>>(c, a); break;
+		case 1: k_input_grad<D, 1, SM><<<grid, block, 0, s>>>(c, a); break;
+		case 2: k_input_grad<D, 2, SM><<<grid, block, 0, s>>>(c, a); break;
+		case 4: k_input_grad<D, 4, SM><<<grid, block, 0, s>>>(c, a); break;
+		case 8: k_input_grad<D, 8, SM><<<grid, block, 0, s>>>(c, a); break;
 		default: throw Error("GridEncoding: unsupported F");
 	}
 }
@@ -438,8 +442,9 @@ void grid_input_gradient(const GridDesc& g, const InputGradArgs& a, hipStream_t 
 	if (a.n == 0) return;
 	NGP_CHECK(!a.dL_dsh || g.n_dims == 3, "input gradient: the SH direction encoding needs a 3D grid");
 	GridConst c = make_grid_const(g);
-	if (g.n_dims == 3) launch_input_grad<3>(g.n_features, c, a, stream);
-	else launch_input_grad<2>(g.n_features, c, a, stream);
+	const bool sm = g.interpolation == GRID_SMOOTHSTEP;
+	if (g.n_dims == 3) sm ? launch_input_grad<3, true>(g.n_features, c, a, stream) : launch_input_grad<3, false>(g.n_features, c, a, stream);
+	else sm ? launch_input_grad<2, true>(g.n_features, c, a, stream) : launch_input_grad<2, false>(g.n_features, c, a, stream);
 	NGP_HIP(hipGetLastError());
 }
 
@@ -447,16 +452,18 @@ void grid_forward(const GridDesc& g, const GridFwdArgs& a, hipStream_t stream, c
 	if (a.n == 0) return;
 	GridConst c = make_grid_const(g);
 	const bool rows = grid_forward_rows_ok(g, a);
-	if (g.n_dims == 3) launch_fwd<3>(g.n_features, c, a, stream, rows, hist);
-	else launch_fwd<2>(g.n_features, c, a, stream, rows, hist);
+	const bool sm = g.interpolation == GRID_SMOOTHSTEP;
+	if (g.n_dims == 3) sm ? launch_fwd<3, true>(g.n_features, c, a, stream, rows, hist) : launch_fwd<3, false>(g.n_features, c, a, stream, rows, hist);
+	else sm ? launch_fwd<2, true>(g.n_features, c, a, stream, rows, hist) : launch_fwd<2, false>(g.n_features, c, a, stream, rows, hist);
 	NGP_HIP(hipGetLastError());
 }
 
 void grid_backward(const GridDesc& g, const GridBwdArgs& a, hipStream_t stream) {
 	if (a.n == 0) return;
 	GridConst c = make_grid_const(g);
-	if (g.n_dims == 3) launch_bwd<3>(g.n_features, c, a, stream);
-	else launch_bwd<2>(g.n_features, c, a, stream);
+	const bool sm = g.interpolation == GRID_SMOOTHSTEP;
+	if (g.n_dims == 3) sm ? launch_bwd<3, true>(g.n_features, c, a, stream) : launch_bwd<3, false>(g.n_features, c, a, stream);
+	else sm ? launch_bwd<2, true>(g.n_features, c, a, stream) : launch_bwd<2, false>(g.n_features, c, a, stream);
 	NGP_HIP(hipGetLastError());
 }
 

@@ -513,7 +513,7 @@ __device__ void scatter_bricks(const GridConst& c, const BrickConst& bk, const G
 
 // INL (here and in k_sc_accumulate / k_sc_split_reduce): the inline plan's instantiation. A template flag: with the
 // inline plan's code as a runtime branch of the one kernel the k_sc_plan path measured 1 % slower at C2.
-template <uint32_t D, uint32_t F, uint32_t SC_CHUNK, uint32_t SC_ST, bool INL = false>
+template <uint32_t D, uint32_t F, uint32_t SC_CHUNK, uint32_t SC_ST, bool INL = false, bool SM = false>
 __global__ void __launch_bounds__(SC_ST) k_sc_scatter(const GridConst c, const Levels lv, const BrickConst bk, const GridBwdArgs a, uint32_t B,
                                                       uint32_t n_vb, uint32_t n_chunks, uint32_t xcd_map, const uint32_t* __restrict__ cur_t,
                                                       const uint32_t* __restrict__ lo_vb, uint16_t* __restrict__ item_idx,
@@ -609,7 +609,7 @@ __global__ void __launch_bounds__(SC_ST) k_sc_scatter(const GridConst c, const L
 			for (uint32_t f = 0; f < F; ++f) g[f] = active ? (float)a.dL_dy[(size_t)(l * F + f) * a.dy_stride + i] : 0.f;
 		}
 		float frac[D]; uint32_t base[D];
-		level_setup<D>(c, l, x, frac, base);
+		level_setup<D, SM>(c, l, x, frac, base);
 #if NGP_SC_FASTIDX
 		uint32_t cidx[NC];
 		corner_indices<D>(c, l, base, cidx);
@@ -756,7 +756,7 @@ __device__ __forceinline__ float fix_to_f32(unsigned long long q) { return (floa
 // sample), level-major, so a wave's lanes share the level. Lane l starts at feature l % F (as
 // accumulate_items: spreads a hot entry's same-address adds). Corners outside the region (positions
 // outside [0, 1]) are added to the global fallback table instead.
-template <uint32_t F>
+template <uint32_t F, bool SM>
 __device__ void accumulate_brick(const GridConst& c, const BrickConst& bk, const GridBwdArgs& a, uint32_t vb, uint32_t lo, uint32_t hi,
                                  const uint16_t* __restrict__ item_idx, const f16* __restrict__ item_val, unsigned long long* acc,
                                  unsigned long long* __restrict__ dst, uint32_t NE, const BrickFallback& fb) {
@@ -784,7 +784,7 @@ __device__ void accumulate_brick(const GridConst& c, const BrickConst& bk, const
 			for (uint32_t f = 0; f < F; ++f) g[f] = (float)a.dL_dy[(size_t)(l * F + f) * a.dy_stride + i];
 		}
 		float frac[3]; uint32_t base[3];
-		level_setup<3>(c, l, x, frac, base);
+		level_setup<3, SM>(c, l, x, frac, base);
 		const uint32_t W = bk.W[l], res = c.resolution[l];
 		uint32_t r0[3];
 		bool lo_in[3], hi_in[3];  // corner coordinate base + bit in 0..res (what the finalize's preimages cover)
@@ -928,7 +928,7 @@ __device__ __forceinline__ void store_pair(f16* grad, float* g32, size_t k, floa
 // direct level l, formed as k_sc_scatter forms its items (to_f16(w * dL/dy), nothing for a masked level) and
 // added as accumulate_items adds them (fixed point, zero skipped, lane-rotated feature order), into
 // acc[(f - f0) * (TE + 1) + entry - t0]. Corners outside the tile belong to the level's other bucket's block.
-template <uint32_t D, uint32_t F, uint32_t FT>
+template <uint32_t D, uint32_t F, uint32_t FT, bool SM>
 __device__ __forceinline__ void direct_samples(const GridConst& c, const GridBwdArgs& a, uint32_t l, uint32_t i0, uint32_t i1, uint32_t f0,
                                                uint32_t t0, uint32_t TE, unsigned long long* acc) {
 	typedef typename ValVec<F>::T V;
@@ -964,7 +964,7 @@ __device__ __forceinline__ void direct_samples(const GridConst& c, const GridBwd
 		for (uint32_t u = 0; u < U; ++u) {
 			if (!active[u]) continue;
 			float frac[D]; uint32_t base[D];
-			level_setup<D>(c, l, x[u], frac, base);
+			level_setup<D, SM>(c, l, x[u], frac, base);
 			uint32_t cidx[NC];
 			corner_indices<D>(c, l, base, cidx);
 #pragma unroll
@@ -996,7 +996,7 @@ __device__ __forceinline__ void direct_samples(const GridConst& c, const GridBwd
 // sample lands in it, so both blocks do equal work whatever the cloud) and stores its planes of both buckets' slabs.
 // F = 1: the block takes its own bucket's entries and drops the other corners. Slabs have the split parts' layout
 // [f * NE + entry], so k_sc_split_reduce sums them like a split bucket's.
-template <uint32_t D, uint32_t F>
+template <uint32_t D, uint32_t F, bool SM>
 __device__ __forceinline__ void accumulate_direct(const GridConst& c, const Levels& lv, const GridBwdArgs& a, uint32_t B, uint32_t x,
                                                   unsigned long long* acc, unsigned long long* __restrict__ scratch) {
 	const uint32_t nd_b = lv.vb_base[lv.nd], v = x % nd_b, r = x / nd_b, NE = 1u << B;
@@ -1012,7 +1012,7 @@ __device__ __forceinline__ void accumulate_direct(const GridConst& c, const Leve
 			const uint32_t TEP = n_l + 1, f0 = sub * FH;
 			for (uint32_t k = threadIdx.x; k < TEP * FH; k += blockDim.x) acc[k] = 0ull;
 			__syncthreads();
-			direct_samples<D, F, FH>(c, a, l, i0, i1, f0, 0u, n_l, acc);
+			direct_samples<D, F, FH, SM>(c, a, l, i0, i1, f0, 0u, n_l, acc);
 			__syncthreads();
 			for (uint32_t k = threadIdx.x; k < n_l * FH; k += blockDim.x) {
 				const uint32_t f = k / n_l, e = k % n_l, b = e >> B;
@@ -1024,7 +1024,7 @@ __device__ __forceinline__ void accumulate_direct(const GridConst& c, const Leve
 	const uint32_t t0 = sub << B, TE = min(NE, n_l - t0), TEP = TE + 1;
 	for (uint32_t k = threadIdx.x; k < TEP * F; k += blockDim.x) acc[k] = 0ull;
 	__syncthreads();
-	direct_samples<D, F, F>(c, a, l, i0, i1, 0u, t0, TE, acc);
+	direct_samples<D, F, F, SM>(c, a, l, i0, i1, 0u, t0, TE, acc);
 	__syncthreads();
 	unsigned long long* dst = scratch + ((size_t)v * lv.dP + r) * pstride;
 	for (uint32_t k = threadIdx.x; k < TE * F; k += blockDim.x) dst[(size_t)(k / TE) * NE + k % TE] = acc[(k / TE) * TEP + k % TE];
@@ -1042,7 +1042,7 @@ __device__ __forceinline__ void accumulate_direct(const GridConst& c, const Leve
 // DD (0, or the grid's dimensions 2 / 3): the instantiation that also holds the direct parts, blocks [0, n_direct) in
 // front of the split parts (accumulate_direct; launched only for plans with direct levels, so that plans without
 // them keep the item-only kernel and its register allocation).
-template <uint32_t F, uint32_t MODE, uint32_t DD = 0, bool INL = false>
+template <uint32_t F, uint32_t MODE, uint32_t DD = 0, bool INL = false, bool SM = false>
 __global__ void __launch_bounds__(SC_BT) k_sc_accumulate(const GridConst c, const Levels lv, const BrickConst bk, const GridBwdArgs a,
                                                          const uint32_t* __restrict__ tot,
                                                          const uint32_t* __restrict__ lo_arr, uint32_t B, uint32_t split_limit,
@@ -1060,7 +1060,7 @@ __global__ void __launch_bounds__(SC_BT) k_sc_accumulate(const GridConst c, cons
 	uint32_t bx = blockIdx.x;
 	if constexpr (DD != 0) {
 		if (bx < n_direct) {
-			accumulate_direct<DD, F>(c, lv, a, B, bx, acc, scratch);
+			accumulate_direct<DD, F, SM>(c, lv, a, B, bx, acc, scratch);
 			return;
 		}
 		bx -= n_direct;
@@ -1090,7 +1090,7 @@ __global__ void __launch_bounds__(SC_BT) k_sc_accumulate(const GridConst c, cons
 		}
 		if (pvb < part_lo || pvb >= part_hi) return;  // BwdParts: a split part of a bucket of another range
 		if (pvb - bk.vb0 < bk.NBK) {
-			accumulate_brick<F>(c, bk, a, pvb - bk.vb0, lo, hi, item_idx, item_val, acc, scratch + (size_t)slot * NE * F, NE, fb);
+			accumulate_brick<F, SM>(c, bk, a, pvb - bk.vb0, lo, hi, item_idx, item_val, acc, scratch + (size_t)slot * NE * F, NE, fb);
 			return;
 		}
 		for (uint32_t k = threadIdx.x; k < NEP * F; k += blockDim.x) acc[k] = 0ull;
@@ -1352,7 +1352,7 @@ Levels make_levels(const GridDesc& g, const ScatterPlan& p) {
 	return lv;
 }
 
-template <uint32_t D>
+template <uint32_t D, bool SM>
 void launch_backward(uint32_t F, const GridConst& c, const Levels& lv, const GridBwdArgs& a, const ScatterPlan& p, char* ws,
                      hipStream_t s, bool overwrite, uint32_t debug, const SlabJob* slab, const FusedAdam& fa, const BwdParts* parts) {
 	const uint32_t* tot = (const uint32_t*)(ws + p.off_tot);
@@ -1426,10 +1426,11 @@ void launch_backward(uint32_t F, const GridConst& c, const Levels& lv, const Gri
 		else go(sc1024, accum, splitr);
 	};
 	// plans with direct levels take the accumulate instantiation that holds the direct parts (DD = D)
-	// and plans with the inline plan the three kernels' INL instantiations
+	// and plans with the inline plan the three kernels' INL instantiations; SM (Smoothstep grids, chosen by the caller
+	// from GridDesc::interpolation) goes to the two kernels that form weights (the reduce sees sums only)
 #define NGP_SC_K(FF, MM, DDD, II)                                                                                                 \
-	by_chunk(k_sc_scatter<D, FF, 512, 512, II>, k_sc_scatter<D, FF, 1024, 1024, II>, k_sc_accumulate<FF, MM, DDD, II>,            \
-	         k_sc_split_reduce<FF, MM, II>)
+	by_chunk(k_sc_scatter<D, FF, 512, 512, II, SM>, k_sc_scatter<D, FF, 1024, 1024, II, SM>,                                      \
+	         k_sc_accumulate<FF, MM, DDD, II, SM>, k_sc_split_reduce<FF, MM, II>)
 #define NGP_SC_M(FF, MM)                                     \
 	if (n_direct && p.plan_inline) NGP_SC_K(FF, MM, D, true); \
 	else if (n_direct) NGP_SC_K(FF, MM, D, false);            \
@@ -1663,8 +1664,10 @@ void grid_backward_sorted(const GridDesc& g, const GridBwdArgs& b, const Scatter
 	const GridConst c = make_grid_const(g);
 	const Levels lv = make_levels(g, p);
 	const FusedAdam fa = fused ? *fused : FusedAdam{};
-	if (g.n_dims == 3) launch_backward<3>(g.n_features, c, lv, b, p, (char*)workspace, s, overwrite, debug, slab, fa, parts);
-	else launch_backward<2>(g.n_features, c, lv, b, p, (char*)workspace, s, overwrite, debug, slab, fa, parts);
+	auto go = [&](auto launch) { launch(g.n_features, c, lv, b, p, (char*)workspace, s, overwrite, debug, slab, fa, parts); };
+	const bool sm = g.interpolation == GRID_SMOOTHSTEP;
+	if (g.n_dims == 3) sm ? go(launch_backward<3, true>) : go(launch_backward<3, false>);
+	else sm ? go(launch_backward<2, true>) : go(launch_backward<2, false>);
 }
 
 }  // namespace ngp

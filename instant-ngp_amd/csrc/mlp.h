@@ -95,7 +95,8 @@ MlpPlan make_mlp_plan(uint32_t enc_width, uint32_t width, uint32_t hidden, uint3
 void prepare_frags(const FragDesc* descs_dev, uint32_t n_frags, const f16* params, f16x8* frags, hipStream_t s);
 
 enum MlpMode : uint32_t { MLP_INFER = 0, MLP_TRAIN = 1, MLP_DENSITY = 2, MLP_INFER_ENC = 3,
-                          MLP_DENSITY_TRAIN = 5 };  // density network forward + backward only (NeRF)
+                          MLP_DENSITY_TRAIN = 5,  // density network forward + backward only (NeRF)
+                          MLP_INFER_ENC_SMOOTH = 6 };  // MLP_INFER_ENC of a Smoothstep grid (GridDesc::interpolation)
 // MLP_INFER_ENC is fused for 3D grids with 4 levels of 4 features (one 16-wide encoding step: C2)
 // internal output layout of the density network: row 0 only, as a flat array of n (the density grid update
 // reads nothing else)

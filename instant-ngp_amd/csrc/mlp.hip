@@ -455,7 +455,8 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(1, 
 	constexpr bool DTRAIN = MODE == MLP_DENSITY_TRAIN;  // density network forward + backward only
 	constexpr bool TRAIN = MODE == MLP_TRAIN || DTRAIN;
 	constexpr bool DENSITY = MODE == MLP_DENSITY;
-	constexpr bool FUSE = MODE == MLP_INFER_ENC;
+	constexpr bool FUSE = MODE == MLP_INFER_ENC || MODE == MLP_INFER_ENC_SMOOTH;
+	constexpr bool SMOOTH = MODE == MLP_INFER_ENC_SMOOTH;  // the grid's Smoothstep interpolation (grid.h interp_frac)
 	static_assert(!FUSE || ES == 1, "fused encoding: one 16-wide encoding step");
 	constexpr int NFRAG = TRAIN ? Lay::N_ALL : (DENSITY ? Lay::F_R0 : Lay::N_FWD);
 	extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -540,6 +541,7 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(1, 
 					base[d] = (uint32_t)(int)t;
 					gfrac[j][d] = p - t;
 				}
+				interp_frac<3, SMOOTH>(gfrac[j]);
 				fuse_gather_level(a.table + (size_t)lv_off[j] * 4, base, lv_res[j], lv_T[j], lv_hashed[j], lv_active[j], graw[j]);
 			}
 		} else {
@@ -1228,6 +1230,7 @@ void nerf_mlp_run(const NerfMlpPlan& p, MlpMode mode, const NerfMlpArgs& a, hipS
 		case MLP_TRAIN: dispatch_nerf<MLP_TRAIN>(p, a, s); break;
 		case MLP_DENSITY: dispatch_nerf<MLP_DENSITY>(p, a, s); break;
 		case MLP_INFER_ENC: dispatch_nerf_fused<MLP_INFER_ENC>(p, a, s); break;
+		case MLP_INFER_ENC_SMOOTH: dispatch_nerf_fused<MLP_INFER_ENC_SMOOTH>(p, a, s); break;
 		case MLP_DENSITY_TRAIN: dispatch_nerf<MLP_DENSITY_TRAIN>(p, a, s); break;
 	}
 }

@@ -260,6 +260,8 @@ PYBIND11_MODULE(pyngp, m) {
 		     py::arg("json"), py::arg("config_base_path") = "", "Reload the network from a json object.")
 		.def("n_params", &Testbed::n_params, "Number of trainable parameters")
 		.def("n_encoding_params", &Testbed::n_encoding_params, "Number of trainable parameters in the encoding")
+		.def_property_readonly("grid_interpolation", &Testbed::grid_interpolation,
+		                       "The grid encoding's interpolation, from the network config: \"Linear\" or \"Smoothstep\"")
 		.def("save_snapshot", &Testbed::save_snapshot, py::arg("path"), py::arg("include_optimizer_state") = false,
 		     py::arg("compress") = true, py::call_guard<py::gil_scoped_release>(),
 		     "Save a snapshot of the currently trained model (.ingp: gzip'd msgpack).")

@@ -410,6 +410,13 @@ public:
 		check(ngp_model_param_layout(m_model, &lo), "ngp_model_param_layout");
 		return lo.grid_params;
 	}
+	// the encoding's "interpolation" as the model parsed it from the network config ("" before reset_network)
+	std::string grid_interpolation() const {
+		if (!m_model) return "";
+		double v = 0.0;
+		check(ngp_model_query(m_model, "grid_interpolation", &v), "ngp_model_query");
+		return v == 1.0 ? "Smoothstep" : "Linear";
+	}
 
 	// ---- training -----------------------------------------------------------------------------------
 	// Testbed::train (testbed.cu:4285-4370); the loss is read back every 16 steps, as the reference does

@@ -125,10 +125,17 @@ class Model:
 
     def query(self, key):
         """engine state (ngp_model_query): "grid_brick_levels", "grid_direct_levels", "grid_direct_part" (samples per
-        direct part), "grid_plan_inline" (the current plan runs without k_sc_plan)"""
+        direct part), "grid_plan_inline" (the current plan runs without k_sc_plan), "grid_interpolation" (0 Linear,
+        1 Smoothstep), "fused_inference" (inference encodes inside the MLP kernel)"""
         v = C.c_double()
         check(lib().ngp_model_query(self.handle, key.encode(), C.byref(v)))
         return v.value
+
+    @property
+    def interpolation(self):
+        """The grid encoding's "interpolation" (tcnn InterpolationType): "Linear" or "Smoothstep". Read-only: it is
+        fixed by the encoding config the network was created with."""
+        return ("Linear", "Smoothstep")[int(self.query("grid_interpolation"))]
 
     def reserve(self, n):
         check(lib().ngp_model_reserve(self.handle, n))
